@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Headline benchmark: samples/sec (one sample = one 7-camera frame, end to end) at VoV-99, 640x960 (BASELINE.json).
 
-  python bench.py --gpus 1 --steps 100 --warmup 5
+  python bench.py --gpus 1 --steps 100 --warmup 5 [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 One "step" = one full frame through the HIP engine: 7 x (3,640,960) synthetic images resident in HBM -> VoV-99 -> FPN ->
@@ -13,11 +13,14 @@ Prints ONE JSON line on rank 0.
 
 Headline (`value`, `dtype`, `ms_per_step`): the engine that MEETS the north-star logit tolerance (bf16x3: every
 conv product as three bf16 MFMAs on pair-stored activations, exact-fp32 decoder; `parity.meets_tolerance` true) under the REFERENCE's
-timing protocol (tools/analysis_tools/benchmark.py:84-111): K frames, a device sync (and a barrier for N > 1) before
-and after EVERY frame, between the barrier + sync that bracket the timed region -- `value` = K / that time.  Side blocks of the same
-run: `protocol.pipelined` (the same engine, K frames issued back to back with the frame pipeline on: throughput of a stream),
-`protocol.sync_per_frame_groups` (the frame's cameras as two groups on parallel streams), and `fast_mode` (the bf16 engine -- BASELINE
-configs[1]'s dtype, 40x outside the tolerance -- under both protocols; `--no-fast-mode` skips it).
+timing protocol (tools/analysis_tools/benchmark.py:84-111): K = --steps frames, a device sync (and a barrier for N > 1)
+before and after EVERY frame, between the barrier + sync that bracket the timed region -- `value` = K / that time, `ms_per_step` = that
+time / K.  A plain run does only that: set up, warm up, time the K frames, print the line.  `--dump-outputs DIR` also writes what the
+last timed frame returned as DIR/<name>.npy (same arguments, same inputs: two builds can be compared output for output).
+`--full` adds the side blocks: `protocol.pipelined` (the same engine, K frames issued back to back with the frame pipeline on:
+throughput of a stream), `protocol.sync_per_frame_groups` (the frame's cameras as two groups on parallel streams),
+`protocol.two_streams_pipelined`, the kernel rooflines, `cpu_baseline` + `parity` (the oracle on the host), and `fast_mode` (the bf16
+engine -- BASELINE configs[1]'s dtype, 40x outside the tolerance -- under both protocols; `--no-fast-mode` skips it).
 """
 import argparse
 import json
@@ -41,6 +44,7 @@ MFMA_PEAK = {"bf16": 2.5e15, "fp32": 157.3e12,     # dense FLOP/s (same guide)
              "bf16x3": 2.5e15 / 3}                 # split mode: three bf16 MFMAs per useful product
 BACKBONE_FLOP_PER_CAM = 2 * 201.87e9   # VoV-99 @ 640x960
 AGG_KERNEL = "aggregate_v8_kernel"
+DUMP_BYTES = 64 << 20      # --dump-outputs: bytes written at most
 K_PROP = 92                # adaptive-query count fixed at 644 = 7 x 92 (static shapes)
 
 
@@ -210,11 +214,12 @@ def agg_traffic_live(fp32_rows, timeout_s=150):
 
 
 def measure(args, precision, steps, warmup, world, rank, dev, sharded, dist, kernel_timings=True, proposals="topk", latency_runner=True,
-            two_streams=False):
+            two_streams=False, full=True, dump=False):
     """Build an engine of `precision` and run, in this order: the parity frames; region A -- the reference's protocol, K frames with a
     device sync (+ barrier) around every one, on the engine in its single-frame configuration (one hipGraph per frame, no frame
-    overlap, tiles tuned for launches alone); region B -- K frames back to back with the frame pipeline on; the camera-group latency
-    runner; the per-kernel roofline timings.  Returns a dict of raw figures."""
+    overlap, tiles tuned for launches alone); with `full` also region B -- K frames back to back with the frame pipeline on; the
+    camera-group latency runner; the per-kernel roofline timings.  `dump`: keep region A's last outputs on the host (res["outputs"]).
+    Returns a dict of raw figures."""
     from far3d_amd import engine, ops, synth, weights
     from far3d_amd import dist as fdist
     # proposals: "topk" = 92 best peaks per camera (static, SURVEY 8(d): 644 adaptive queries); "threshold" = the reference's rule
@@ -266,6 +271,8 @@ def measure(args, precision, steps, warmup, world, rank, dev, sharded, dist, ker
     for fi in range(2):
         o = runner.forward_frame(*frames[fi])
         runner.wait_outputs()
+        if not full:        # no parity block to feed: the two frames are the scene start and the graph capture
+            continue
         cnt = o["sel_cnt"].cpu().numpy() if "sel_cnt" in o else None
         sel = [(n, int(i)) for n in range(7) for i in o["sel_idx"][n, :cnt[n]].cpu().numpy()] if cnt is not None else []
         eng_frames.append(dict(logits=o["all_cls_scores"].float().cpu().clone(), sel=sel,
@@ -303,6 +310,14 @@ def measure(args, precision, steps, warmup, world, rank, dev, sharded, dist, ker
     N, S, C = out["feat_flatten"].shape
     lg = out["all_cls_scores"]          # fixed-capacity proposal mode: the rows without a query carry -inf logits by construction
     assert not torch.isnan(lg).any() and not (lg == float("inf")).any(), "non-finite logits"
+    # the last timed frame's outputs, copied before anything else reuses the engine's buffers
+    outputs = output_arrays(out) if dump else None
+    if not full:
+        res = dict(proposal_stats(out), steps=steps, dt_sync=dt_sync, per_frame=per_frame, stage_ms=stage_ms, A=A, prec=dict(eng.prec), cfg=cfg,
+                   outputs=outputs)
+        del eng, runner, frames, out
+        torch.cuda.empty_cache()
+        return res
 
     # ---------------------------------------------------------------- region B: frames back to back, frame pipeline on
     # frames of one stream are software-pipelined: the per-camera stages of the next frames overlap the head of frame i (engine.py);
@@ -445,9 +460,7 @@ def measure(args, precision, steps, warmup, world, rank, dev, sharded, dist, ker
         eng.tile_table = keep_table
     except Exception as e:   # noqa: BLE001
         timing_error = "%s: %s" % (type(e).__name__, str(e).splitlines()[0] if str(e) else "")
-    n_adapt = int(out["num_adaptive_dev"].item()) if out.get("num_adaptive_dev") is not None else int(out["num_adaptive"])
-    overflow = bool(int(out["proposal_overflow"].item())) if out.get("proposal_overflow") is not None else False
-    res = dict(n_adaptive=n_adapt, proposal_overflow=overflow, steps=steps, dt=dt, dt_sync=dt_sync, dev_ms=dev_ms, per_frame=per_frame, lat_groups=lat_groups,
+    res = dict(proposal_stats(out), outputs=outputs, steps=steps, dt=dt, dt_sync=dt_sync, dev_ms=dev_ms, per_frame=per_frame, lat_groups=lat_groups,
                two_streams=two,
                A=A, N=N, S=S, C=C, eng_frames=eng_frames, agg_ms=agg_ms, bb_ms=bb_ms, stage_ms=stage_ms,
                timing_error=timing_error, prec=dict(eng.prec), pipeline=pipeline_on, cfg=cfg, tile_table=tile_table_pipelined,
@@ -457,6 +470,57 @@ def measure(args, precision, steps, warmup, world, rank, dev, sharded, dist, ker
     del eng, runner, frames, out
     torch.cuda.empty_cache()
     return res
+
+
+def proposal_stats(out):
+    """Adaptive queries of a frame's outputs and whether the fixed proposal capacity overflowed (threshold mode)."""
+    n_adapt = int(out["num_adaptive_dev"].item()) if out.get("num_adaptive_dev") is not None else int(out["num_adaptive"])
+    overflow = bool(int(out["proposal_overflow"].item())) if out.get("proposal_overflow") is not None else False
+    return dict(n_adaptive=n_adapt, proposal_overflow=overflow)
+
+
+def output_arrays(outs):
+    """The arrays a caller of forward_frame receives, on the host, by name (nested dicts / lists flattened to dotted names):
+    float64 and integer tensors as float64, every other tensor as float32, Python numbers as 0-d float64."""
+    import numpy as np
+    flat = {}
+
+    def walk(name, v):
+        if isinstance(v, dict):
+            for k in sorted(v):
+                walk("%s.%s" % (name, k) if name else str(k), v[k])
+        elif isinstance(v, (list, tuple)):
+            for i, x in enumerate(v):
+                walk("%s.%d" % (name, i), x)
+        elif isinstance(v, torch.Tensor):
+            wide = v.dtype == torch.float64 or not (v.is_floating_point() or v.dtype == torch.bool)
+            flat[name] = v.detach().to("cpu", torch.float64 if wide else torch.float32).numpy()
+        elif isinstance(v, (bool, int, float)):
+            flat[name] = np.asarray(v, dtype=np.float64)
+
+    walk("", outs)
+    return flat
+
+
+def write_outputs(out_dir, arrays, budget=DUMP_BYTES):
+    """--dump-outputs: one DIR/<name>.npy per array.  An array of more than `cap` elements is replaced by a fixed seeded sample of
+    its flattened elements (the same positions in every run), `cap` halved until everything fits in `budget` bytes."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    cap = 1 << 20
+    while True:
+        kept = {}
+        for k, a in arrays.items():
+            if a.size > cap:
+                pos = np.sort(np.random.default_rng(0).choice(a.size, size=cap, replace=False))
+                a = a.reshape(-1)[pos]
+            kept[k] = a
+        if sum(a.nbytes + 256 for a in kept.values()) <= budget or cap == 1:      # + the .npy header
+            break
+        cap //= 2
+    for k, a in kept.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    return sum(a.nbytes for a in kept.values())
 
 
 def agg_roofline(args, res, traffic=None, traffic_src=None, live=False, committed=None, committed_src=None):
@@ -543,7 +607,7 @@ def main():
     ap.add_argument("--no-pmc", action="store_true", help="do not measure roofline.traffic with rocprofv3 --pmc passes (two short sub-runs); the "
                     "committed in-frame figure of the evidence set is reported instead")
     ap.add_argument("--no-fast-mode", "--no-in-tolerance", dest="fast_mode", action="store_false",
-                    help="skip the second engine of the default run (the bf16 `fast_mode` block); --no-in-tolerance is the flag's old name")
+                    help="--full: skip the second engine (the bf16 `fast_mode` block); --no-in-tolerance is the flag's old name")
     ap.add_argument("--eager", action="store_true", help="launch kernels one by one instead of replaying a hipGraph")
     ap.add_argument("--no-pipeline", action="store_true", help="single GPU: do not overlap the camera stages of frame i+1 with the head of frame i")
     ap.add_argument("--agg-variant", type=int, default=0, help="far3d_aggregate_forward kernel variant (A/B timing)")
@@ -566,6 +630,13 @@ def main():
                     "since round 5; bf16 decoder only)")
     ap.add_argument("--fused-rows", dest="fused_rows", action="store_true", help="(default) kept so that round 4's command lines still parse")
     ap.set_defaults(fused_rows=True, fast_mode=True)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: protocol.pipelined and the other protocols, the kernel rooflines (with "
+                         "their rocprofv3 --pmc passes), the bf16 `fast_mode` engine, the CPU baseline and the parity against the oracle.  "
+                         "Without it the run sets up, warms up, times the --steps frames of `value` and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed frames, write the outputs of the last one (what forward_frame returns, float32 / float64; a fixed "
+                         "seeded sample of an array beyond 2^20 elements, %d MB at most) as DIR/<name>.npy" % (DUMP_BYTES >> 20))
     ap.add_argument("--allow-shared-gpu", action="store_true",
                     help="N ranks on fewer than N GPUs (test rig only): ranks share devices and exchange over gloo; the line says so and "
                          "is not a scaling measurement")
@@ -608,16 +679,25 @@ def main():
     sharded = world > 1 and args.mode == "sharded"
 
     res = measure(args, args.precision, args.steps, args.warmup, world, rank, dev, sharded, dist, proposals=args.proposals,
-                  two_streams=args.two_streams and world == 1)
-    # The headline engine is the one that MEETS the north-star logit tolerance (bf16x3).  The same run also times the bf16 engine --
+                  two_streams=args.full and args.two_streams and world == 1, full=args.full, dump=args.dump_outputs is not None and rank == 0)
+    # The headline engine is the one that MEETS the north-star logit tolerance (bf16x3).  A --full run also times the bf16 engine --
     # BASELINE configs[1]'s dtype, ~40x outside the tolerance -- same workload, same two protocols, and reports it as `fast_mode`.
     res_fast = None
-    if world == 1 and args.precision == "bf16x3" and args.fast_mode and not args.eager and args.proposals == "topk":
+    if args.full and world == 1 and args.precision == "bf16x3" and args.fast_mode and not args.eager and args.proposals == "topk":
         res_fast = measure(args, "bf16", args.steps, args.warmup, world, rank, dev, sharded, dist, kernel_timings=True)
 
     if rank == 0:
+        if args.dump_outputs is not None:
+            write_outputs(args.dump_outputs, res["outputs"])
+
         def rates(r):
             pf = r["per_frame"]
+            sync_per_frame = {"frames": len(pf), "mean_ms": sum(pf) / len(pf), "p50_ms": pf[len(pf) // 2],
+                              "samples_per_s_mean": 1e3 * len(pf) / sum(pf),
+                              "what": "reference protocol (tools/analysis_tools/benchmark.py:84-111): device sync before and after every frame "
+                                      "-> `value`; one hipGraph per frame, no frame overlap"}
+            if "dt" not in r:                 # not a --full run: region A alone
+                return {"sync_per_frame": sync_per_frame}
             return {"pipelined": {"frames": r["steps"], "mean_ms": r["dt"] / r["steps"] * 1e3, "samples_per_s": r["steps"] * rep / r["dt"],
                                   "p50_ms_device_events": r["dev_ms"][len(r["dev_ms"]) // 2], "p50_samples_per_s": 1e3 / r["dev_ms"][len(r["dev_ms"]) // 2],
                                   "what": "frames issued back to back, ONE sync at each end: the throughput of a stream of frames (not `value`)",
@@ -626,25 +706,11 @@ def main():
                                   "frame_overlap_what": "the per-camera stages of the next frames (one frame per camera stream, high priority) run "
                                                         "concurrently while the head of frame i is in flight (one buffer set per frame in flight, head "
                                                         "graphs ordered on one stream: results identical to the unpipelined engine)"},
-                    "sync_per_frame": {"frames": len(pf), "mean_ms": sum(pf) / len(pf), "p50_ms": pf[len(pf) // 2],
-                                       "samples_per_s_mean": 1e3 * len(pf) / sum(pf),
-                                       "what": "reference protocol (tools/analysis_tools/benchmark.py:84-111): device sync before and after every frame "
-                                               "-> `value`; one hipGraph per frame, no frame overlap"}}
-        dt, dev_ms, per_frame, A, N, S, C, cfg = (res[k] for k in ("dt", "dev_ms", "per_frame", "A", "N", "S", "C", "cfg"))
+                    "sync_per_frame": sync_per_frame}
+        A = res["A"]
         rep = world if (world > 1 and not sharded) else 1        # replicas: every rank ran its own stream of frames
         samples = args.steps * rep
         dt_sync = res["dt_sync"]
-        # HBM traffic of the dominant kernel: measured by this run when rocprofv3 is there (isolated launches on benchmark-size operands),
-        # with the committed IN-FRAME figure of the evidence set beside it; without rocprofv3 the committed figure alone, labelled
-        fp32_rows = res["prec"]["value"] != torch.bfloat16
-        committed, committed_src = agg_traffic(fp32_rows=fp32_rows)
-        traffic, traffic_src, live = committed, committed_src, False
-        if world == 1 and not args.no_pmc:
-            tl, src = agg_traffic_live(fp32_rows)
-            if tl is not None:
-                traffic, traffic_src, live = tl, src, True
-            else:
-                traffic_src = "%s; live measurement unavailable: %s" % (committed_src, src)
         line = {
             "metric": "samples/sec (7-cam frame) end-to-end @ VoV-99 640x960",
             "value": samples / dt_sync, "unit": "samples/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -667,11 +733,23 @@ def main():
                                                                        "%d independent scene streams (replicas, no collective)" % world),
                        "precision_assignment": {k: str(v).replace("torch.", "") for k, v in res["prec"].items()},
                        "weights": "seeded random (far3d_amd.weights.init_state_dict, seed 0)", "commit": build_commit()},
-            "protocol": rates(res),
-            "roofline": agg_roofline(args, res, traffic, traffic_src, live, committed, committed_src),
-            "roofline_backbone": backbone_roofline(res),
+            "protocol": rates(res), "full": bool(args.full),
         }
-        if res["timing_error"]:
+        if args.full:
+            # HBM traffic of the dominant kernel: measured by this run when rocprofv3 is there (isolated launches on benchmark-size operands),
+            # with the committed IN-FRAME figure of the evidence set beside it; without rocprofv3 the committed figure alone, labelled
+            fp32_rows = res["prec"]["value"] != torch.bfloat16
+            committed, committed_src = agg_traffic(fp32_rows=fp32_rows)
+            traffic, traffic_src, live = committed, committed_src, False
+            if world == 1 and not args.no_pmc:
+                tl, src = agg_traffic_live(fp32_rows)
+                if tl is not None:
+                    traffic, traffic_src, live = tl, src, True
+                else:
+                    traffic_src = "%s; live measurement unavailable: %s" % (committed_src, src)
+            line["roofline"] = agg_roofline(args, res, traffic, traffic_src, live, committed, committed_src)
+            line["roofline_backbone"] = backbone_roofline(res)
+        if res.get("timing_error"):
             line["kernel_timing_error"] = res["timing_error"]
         if res.get("lat_groups"):
             line["protocol"]["sync_per_frame_groups"] = res["lat_groups"]
@@ -690,7 +768,7 @@ def main():
                 return None
             return o
         orc = None
-        if world == 1 and not args.no_cpu_baseline and args.proposals == "topk":
+        if args.full and world == 1 and not args.no_cpu_baseline and args.proposals == "topk":
             line["cpu_baseline"], orc = oracle_frames(2)
             line["parity"] = parity_block(args.precision, res["eng_frames"], orc)
             line["meets_tolerance"] = line["parity"]["meets_tolerance"]

@@ -40,3 +40,19 @@ def test_bench_gpus2_without_gpus_says_so(hip_lib):
     assert r.returncode == 0
     assert line is not None and line["value"] is None and line["n_gpus"] == 2 and "needs 2 visible GPUs" in line["error"]
     assert "needs 2 visible GPUs" in r.stderr
+
+
+def test_bench_plain_run_dumps_its_outputs(hip_lib, tmp_path):
+    """A plain `bench.py --gpus 1` run: the headline line alone (no --full side blocks), --steps timed frames, and with --dump-outputs
+    the last timed frame's outputs as float32 / float64 .npy files."""
+    import numpy as np
+    r, line = _run(["--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path)])
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert line is not None, r.stdout[-2000:]
+    assert line["steps"] == 3 and line["protocol"]["sync_per_frame"]["frames"] == 3 and line["dtype"] == "bf16x3"
+    assert line["value"] > 0 and abs(line["value"] * line["ms_per_step"] * 1e-3 - 1.0) < 1e-6
+    assert not line["full"] and not any(k in line for k in ("roofline", "cpu_baseline", "parity", "fast_mode"))
+    arrays = {f[:-4]: np.load(tmp_path / f) for f in os.listdir(tmp_path)}
+    assert arrays["all_cls_scores"].shape == (6, 1, 1544, 26) and np.isfinite(arrays["all_cls_scores"]).all()
+    assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+    assert sum(os.path.getsize(tmp_path / (k + ".npy")) for k in arrays) <= 64 << 20

@@ -136,6 +136,37 @@ def test_bench_launch_plan():
     assert cmd[-6:] == ["--gpus", "8", "--steps", "20", "--warmup", "5"] and cmd[-7].endswith("bench.py")
 
 
+def test_bench_dump_outputs(tmp_path):
+    """`bench.py --dump-outputs DIR`: every array of the frame's output dict by dotted name, float32 / float64 only, large arrays as
+    the same seeded sample in every run, the whole dump within its byte budget."""
+    import importlib.util
+    import os
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("far3d_bench", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    g = torch.Generator().manual_seed(0)
+    outs = dict(all_cls_scores=torch.randn(6, 1, 50, 26, generator=g).bfloat16(), feat_flatten=torch.randn(3, 1 << 19, generator=g),
+                result=dict(labels_3d=torch.arange(7), keep=torch.ones(7, dtype=torch.bool)), fpn=[torch.randn(2, 3, generator=g)],
+                timestamp=torch.zeros(2, dtype=torch.float64), num_adaptive=644, num_adaptive_dev=None, tag="x")
+    arrays = bench.output_arrays(outs)
+    assert sorted(arrays) == ["all_cls_scores", "feat_flatten", "fpn.0", "num_adaptive", "result.keep", "result.labels_3d", "timestamp"]
+    assert {k: a.dtype for k, a in arrays.items()} == {"all_cls_scores": np.float32, "feat_flatten": np.float32, "fpn.0": np.float32,
+                                                         "num_adaptive": np.float64, "result.keep": np.float32, "result.labels_3d": np.float64,
+                                                         "timestamp": np.float64}
+    assert np.array_equal(arrays["all_cls_scores"], outs["all_cls_scores"].float().numpy())
+    budget = 3 << 20
+    bench.write_outputs(str(tmp_path / "a"), arrays, budget=budget)
+    bench.write_outputs(str(tmp_path / "b"), arrays, budget=budget)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted(k + ".npy" for k in arrays)
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= budget
+    a, b = (np.load(tmp_path / d / "feat_flatten.npy") for d in "ab")
+    assert a.size < arrays["feat_flatten"].size and np.array_equal(a, b) and np.isin(a, arrays["feat_flatten"]).all()
+    assert np.array_equal(np.load(tmp_path / "a" / "all_cls_scores.npy"), arrays["all_cls_scores"])
+
+
 def test_ida_matrix_against_a_stepwise_float32_chain():
     """ida_matrix is a float64 closed form rounded once; the reference (datasets/pipelines/custom_pipeline.py:294-311)
     composes scale, crop, flip and rotation step by step in float32.  Equal when rotate == 0 (the reference's only supported

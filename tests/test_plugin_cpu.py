@@ -8,7 +8,8 @@ import torch
 from far3d_amd import config, plugin, weights
 from tests.conftest import ROOT
 
-REF_CFG = "/root/reference/projects/configs/far3d.py"
+# the reference's config file (projects/configs/far3d.py) as data: its `model` / `point_cloud_range` entries (tools/gen_golden_config.py)
+REF_CFG = os.path.join(ROOT, "tests", "golden", "reference_config.json")
 
 
 def test_default_cfg_builds_and_matches_reference_manifest():
@@ -21,9 +22,11 @@ def test_default_cfg_builds_and_matches_reference_manifest():
     assert cfg["num_cams"] == 7 and cfg["num_query"] == 644 and cfg["num_propagated"] == 256 and cfg["max_num"] == 300
 
 
-@pytest.mark.skipif(not os.path.exists(REF_CFG), reason="reference checkout only exists in the build container")
-def test_reference_config_file_loads_unchanged():
-    cfg = config.load_config(REF_CFG)
+def test_reference_config_file_loads_unchanged(tmp_path):
+    # written back as a python config file and loaded through the same loader as the original
+    p = tmp_path / "far3d.py"
+    p.write_text("".join("%s = %r\n" % kv for kv in sorted(json.load(open(REF_CFG)).items())))
+    cfg = config.load_config(str(p))
     assert cfg.model.type == "Far3D" and cfg.point_cloud_range[3] == 152.4
     det = plugin.build_detector(cfg.model)
     ours = plugin.build_detector(config.default_model_cfg())

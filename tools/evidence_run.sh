@@ -10,10 +10,10 @@ if [ "${TESTS:-1}" = "1" ]; then
   timeout 2400 python -m pytest tests -m gpu -q -x --durations=12 2>&1 | tail -30 | tee $O/pytest_gpu.txt
   python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -3 | tee $O/smoke.txt
 fi
-timeout 900 python bench.py 2>$O/bench.err | tail -1 > $O/bench.json; cut -c1-300 $O/bench.json
-timeout 600 python bench.py --precision fp32 --steps 20 --no-cpu-baseline --no-pmc --no-two-streams 2>$O/bench_fp32.err | tail -1 > $O/bench_fp32.json; cut -c1-200 $O/bench_fp32.json
-timeout 600 python bench.py --precision bf16 --steps 50 --no-cpu-baseline --no-pmc --no-two-streams 2>$O/bench_bf16.err | tail -1 > $O/bench_bf16.json; cut -c1-200 $O/bench_bf16.json
-timeout 600 python bench.py --proposals threshold --capacity 4096 --steps 30 --no-cpu-baseline --no-pmc 2>$O/bench_thr.err | tail -1 > $O/bench_threshold.json; cut -c1-200 $O/bench_threshold.json
+timeout 900 python bench.py --full 2>$O/bench.err | tail -1 > $O/bench.json; cut -c1-300 $O/bench.json
+timeout 600 python bench.py --full --precision fp32 --steps 20 --no-cpu-baseline --no-pmc --no-two-streams 2>$O/bench_fp32.err | tail -1 > $O/bench_fp32.json; cut -c1-200 $O/bench_fp32.json
+timeout 600 python bench.py --full --precision bf16 --steps 50 --no-cpu-baseline --no-pmc --no-two-streams 2>$O/bench_bf16.err | tail -1 > $O/bench_bf16.json; cut -c1-200 $O/bench_bf16.json
+timeout 600 python bench.py --full --proposals threshold --capacity 4096 --steps 30 --no-cpu-baseline --no-pmc 2>$O/bench_thr.err | tail -1 > $O/bench_threshold.json; cut -c1-200 $O/bench_threshold.json
 timeout 300 python tools/stage_times.py bf16 > $O/stage_times_bf16.txt 2>&1; tail -16 $O/stage_times_bf16.txt
 timeout 300 python tools/stage_times.py bf16x3 > $O/stage_times_bf16x3.txt 2>&1
 # the aggregation kernel as the engine runs it (sorted mode: "8s") and as a stand-alone caller gets it (unsorted), the A/B of the two with
@@ -36,7 +36,7 @@ timeout 200 python tools/topk_phase_times.py --shipped 2>/dev/null | grep -v amd
 cd /tmp && export TMPDIR=/tmp
 # the per-kernel statistics come from frames that run ONE AT A TIME (sync-per-frame region + --no-pipeline for the back-to-back region): with
 # the frame pipeline three camera stages and a head share the chip and a kernel's in-trace duration measures its co-runners as much as itself
-PROF_ARGS="--no-pipeline --steps 10 --warmup 3 --no-cpu-baseline --no-fast-mode --no-pmc --latency-groups 0"
+PROF_ARGS="--full --no-pipeline --steps 10 --warmup 3 --no-cpu-baseline --no-fast-mode --no-pmc --latency-groups 0"
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_bench -o run -- python $R/bench.py $PROF_ARGS > $O/prof_bench.log 2>&1
 python $R/tools/layer_report.py $O/prof_bench/run_kernel_trace.csv v > $O/conv_layers.txt 2>&1; tail -9 $O/conv_layers.txt
 python $R/tools/frame_report.py $O/prof_bench/run_kernel_trace.csv 45 > $O/frame_report.txt 2>&1; head -12 $O/frame_report.txt
@@ -48,7 +48,7 @@ cp $O/prof_bf16/run_kernel_stats.csv $O/bench_kernel_stats_bf16.csv 2>/dev/null;
 # PMC: one derived counter per pass (FETCH_SIZE + WRITE_SIZE together exceed the hardware), every pass under `timeout` (a failed
 # rocprofv3 does not exit on its own); the eager bench so that every kernel is its own dispatch
 if [ -n "$PMC" ]; then
-  EAGER="--eager --steps 5 --warmup 2 --no-cpu-baseline --no-fast-mode --no-pmc --latency-groups 0"
+  EAGER="--full --eager --steps 5 --warmup 2 --no-cpu-baseline --no-fast-mode --no-pmc --latency-groups 0"
   for c in FETCH_SIZE WRITE_SIZE; do
     timeout 300 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $O/pmcx3_$c -o run -- python $R/bench.py $EAGER > $O/pmcx3_$c.log 2>&1 || echo "pmc pass x3 $c failed"
   done

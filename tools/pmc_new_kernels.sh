@@ -3,7 +3,7 @@
 # bench, summarised per kernel by tools/pmc_kernels.py.   usage (GPU box): bash tools/pmc_new_kernels.sh <out dir under gpurun_out>
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/${1:-pmc_new}; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-run() { d=$1; shift; timeout 200 rocprofv3 --pmc "$@" --kernel-trace --output-format csv -d $O/$d -o run -- python $R/bench.py --eager --steps 4 --warmup 2 --no-cpu-baseline --no-in-tolerance > $O/$d.log 2>&1 || echo "pass $d failed"; }
+run() { d=$1; shift; timeout 200 rocprofv3 --pmc "$@" --kernel-trace --output-format csv -d $O/$d -o run -- python $R/bench.py --full --eager --steps 4 --warmup 2 --no-cpu-baseline --no-in-tolerance > $O/$d.log 2>&1 || echo "pass $d failed"; }
 run p1 SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD
 run p2 SQ_WAVE_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU_MFMA_MOPS_BF16 SQ_LDS_BANK_CONFLICT SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS
 cd $R
