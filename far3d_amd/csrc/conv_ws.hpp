@@ -61,13 +61,34 @@ extern std::atomic<int> g_ws_ablate;
 #define FAR3D_WS_ABLATE_ARG 0
 #endif
 
+// Grouped launches (far3d_conv2d_nhwc_grouped, tiles 500-559): up to FAR3D_WS_GROUP_MAX independent problems of ONE Cin in one persistent
+// launch -- the small maps of the FPN outputs and the 2D head fill a fraction of the chip each, together they fill it.  The table travels BY
+// VALUE in the kernel arguments (captured with the launch by hipGraph), problems in item order: problem q owns the launch items
+// [item0, next item0), decoded inside it exactly like a launch of its own.  Every item has the same steps (same Cin): the workgroups walk
+// ONE item list, and the producer's two cursors (weights, patch) and the consumers switch problem at item boundaries, the cross-item
+// prefetch included.  Products and their order do not depend on the item, so every output element is bit-identical to a launch of its own.
+// Grouped problems may carry the camera-aware MLN second output of the FPN (y2 = scale[n][m] * v + shift[n][m], fp32, the operations of
+// igemm_epilogue_px in its order); the single-problem kernel keeps its epilogue as it was.
+struct WsProblem {
+  const void* x; const void* w; const float* bias; void* y;
+  float* y2; const float* y2_scale; const float* y2_shift;
+  long x_img_stride, y_img_stride, y2_img_stride;
+  int N, H, W, ldx, ldy, ldy2, Cout, act;
+  int tiles_x, tiles_y, n_mt, item0;                  // filled in by the launcher
+};
+struct WsGroup { WsProblem p[FAR3D_WS_GROUP_MAX]; int n; };
+struct WsSingle {};
+
 // Profiling build: per-workgroup record of the persistent kernel (tools/probe/ws_conv_prof.py; 16 x uint64 per workgroup): slot 0 hardware
 // id, 1 s_memtime at entry, 2 first step's operands landed (consumer wave 0 past the first barrier), 3 s_memtime at the end of consumer
 // wave 0, 4 tiles processed, 5 steps, 6 / 7 s_memrealtime (100 MHz) at entry / end, 8 cycles consumer wave 0 spent between arriving at a
 // step's barrier and leaving it, 9 cycles it spent in the steps' bodies (fragment reads + MFMA issue), 10 cycles in the epilogues.
-template <int WGM, int WGN, int WM, int WN, int NP, bool PAIR, bool DBUF, int NSW = 3, bool FLAGS = false, int GRP = 1>
-__global__ __launch_bounds__(64 * (WGM * WGN + NP)) void conv3x3_ws_kernel(IgemmParams P, int tiles_x, int tiles_y, int n_mt, int n_items, int ablate) {
+template <int WGM, int WGN, int WM, int WN, int NP, bool PAIR, bool DBUF, int NSW = 3, bool FLAGS = false, int GRP = 1, class GT = WsSingle>
+__global__ __launch_bounds__(64 * (WGM * WGN + NP)) void conv3x3_ws_kernel(IgemmParams P, int tiles_x, int tiles_y, int n_mt, int n_items, int ablate,
+                                                                          GT GP) {
 #if defined(__HIP_DEVICE_COMPILE__)
+  constexpr bool GROUPED = std::is_same<GT, WsGroup>::value;
+  static_assert(!GROUPED || (PAIR && !FLAGS), "grouped launches: pair storage, barrier hand-over");
   constexpr int NWC = WGM * WGN;                      // consumer waves
   // NSW: weight ring depth, one tap per stage; the producers run NSW - 1 steps ahead of the consumers.  (Round 6, first measurement:
   // with 3 stages the persistent kernel only TIED the shipped one -- a step took 1.18 us against 0.73 us of MFMA work: two steps
@@ -108,6 +129,15 @@ __global__ __launch_bounds__(64 * (WGM * WGN + NP)) void conv3x3_ws_kernel(Igemm
   const int my_items = (n_items - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x;
   const int total_steps = my_items * spt, total_chunks = my_items * nchunks;
   const int Ktot = 9 * P.cin_pad * PLD;               // elements of a packed weight row
+  // launch item -> (problem q, item of the problem li, the problem's tile grid); a single-problem launch is problem 0 of the arguments
+  auto locate = [&](int item, int& q, int& li, int& txs, int& tys, int& nmt) __attribute__((always_inline)) {
+    q = 0; li = item; txs = tiles_x; tys = tiles_y; nmt = n_mt;
+    if constexpr (GROUPED) {
+      for (int i = 1; i < GP.n; ++i) q += item >= GP.p[i].item0 ? 1 : 0;
+      q = __builtin_amdgcn_readfirstlane(q);
+      li = item - GP.p[q].item0; txs = GP.p[q].tiles_x; tys = GP.p[q].tiles_y; nmt = GP.p[q].n_mt;
+    }
+  };
 #ifdef FAR3D_PROFILING
   if (P.prof && t == 0) {
     unsigned hw_, xcc_;
@@ -133,37 +163,49 @@ __global__ __launch_bounds__(64 * (WGM * WGN + NP)) void conv3x3_ws_kernel(Igemm
     unsigned wvoff[GWL];
 #pragma unroll
     for (int i = 0; i < GWL; ++i) wvoff[i] = (unsigned)((((pw + NP * i) * 16 + rg) * Ktot + lc * 8) * 2);
-    const long img_bytes = (long)P.H * P.W * P.ldx * 2;
+    long img_bytes = (long)P.H * P.W * P.ldx * 2;       // one image of the patch cursor's problem
     // issue cursors: the weights of step SW (tile tiW) and the patch of global chunk GP (tile tiP) are what comes next
     unsigned pvoff[GPL];
     const bf16_t* x_base = nullptr;                    // image of the patch cursor's tile
     const bf16_t* w_base = nullptr;                    // first weight row of the weight cursor's tile
     long w_bytes = 0;
-    auto decode = [&](int k, int& n, int& y0, int& x0, int& m0) __attribute__((always_inline)) {
+    auto decode = [&](int k, int& n, int& y0, int& x0, int& m0, int& q) __attribute__((always_inline)) {
       const int item = (int)blockIdx.x + k * (int)gridDim.x;
-      const int mt = item % n_mt, pt = item / n_mt;
-      const int tx = pt % tiles_x, r = pt / tiles_x;
-      const int ty = r % tiles_y;
-      n = __builtin_amdgcn_readfirstlane(r / tiles_y); y0 = __builtin_amdgcn_readfirstlane(ty * TH);
+      int li, txs, tys, nmt;
+      locate(item, q, li, txs, tys, nmt);
+      const int mt = li % nmt, pt = li / nmt;
+      const int tx = pt % txs, r = pt / txs;
+      const int ty = r % tys;
+      n = __builtin_amdgcn_readfirstlane(r / tys); y0 = __builtin_amdgcn_readfirstlane(ty * TH);
       x0 = __builtin_amdgcn_readfirstlane(tx * 32); m0 = __builtin_amdgcn_readfirstlane(mt * BM);
     };
     auto set_w_tile = [&](int k) __attribute__((always_inline)) {
-      int n, y0, x0, m0;
-      decode(k, n, y0, x0, m0);
-      w_base = reinterpret_cast<const bf16_t*>(P.w) + (long)m0 * Ktot;
-      w_bytes = w_tile_bytes(BM, m0, P.Cout, Ktot);
+      int n, y0, x0, m0, q;
+      decode(k, n, y0, x0, m0, q);
+      const void* w = P.w;
+      int Cout = P.Cout;
+      if constexpr (GROUPED) { w = GP.p[q].w; Cout = GP.p[q].Cout; }
+      w_base = reinterpret_cast<const bf16_t*>(w) + (long)m0 * Ktot;
+      w_bytes = w_tile_bytes(BM, m0, Cout, Ktot);
     };
     auto set_p_tile = [&](int k) __attribute__((always_inline)) {
-      int n, y0, x0, m0;
-      decode(k, n, y0, x0, m0);
-      x_base = reinterpret_cast<const bf16_t*>(P.x) + (long)n * P.x_img_stride;
+      int n, y0, x0, m0, q;
+      decode(k, n, y0, x0, m0, q);
+      const void* x = P.x;
+      long xis = P.x_img_stride;
+      int H = P.H, W = P.W, ldx = P.ldx;
+      if constexpr (GROUPED) {
+        x = GP.p[q].x; xis = GP.p[q].x_img_stride; H = GP.p[q].H; W = GP.p[q].W; ldx = GP.p[q].ldx;
+        img_bytes = (long)H * W * ldx * 2;
+      }
+      x_base = reinterpret_cast<const bf16_t*>(x) + (long)n * xis;
 #pragma unroll
       for (int i = 0; i < GPL; ++i) {
         const int idx = (pw + NP * i) * 16 + rg;
         const int py = idx / PW, px = idx - py * PW;
         const int iy = y0 - 1 + py, ix = x0 - 1 + px;
-        const bool ok = idx < PPIX && iy >= 0 && iy < P.H && ix >= 0 && ix < P.W;     // halo outside the image: hardware zero fill
-        pvoff[i] = ok ? (unsigned)((((long)iy * P.W + ix) * P.ldx + lc * 8) * 2) : OOB;
+        const bool ok = idx < PPIX && iy >= 0 && iy < H && ix >= 0 && ix < W;     // halo outside the image: hardware zero fill
+        pvoff[i] = ok ? (unsigned)((((long)iy * W + ix) * ldx + lc * 8) * 2) : OOB;
       }
     };
     auto issue_w = [&](int step_in_tile, int stage) __attribute__((always_inline)) {      // one tap of one chunk: BM rows x 64 B per plane
@@ -332,9 +374,11 @@ __global__ __launch_bounds__(64 * (WGM * WGN + NP)) void conv3x3_ws_kernel(Igemm
 #endif
   for (int k = 0; k < my_items; ++k) {
     const int item = (int)blockIdx.x + k * (int)gridDim.x;
-    const int mt = item % n_mt, pt = item / n_mt;
-    const int tx = pt % tiles_x, rr = pt / tiles_x;
-    const int ty = rr % tiles_y, n = rr / tiles_y;
+    int prob, li, txs, tys, nmt;
+    locate(item, prob, li, txs, tys, nmt);
+    const int mt = li % nmt, pt = li / nmt;
+    const int tx = pt % txs, rr = pt / txs;
+    const int ty = rr % tys, n = rr / tys;
     const int x0 = tx * 32, y0 = ty * TH, m0 = mt * BM;
 #pragma unroll
     for (int i = 0; i < WM; ++i)
@@ -447,16 +491,29 @@ __global__ __launch_bounds__(64 * (WGM * WGN + NP)) void conv3x3_ws_kernel(Igemm
     // then owns 8 consecutive channels = one 16-byte store per plane and quad pair.
     {
       const int px = x0 + l31;
-      unsigned char* yb = reinterpret_cast<unsigned char*>(P.y);
+      void* y = P.y;
+      const float* bias = P.bias;
+      long yis = P.y_img_stride;
+      int Ho = P.Ho, Wo = P.Wo, ldy = P.ldy, Cout = P.Cout, act = P.act;
+      [[maybe_unused]] float* y2 = nullptr;
+      [[maybe_unused]] const float *y2s = nullptr, *y2h = nullptr;
+      [[maybe_unused]] long y2is = 0;
+      [[maybe_unused]] int ldy2 = 0;
+      if constexpr (GROUPED) {
+        const WsProblem& pq = GP.p[prob];
+        y = pq.y; bias = pq.bias; yis = pq.y_img_stride; Ho = pq.H; Wo = pq.W; ldy = pq.ldy; Cout = pq.Cout; act = pq.act;
+        y2 = pq.y2; y2s = pq.y2_scale; y2h = pq.y2_shift; y2is = pq.y2_img_stride; ldy2 = pq.ldy2;
+      }
+      unsigned char* yb = reinterpret_cast<unsigned char*>(y);
 #pragma unroll
       for (int j = 0; j < WN; ++j) {
         const int py = y0 + wn * WN + j;
-        const bool ok = py < P.Ho && px < P.Wo;
-        const long pix_b = ((long)n * P.y_img_stride + ((long)py * P.Wo + px) * P.ldy) * 2;      // bytes
+        const bool ok = py < Ho && px < Wo;
+        const long pix_b = ((long)n * yis + ((long)py * Wo + px) * ldy) * 2;      // bytes
 #pragma unroll
         for (int i = 0; i < WM; ++i) {
           const int cb = m0 + (wm * WM + i) * 32;        // first channel of this 32-channel block
-          if (cb >= P.Cout) continue;                    // wave-uniform (Cout % 32 == 0)
+          if (cb >= Cout) continue;                      // wave-uniform (Cout % 32 == 0)
 #pragma unroll
           for (int qp = 0; qp < 2; ++qp) {               // quad pairs (0,1) and (2,3)
             uint2 h[2], l[2];
@@ -464,21 +521,31 @@ __global__ __launch_bounds__(64 * (WGM * WGN + NP)) void conv3x3_ws_kernel(Igemm
             for (int u = 0; u < 2; ++u) {
               const int q = 2 * qp + u;
               float4 b4 = make_float4(0.f, 0.f, 0.f, 0.f);
-              if (P.bias) b4 = *reinterpret_cast<const float4*>(P.bias + cb + 8 * q + 4 * hi);
+              if (bias) b4 = *reinterpret_cast<const float4*>(bias + cb + 8 * q + 4 * hi);
               float v[4];
 #pragma unroll
               for (int e = 0; e < 4; ++e) v[e] = acc[i][j][4 * q + e];
               v[0] += b4.x; v[1] += b4.y; v[2] += b4.z; v[3] += b4.w;
-              if (P.act == ACT_RELU) {
+              if (act == ACT_RELU) {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
-              } else if (P.act == ACT_SWISH) {
+              } else if (act == ACT_SWISH) {
                 if constexpr (PAIR) {
 #pragma unroll
                   for (int e = 0; e < 4; ++e) v[e] = v[e] * (1.f / (1.f + expf(-v[e])));
                 } else {
 #pragma unroll
                   for (int e = 0; e < 4; ++e) v[e] = v[e] * __frcp_rn(1.f + __expf(-v[e]));
+                }
+              }
+              if constexpr (GROUPED) {
+                if (y2 && ok) {                          // fp32 second output of this lane's 4 channels: one 16-byte store
+                  const int m = cb + 8 * q + 4 * hi;
+                  const long so = (long)n * Cout + m;
+                  float w4[4];
+#pragma unroll
+                  for (int e = 0; e < 4; ++e) w4[e] = y2s[so + e] * v[e] + y2h[so + e];
+                  *reinterpret_cast<float4*>(y2 + n * y2is + ((long)py * Wo + px) * ldy2 + m) = make_float4(w4[0], w4[1], w4[2], w4[3]);
                 }
               }
               if constexpr (PAIR) split4f(v[0], v[1], v[2], v[3], h[u], l[u]);
@@ -1001,6 +1068,49 @@ static int launch_conv3x3_ws(const IgemmParams& P, hipStream_t st) {
   if constexpr (lds > 65536)
     if (const int rc = far3d_allow_lds(reinterpret_cast<const void*>(&conv3x3_ws_kernel<WGM, WGN, WM, WN, NP, PAIR, DBUF, NSW, FLAGS, GRP>), (int)lds, lds_ok, "far3d_conv2d_nhwc")) return rc;
   hipLaunchKernelGGL((conv3x3_ws_kernel<WGM, WGN, WM, WN, NP, PAIR, DBUF, NSW, FLAGS, GRP>), dim3((unsigned)grid), dim3(64 * (WGM * WGN + NP)), lds, st, P, tiles_x, tiles_y, n_mt,
-                     n_items, FAR3D_WS_ABLATE_ARG);
+                     n_items, FAR3D_WS_ABLATE_ARG, WsSingle{});
+  return 0;
+}
+
+// Grouped launch of the same workgroup shape: G holds the problems (sizes, pointers); this orders them largest first, fills in their tile
+// grids and item ranges, and launches min(items, resident workgroups) persistent workgroups over the concatenated item list.  P carries
+// what the problems share (cin_pad).
+template <int WGM, int WGN, int WM, int WN, int NP, bool PAIR, bool DBUF, int NSW = 3, bool FLAGS = false, int GRP = 1>
+static int launch_conv3x3_ws_grouped(const IgemmParams& P, const WsGroup& G0, hipStream_t st) {
+  constexpr int BM = 32 * WGM * WM, TH = WGN * WN, PLD = PAIR ? 2 : 1;
+  constexpr int PG = (34 * (TH + 2) + 15) / 16;
+  constexpr size_t lds = (size_t)NSW * PLD * BM * 64 + (size_t)2 * PLD * PG * 1024 + (FLAGS ? 128 : 0);
+  static_assert(lds <= 163840, "LDS budget");
+  WsGroup G = G0;
+  long items[FAR3D_WS_GROUP_MAX];
+  for (int i = 0; i < G.n; ++i) {
+    WsProblem& q = G.p[i];
+    q.tiles_x = (q.W + 31) / 32; q.tiles_y = (q.H + TH - 1) / TH; q.n_mt = (q.Cout + BM - 1) / BM;
+    items[i] = (long)q.N * q.tiles_x * q.tiles_y * q.n_mt;
+  }
+  for (int i = 1; i < G.n; ++i)                        // largest problem first (stable insertion sort of at most 16 entries)
+    for (int j = i; j > 0 && items[j] > items[j - 1]; --j) {
+      const WsProblem t = G.p[j]; G.p[j] = G.p[j - 1]; G.p[j - 1] = t;
+      const long u = items[j]; items[j] = items[j - 1]; items[j - 1] = u;
+    }
+  long n_items = 0;
+  for (int i = 0; i < G.n; ++i) { G.p[i].item0 = (int)n_items; n_items += items[i]; }
+  if (n_items >= (1L << 31) - 4096) { far3d_set_error("far3d_conv2d_nhwc_grouped: %ld items", n_items); return FAR3D_ERR_ARG; }
+  static std::atomic<int> n_cu{0};
+  int cus = n_cu.load(std::memory_order_relaxed);
+  if (cus == 0) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) dev = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
+    n_cu.store(cus, std::memory_order_relaxed);
+  }
+  constexpr int wg_per_cu = lds <= 81920 && 64 * (WGM * WGN + NP) <= 1024 ? 2 : 1;
+  const int grid = n_items < cus * wg_per_cu ? (int)n_items : cus * wg_per_cu;
+  static std::atomic<unsigned long long> lds_ok{0};
+  if constexpr (lds > 65536)
+    if (const int rc = far3d_allow_lds(reinterpret_cast<const void*>(&conv3x3_ws_kernel<WGM, WGN, WM, WN, NP, PAIR, DBUF, NSW, FLAGS, GRP, WsGroup>), (int)lds, lds_ok,
+                                       "far3d_conv2d_nhwc_grouped")) return rc;
+  hipLaunchKernelGGL((conv3x3_ws_kernel<WGM, WGN, WM, WN, NP, PAIR, DBUF, NSW, FLAGS, GRP, WsGroup>), dim3((unsigned)grid), dim3(64 * (WGM * WGN + NP)), lds, st, P,
+                     G.p[0].tiles_x, G.p[0].tiles_y, G.p[0].n_mt, (int)n_items, FAR3D_WS_ABLATE_ARG, G);
   return 0;
 }

@@ -518,12 +518,18 @@ class Far3DEngine:
         for i in range(n - 1, -1, -1):   # top-down: laterals[i-1] += nearest_upsample(laterals[i])
             lat[i] = ops.conv2d_nhwc(ins[i], self.fpn_lat[i], out=self._buf(("lat", i), (N, hw[i][0], hw[i][1], 256 * self.cs), act),
                                      res=lat[i + 1] if i + 1 < n else None)
-        raw = []
-        for i in range(n + 1):
-            src = lat[i] if i < n else raw[n - 1]
-            y2 = tokens[:, starts[i]: starts[i] + hw[i][0] * hw[i][1]].view(N, hw[i][0], hw[i][1], 256)
-            raw.append(ops.conv2d_nhwc(src, self.fpn_out[i], out=self._buf(("fpn", i), (N, hw[i][0], hw[i][1], 256 * self.cs), act),
-                                       y2=y2, y2_scale=mln_scale, y2_shift=mln_shift))
+        raw = [None] * (n + 1)
+        y2s = [tokens[:, starts[i]: starts[i] + hw[i][0] * hw[i][1]].view(N, hw[i][0], hw[i][1], 256) for i in range(n + 1)]
+        outs = [self._buf(("fpn", i), (N, hw[i][0], hw[i][1], 256 * self.cs), act) for i in range(n + 1)]
+        # the stride-1 outputs are independent of one another: one grouped launch where it was measured to win (ops.group_tile)
+        gt = ops.group_tile("fpn.out", N * hw[0][0] * hw[0][1]) if self.pair else 0
+        if gt and all(ops.conv_groupable(lat[i], self.fpn_out[i]) for i in range(n)):
+            raw[:n] = ops.conv2d_nhwc_grouped([dict(x=lat[i], pc=self.fpn_out[i], out=outs[i], y2=y2s[i], y2_scale=mln_scale, y2_shift=mln_shift)
+                                               for i in range(n)], gt)
+        else:
+            for i in range(n):
+                raw[i] = ops.conv2d_nhwc(lat[i], self.fpn_out[i], out=outs[i], y2=y2s[i], y2_scale=mln_scale, y2_shift=mln_shift)
+        raw[n] = ops.conv2d_nhwc(raw[n - 1], self.fpn_out[n], out=outs[n], y2=y2s[n], y2_scale=mln_scale, y2_shift=mln_shift)
         return raw, tokens, hw, starts
 
     # ------------------------------------------------------------------------------------------ a4: 2D head + depth
@@ -531,6 +537,12 @@ class Far3DEngine:
     def roi_head(self, raw, centers2d=None):
         """YOLOX towers + depth head on the raw FPN maps.  centers2d: optional list that receives the (N,h,w,2) centre-offset maps
         (a loss input the inference path never reads; the stand-alone YOLOXHeadCustom.forward returns them like the reference)."""
+        d = raw[0]
+        npix = d.shape[0] * d.shape[1] * d.shape[2]
+        gt0 = ops.group_tile("roi.tower0", npix) if self.pair else 0
+        gt1 = ops.group_tile("roi.cls1reg1", npix) if self.pair else 0
+        if gt0 and gt1 and centers2d is None and self._roi_groupable(raw):
+            return self._roi_head_grouped(raw, gt0, gt1)
         cls, reg = [], []
         for l, x in enumerate(raw):
             lv = self.roi[l]
@@ -547,6 +559,34 @@ class Far3DEngine:
         for i in range(2):
             d = ops.conv2d_nhwc(d, self.depth["convs"][i])
             d = ops.groupnorm_nhwc(d, *self.depth["gn"][i], groups=32, relu=True, scratch=gscr, pair=self.pair)
+        return cls, reg, ops.conv2d_nhwc(d, self.depth["cls"], out_dtype=torch.float32)
+
+    def _roi_groupable(self, raw):
+        if 2 * len(raw) + 1 > ops.GROUP_MAX:
+            return False
+        lv0 = [(x, self.roi[l]["tower0"]) for l, x in enumerate(raw)]
+        c1 = [lv["cls"][1] for lv in self.roi] + [lv["reg"][1] for lv in self.roi] + list(self.depth["convs"])
+        return (all(ops.conv_groupable(x, pc) for x, pc in lv0) and ops.conv_groupable(raw[0], self.depth["convs"][0]) and
+                all(pc.terms == 3 and pc.KH == 3 and pc.stride == 1 and pc.pad == 1 and pc.Cin == 256 and pc.Cout % 32 == 0 for pc in c1) and
+                all(pc.Cout == 512 for _, pc in lv0))
+
+    def _roi_head_grouped(self, raw, gt0, gt1):
+        """roi_head as two grouped launches of the persistent 3x3 kernel -- {tower0 of every level, depth.c0}, then {cls1 and reg1 of every
+        level, depth.c1} -- with the depth head's GroupNorm between them and the 1x1 heads after: the same layers on the same inputs, every
+        output bit-identical to the per-layer launches (ops.conv2d_nhwc_grouped)."""
+        L = len(raw)
+        outs = ops.conv2d_nhwc_grouped([dict(x=x, pc=self.roi[l]["tower0"], act="swish") for l, x in enumerate(raw)] +
+                                       [dict(x=raw[0], pc=self.depth["convs"][0])], gt0)
+        t0s, d = outs[:L], outs[L]
+        gscr = self._buf(("gn_scratch",), (ops.ese_scratch_floats(d.shape[0], d.shape[-1] // self.cs),), torch.float32)
+        d = ops.groupnorm_nhwc(d, *self.depth["gn"][0], groups=32, relu=True, scratch=gscr, pair=self.pair)
+        half = [t.shape[-1] // 2 for t in t0s]
+        outs = ops.conv2d_nhwc_grouped([dict(x=t[..., :h], pc=self.roi[l]["cls"][1], act="swish") for l, (t, h) in enumerate(zip(t0s, half))] +
+                                       [dict(x=t[..., h:], pc=self.roi[l]["reg"][1], act="swish") for l, (t, h) in enumerate(zip(t0s, half))] +
+                                       [dict(x=d, pc=self.depth["convs"][1])], gt1)
+        d = ops.groupnorm_nhwc(outs[2 * L], *self.depth["gn"][1], groups=32, relu=True, scratch=gscr, pair=self.pair)
+        cls = [ops.conv2d_nhwc(outs[l], self.roi[l]["cls_head"], out_dtype=torch.float32) for l in range(L)]
+        reg = [ops.conv2d_nhwc(outs[L + l], self.roi[l]["reg_head"], out_dtype=torch.float32) for l in range(L)]
         return cls, reg, ops.conv2d_nhwc(d, self.depth["cls"], out_dtype=torch.float32)
 
     # ------------------------------------------------------------------------------------------ memory (a6/a11)

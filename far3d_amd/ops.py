@@ -274,7 +274,10 @@ def use_tile_tables(bf16_table, pair_table=None):
         _TABLE_SEL.cur = prev
 
 
-WS_TILES = range(400, 478)      # persistent wave-specialised kernels (csrc/conv_ws.hpp; 400-459 3x3, 460-477 1x1 GEMM on pair maps; 479-481 are fp32-row GEMM tiles): bias + activation + pair / bf16 store only
+WS_TILES = set(range(400, 478)) | set(range(500, 560))   # persistent wave-specialised kernels (csrc/conv_ws.hpp; 400-459 3x3, 460-477 1x1 GEMM on pair maps; 479-481 are fp32-row GEMM tiles): bias + activation + pair / bf16 store only; 500-559 grouped 3x3 launches (conv2d_nhwc_grouped)
+GROUP_TILES = range(500, 560)
+GROUP_MAX = 16                  # FAR3D_WS_GROUP_MAX in include/far3d_hip.h
+GROUP_TILE_TABLE = "tuning_mi355x_groups.json"
 
 
 def _tuned_tile(Cout, Cin, k, stride, npix, table=None, ws_ok=False):
@@ -449,6 +452,93 @@ def conv2d_nhwc(x, pc, out=None, act=None, out_dtype=None, res=None, y2=None, y2
         rp, rdt, ldr, rs, Hr, Wr, y2p, y2dt, ldy2, y2s, sp, hp, _sums_ptr(sums, N, pc.Cout), tile,
         _stream(x)), "far3d_conv2d_nhwc")
     return out
+
+
+class _ConvProblem(ctypes.Structure):
+    """far3d_conv_problem (include/far3d_hip.h)."""
+    _fields_ = [("x", ctypes.c_void_p), ("w", ctypes.c_void_p), ("bias", ctypes.c_void_p), ("y", ctypes.c_void_p),
+                ("y2", ctypes.c_void_p), ("y2_scale", ctypes.c_void_p), ("y2_shift", ctypes.c_void_p),
+                ("x_img_stride", ctypes.c_long), ("y_img_stride", ctypes.c_long), ("y2_img_stride", ctypes.c_long),
+                ("N", ctypes.c_int), ("H", ctypes.c_int), ("W", ctypes.c_int), ("Cin", ctypes.c_int), ("Cout", ctypes.c_int),
+                ("ldx", ctypes.c_int), ("ldy", ctypes.c_int), ("ldy2", ctypes.c_int), ("act", ctypes.c_int)]
+
+
+def conv_groupable(x, pc):
+    """True if (x, pc) can be one problem of conv2d_nhwc_grouped: a 3x3 / stride 1 / pad 1 layer with split products (pc.terms 3) on a
+    pair-stored map whose channels are a multiple of 32, 16-byte aligned rows."""
+    if not (_is_pair_input(x, pc) and pc.terms == 3 and pc.KH == 3 and pc.KW == 3 and pc.stride == 1 and pc.pad == 1):
+        return False
+    if pc.Cin % 32 or pc.Cout % 32 or x.shape[-1] != 2 * pc.Cin or x.dim() != 4 or x.stride(3) != 1:
+        return False
+    return x.data_ptr() % 16 == 0 and x.stride(2) % 8 == 0 and x.stride(0) % 8 == 0
+
+
+def group_tile(name, npix, table=None):
+    """The grouped tile measured for the named layer group (far3d_amd/data/tuning_mi355x_groups.json, key "<group>,<level-0 pixels>";
+    tools/tune_conv.py GROUPS=1), or 0 = the group is launched layer by layer.  Like a persistent single-layer tile, an entry holds only
+    near the pixel count it was measured at: the group replaces the per-layer launches only where it was measured to win."""
+    table = table or GROUP_TILE_TABLE
+    tab = _TUNING.get(table)
+    if tab is None:
+        import json
+        import os
+        path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "data", table)
+        raw = json.load(open(path)) if os.path.exists(path) else {}
+        tab = _TUNING[table] = {}
+        for key, tile in raw.items():
+            g, npx = key.rsplit(",", 1)
+            tab.setdefault(g, []).append((int(npx), int(tile)))
+    cands = tab.get(name)
+    if not cands:
+        return 0
+    npx, tile = min(cands, key=lambda c: abs(c[0] - npix))
+    return tile if 4 * abs(npx - npix) <= npx else 0
+
+
+def conv2d_nhwc_grouped(problems, tile):
+    """Up to GROUP_MAX independent 3x3 convolutions of one Cin as ONE launch of the persistent kernel (far3d_conv2d_nhwc_grouped).
+    problems: list of dicts with x (pair-stored NHWC view), pc (PackedConv, split products), optional out (pair-stored view), act, and
+    optional y2 / y2_scale / y2_shift (the fp32 second output of conv2d_nhwc).  Every output is bit-identical to conv2d_nhwc of the same
+    problem.  Returns the list of outputs.  Anything the launch does not cover is an error, never a per-layer fallback."""
+    lib = _lib.require_device()
+    if not 1 <= len(problems) <= GROUP_MAX:
+        raise ValueError("conv2d_nhwc_grouped: %d problems (1..%d)" % (len(problems), GROUP_MAX))
+    if tile not in GROUP_TILES:
+        raise ValueError("conv2d_nhwc_grouped: tile %r is not a grouped tile" % (tile,))
+    arr = (_ConvProblem * len(problems))()
+    outs = []
+    for i, pr in enumerate(problems):
+        x, pc = pr["x"], pr["pc"]
+        if not conv_groupable(x, pc):
+            raise ValueError("conv2d_nhwc_grouped: problem %d is not a 3x3 / s1 / p1 split-product layer on an aligned pair-stored map" % i)
+        N, H, W, _ = x.shape
+        ldx, xs = _nhwc_view(x, "x")
+        out = pr.get("out")
+        if out is None:
+            out = torch.empty((N, H, W, 2 * pc.Cout), dtype=torch.bfloat16, device=x.device)
+        if out.dtype != torch.bfloat16 or tuple(out.shape) != (N, H, W, 2 * pc.Cout):
+            raise ValueError("conv2d_nhwc_grouped: problem %d: out must be a pair-stored %s map" % (i, (N, H, W, 2 * pc.Cout)))
+        ldy, ys = _nhwc_view(out, "out")
+        c = arr[i]
+        c.x, c.w, c.y = x.data_ptr(), pc.w.data_ptr(), out.data_ptr()
+        c.bias = pc.bias.data_ptr() if pc.bias is not None else None
+        c.x_img_stride, c.y_img_stride = xs, ys
+        c.N, c.H, c.W, c.Cin, c.Cout, c.ldx, c.ldy, c.act = N, H, W, pc.Cin, pc.Cout, ldx, ldy, ACT[pr.get("act")]
+        y2 = pr.get("y2")
+        if y2 is not None:
+            sc, sh = pr["y2_scale"], pr["y2_shift"]
+            if y2.dtype != torch.float32:
+                raise TypeError("conv2d_nhwc_grouped: problem %d: y2 must be float32 (got %s)" % (i, y2.dtype))
+            _chk(sc, "y2_scale", torch.float32)
+            _chk(sh, "y2_shift", torch.float32)
+            if sc.numel() != N * pc.Cout or sh.numel() != N * pc.Cout or tuple(y2.shape) != (N, H, W, pc.Cout):
+                raise ValueError("conv2d_nhwc_grouped: problem %d: y2/scale/shift shapes inconsistent" % i)
+            c.ldy2, c.y2_img_stride = _nhwc_view(y2, "y2")
+            c.y2, c.y2_scale, c.y2_shift = y2.data_ptr(), sc.data_ptr(), sh.data_ptr()
+        outs.append(out)
+    _lib.check(lib.far3d_conv2d_nhwc_grouped(ctypes.cast(arr, ctypes.c_void_p), len(problems), tile, _stream(problems[0]["x"])),
+               "far3d_conv2d_nhwc_grouped")
+    return outs
 
 
 # linear(): tile for fp32 rows x fp32 weights (exact fp32 MFMA on the pipelined GEMM kernel, far3d_hip.h tiles 482-494); 0 = the

@@ -187,6 +187,30 @@ int far3d_conv2d_nhwc(const void* x, int x_dt, const void* w, int w_dt, const fl
                       long y2_img_stride, const float* y2_scale, const float* y2_shift, long long* chan_sums, int tile,
                       void* stream);
 
+/* One problem of far3d_conv2d_nhwc_grouped: a 3x3 / stride 1 / pad 1 convolution on pair-stored maps with split weights
+ * (x_dt = y_dt = FAR3D_DT_BF16_PAIR, w_dt = FAR3D_DT_F32_BF16X3), sizes and strides as in far3d_conv2d_nhwc (Ho = H, Wo = W). */
+typedef struct {
+  const void* x;             /* (N, H, W) pair-stored map, pixel stride ldx, image stride x_img_stride; channel offset pre-applied */
+  const void* w;             /* packed split weights of the layer (rows padded as for far3d_conv2d_nhwc) */
+  const float* bias;         /* [Cout padded] or NULL */
+  void* y;                   /* (N, H, W) pair-stored output, pixel stride ldy, image stride y_img_stride */
+  float* y2;                 /* optional fp32 second output y2 = y2_scale[n][m] * v + y2_shift[n][m] (v: the fp32 value before storage), or NULL */
+  const float* y2_scale;     /* [N][Cout] */
+  const float* y2_shift;     /* [N][Cout] */
+  long x_img_stride, y_img_stride, y2_img_stride;
+  int N, H, W, Cin, Cout, ldx, ldy, ldy2;
+  int act;                   /* 0 none, 1 relu, 2 swish */
+} far3d_conv_problem;
+/* problems per far3d_conv2d_nhwc_grouped launch */
+#define FAR3D_WS_GROUP_MAX 16
+
+/* n (1..FAR3D_WS_GROUP_MAX) independent 3x3 convolutions (far3d_conv_problem, host array) of ONE Cin as one launch of the persistent
+ * wave-specialised kernel: its workgroups walk the concatenated (problem, pixel tile, channel tile) item list, largest problem first.
+ * Each output element is bit-identical to the same problem launched by far3d_conv2d_nhwc (every 3x3 tile of the split-product kernels
+ * adds the same products in the same order).  tile: 500-559, the workgroup of persistent tile (tile - 100).  Mixed Cin, more than
+ * FAR3D_WS_GROUP_MAX problems, unaligned rows or an unknown tile are errors; nothing is launched then. */
+int far3d_conv2d_nhwc_grouped(const far3d_conv_problem* probs, int n, int tile, void* stream);
+
 /* Multi-head self-attention core: out = softmax(q k^T * scale) v per head (flash-style, no score tensor in HBM).
  * Replaces the bmm/softmax/bmm inside torch.nn.MultiheadAttention as wrapped by mmcv's MultiheadAttention
  *   (ref cfg projects/configs/far3d.py:112-116; call site models/utils/detr3d_transformer.py:385-394; in-tree

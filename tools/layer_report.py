@@ -33,6 +33,20 @@ for l in range(4):
 p = N*80*120
 layers += [("depth.c0", p, 256, 2304), ("depth.c1", p, 256, 2304), ("depth.cls", p, 51, 256)]
 rows = list(csv.DictReader(open(sys.argv[1])))
+# grouped launches (engine.fpn / engine.roi_head with far3d_amd/data/tuning_mi355x_groups.json; kernels instantiated with WsGroup): one launch
+# runs several layers.  The engine's order is then lat2..lat0, {out0-2}, out3, {tower0 x 4, depth.c0}, {cls1 x 4, reg1 x 4, depth.c1},
+# the 1x1 heads; a grouped launch is attributed to ONE row that sums its layers' FLOPs (npix = 0 marks such a row).
+if any("WsGroup" in r["Kernel_Name"] for r in rows):
+    by = {nm: (npx, co, K) for nm, npx, co, K in layers}
+    def grp(name, members):
+        return (name, 0, 0, 0, [by[m] for m in members])
+    head = [x for x in layers if not x[0].startswith(("fpn.out", "roi", "depth"))]      # stem, stages, FPN laterals
+    L = range(4)
+    layers = head + [grp("fpn.out[0-2]", ["fpn.out%d" % i for i in range(3)]), ("fpn.out3",) + by["fpn.out3"],
+                     grp("roi.tower0+d.c0", ["roi%d.tower0" % l for l in L] + ["depth.c0"]),
+                     grp("roi.c1r1+d.c1", ["roi%d.cls1" % l for l in L] + ["roi%d.reg1" % l for l in L] + ["depth.c1"])] + \
+             [("roi%d.clsh" % l,) + by["roi%d.clsh" % l] for l in L] + [("roi%d.regh" % l,) + by["roi%d.regh" % l] for l in L] + \
+             [("depth.cls",) + by["depth.cls"]]
 # rocprofv3 writes the trace in completion-record order, not in launch order: two neighbouring launches can come out swapped (round 5's
 # report paired s4.b3.c4 with the concat GEMM's launch and printed 2 460.9 TF/s for the layer after it).  The layers of a frame run on
 # ONE stream, so their start times are their order.
@@ -53,9 +67,13 @@ for k in range(len(stems) - 1, -1, -1):
 assert ig is not None, "no complete frame (%d conv launches) in the trace" % len(layers)
 tot_t = tot_f = 0
 agg = {}
-for (name, npix, cout, K), r in zip(layers, ig):
+for lay, r in zip(layers, ig):
+    name, npix, cout, K = lay[:4]
     t = (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) * 1e-9
-    fl = 2.0 * npix * cout * K
+    fl = 2.0 * npix * cout * K if len(lay) == 4 else sum(2.0 * a * b * c for a, b, c in lay[4])
+    if len(lay) > 4:
+        K = 2304          # every grouped layer is a 3x3 over 256 channels
+        assert "WsGroup" in r["Kernel_Name"], "grouped layers %s paired with launch %s" % (name, r["Kernel_Name"][:60])
     # sanity of the pairing: a 3x3 layer runs on a 3x3 / generic kernel, never on the 1x1 GEMM kernel, and the other way round; no
     # layer can exceed the matrix peak of its arithmetic (three MFMAs per product in the pair / split modes)
     kn = r["Kernel_Name"]

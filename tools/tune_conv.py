@@ -1,6 +1,7 @@
 """Sweep the workgroup tile of far3d_conv2d_nhwc for every distinct conv shape of the VoV-99 640x960x7 frame (bf16) and
 write the winners to gpurun_out/tuning_mi355x.json (key "Cout,Cin,k,stride,Npix"; copied to far3d_amd/data/).  Device time
-via hipGraph replay.  MODE=bf16x3: the split-precision mode (fp32 tensors, tiles 1-5) -> tuning_mi355x_bf16x3.json."""
+via hipGraph replay.  MODE=bf16x3: the split-precision mode (fp32 tensors, tiles 1-5) -> tuning_mi355x_bf16x3.json.
+GROUPS=1: the layer groups of the FPN outputs / 2D head as grouped launches (tiles 500-559) -> tuning_mi355x_groups.json."""
 import json, os, sys
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -160,5 +161,49 @@ def main():
         name += "_n" + os.environ["NCAM"]
     json.dump(table, open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gpurun_out", name + ".json"), "w"), indent=0, sort_keys=True)
 
+GROUP_CANDIDATES = (500, 505, 552, 556, 559)
+
+
+def group_shapes(N):
+    """The layer groups engine.fpn / engine.roi_head launch as one grouped call: name -> [(H, W, Cout, act, y2)] at Cin 256."""
+    hw = [(80, 120), (40, 60), (20, 30), (10, 15)]
+    return {"fpn.out": [(h, w, 256, None, True) for h, w in hw[:3]],
+            "roi.tower0": [(h, w, 512, "swish", False) for h, w in hw] + [(80, 120, 256, None, False)],
+            "roi.cls1reg1": [(h, w, 256, "swish", False) for h, w in hw] * 2 + [(80, 120, 256, None, False)]}
+
+
+def groups_main():
+    """GROUPS=1: time each layer group as its per-layer launches (the tiles the tables ship) and as one grouped launch per candidate tile
+    -> $OUT_DIR/tuning_mi355x_groups.json (default: the working directory; copy it to far3d_amd/data/), key "<group>,<level-0 pixels>".  A group gets an entry only where its best grouped launch
+    beats the per-layer launches by more than 3 % (the tables' rule for a persistent tile)."""
+    dev = "cuda:0"
+    N = int(os.environ.get("NCAM", "7"))
+    table = {}
+    for gname, shp in group_shapes(N).items():
+        probs = []
+        for (H, W, cout, act, mln) in shp:
+            x = ops.pair_from_float(torch.randn(N, H, W, 256, device=dev))
+            pc = ops.PackedConv(torch.randn(cout, 256, 3, 3) * 0.05, torch.randn(cout), stride=1, pad=1, dtype=torch.float32, device=dev, compute="bf16x3")
+            d = dict(x=x, pc=pc, out=torch.empty(N, H, W, 2 * cout, dtype=torch.bfloat16, device=dev), act=act)
+            if mln:
+                d.update(y2=torch.empty(N, H, W, cout, device=dev), y2_scale=torch.rand(N, cout, device=dev), y2_shift=torch.rand(N, cout, device=dev))
+            probs.append(d)
+        fl = sum(2.0 * p["x"].shape[0] * p["x"].shape[1] * p["x"].shape[2] * p["pc"].Cout * 256 * 9 for p in probs)
+        t_single = timeit(lambda: [ops.conv2d_nhwc(p["x"], p["pc"], out=p["out"], act=p["act"], y2=p.get("y2"), y2_scale=p.get("y2_scale"),
+                                                   y2_shift=p.get("y2_shift")) for p in probs])
+        res = {tl: timeit(lambda: ops.conv2d_nhwc_grouped(probs, tl)) for tl in GROUP_CANDIDATES}
+        best = min((t, tl) for tl, t in res.items())
+        npix = N * shp[0][0] * shp[0][1]
+        if best[0] < 0.97 * t_single:
+            table["%s,%d" % (gname, npix)] = best[1]
+        print("%-13s %2d layers %6.1f GFLOP | per-layer %7.1f us %5.0f TF/s | " % (gname, len(probs), fl / 1e9, t_single * 1e6, fl / t_single / 1e12) +
+              " ".join("g%d %6.1f" % (tl, t * 1e6) for tl, t in sorted(res.items())) +
+              " | best g%d %6.1f us %5.0f TF/s (%+.1f %%)" % (best[1], best[0] * 1e6, fl / best[0] / 1e12, 100 * (best[0] / t_single - 1)), flush=True)
+    name = "tuning_mi355x_groups" + ("" if N == 7 else "_n%d" % N)
+    out_dir = os.environ.get("OUT_DIR", ".")
+    os.makedirs(out_dir, exist_ok=True)
+    json.dump(table, open(os.path.join(out_dir, name + ".json"), "w"), indent=0, sort_keys=True)
+
+
 if __name__ == "__main__":
-    main()
+    groups_main() if os.environ.get("GROUPS") else main()
