@@ -41,8 +41,9 @@ def load_config(path):
 
 
 def default_model_cfg(num_cams=7, num_query=644, num_propagated=256, memory_len=1024, topk_proposals=256, backbone="V-99-eSE",
-                      proposal_topk=None, proposal_capacity=None):
-    """The Far3D VoV-99 Argoverse-2 model (values of the reference's only config), assembled programmatically."""
+                      proposal_topk=None, proposal_capacity=None, multi_depth_config=None):
+    """The Far3D VoV-99 Argoverse-2 model (values of the reference's only config), assembled programmatically.
+    multi_depth_config: overrides the head's dict(topk=1, range_min=30) (e.g. topk=2: multi-depth 2D proposals)."""
     depthnet = dict(type=0, hidden_dim=256, num_depth_bins=50, depth_min=0.1, depth_max=110, stride=8)
     strides = [8, 16, 32, 64]
     self_attn = dict(type="MultiheadAttention", embed_dims=256, num_heads=8, dropout=0.1)
@@ -53,7 +54,7 @@ def default_model_cfg(num_cams=7, num_query=644, num_propagated=256, memory_len=
     head = dict(type="FarHead", num_classes=26, in_channels=256, num_query=num_query, memory_len=memory_len,
                 topk_proposals=topk_proposals, num_propagated=num_propagated, with_dn=True, with_ego_pos=True,
                 add_query_from_2d=True, depthnet_config=depthnet, add_multi_depth_proposal=True,
-                multi_depth_config=dict(topk=1, range_min=30), return_bbox2d_scores=True, return_context_feat=True, code_size=8,
+                multi_depth_config=dict(multi_depth_config or dict(topk=1, range_min=30)), return_bbox2d_scores=True, return_context_feat=True, code_size=8,
                 code_weights=[1.0] * 8,
                 transformer=dict(type="Detr3DTransformer",
                                  decoder=dict(type="Detr3DTransformerDecoder", embed_dims=256, num_layers=6, transformerlayers=layer)),

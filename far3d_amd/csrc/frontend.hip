@@ -270,11 +270,83 @@ struct GatherParams {
   float depth_min, bin_size, pc_lo[3], pc_span[3], thr_logodds;
   int N, rows_total;                          // rows_total > 0: fixed-capacity mode (rows past it are dropped, unused ones zero-filled)
   int* m_out; int* overflow_out;              // optional: number of valid rows; 1 if a proposal was (or may have been) dropped
+  // multi-depth variant only (prop_gather_kernel<true>): top-`md_k` depth bins per primary, records for far3d_proposal_extra_rows
+  int md_k, md_min_bin;
+  int* md_flags; int* md_info;                // (rows) valid flag; (rows, 2K): camera, K bins, K-1 ratios (f32 bits)
 };
 
+// MD = true: the multi-depth variant (far3d_proposal_gather_md).  The primary rows are the same arithmetic as MD = false -- the
+// depth bin is the same first-maximum of the logits, found by a wave arg-max instead of a serial loop -- and every primary also
+// leaves a record of its top-K bins for the extra-row launch.
+#define MD_SLOTS 4                            // depth bins per lane: nd <= 256
+// Wave arg-max over the lanes' (value, bin) pairs: value descending, lower bin first on ties.  Exact compares only, so every lane
+// ends with the same pair.
+__device__ __forceinline__ void wave_argmax(float& v, int& i) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) {
+    const float ov = __shfl_xor(v, o);
+    const int oi = __shfl_xor(i, o);
+    if (ov > v || (ov == v && oi < i)) { v = ov; i = oi; }
+  }
+}
+
+// Multi-depth proposals (ref farhead.py:754-805): the top-K depth bins of one primary's cell, ranked by logit (softmax is monotone;
+// the top-1 is the first maximum, i.e. the K = 1 engine's bin), p_k = e_k / s in fp32 (e_k = exp(l_k - max)), the ratios
+// p_k / p_0 that scale the extra rows' log-odds, and the valid flag (top-1 bin >= the bin of range_min).  Lane 0 writes the record
+// of primary `row`; returns the top-1 bin.  Bins are spread over the lanes (bin = lane + 64 * slot).
+template <typename P>
+__device__ int md_topk_record(const P& g, const float* __restrict__ dl, int lane, int n, int row) {
+  float lv[MD_SLOTS];
+#pragma unroll
+  for (int q = 0; q < MD_SLOTS; ++q) {
+    const int b = lane + 64 * q;
+    lv[q] = b < g.nd ? dl[b] : -INFINITY;
+  }
+  unsigned taken = 0u;
+  int bins[8];
+  float lk[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    if (k < g.md_k) {                          // wave-uniform
+      float v = -INFINITY; int i = 0x7fffffff;
+#pragma unroll
+      for (int q = 0; q < MD_SLOTS; ++q) {
+        const int b = lane + 64 * q;
+        if (b < g.nd && !(taken & (1u << q)) && (lv[q] > v || i == 0x7fffffff)) { v = lv[q]; i = b; }
+      }
+      wave_argmax(v, i);
+      if ((i & 63) == lane) taken |= 1u << (i >> 6);
+      bins[k] = i; lk[k] = v;
+    }
+  }
+  // softmax denominator: s = sum_b exp(l_b - max), reduced over the wave, lane 0's sum broadcast (one value for all lanes)
+  float e = 0.f;
+#pragma unroll
+  for (int q = 0; q < MD_SLOTS; ++q)
+    if (lane + 64 * q < g.nd) e += expf(lv[q] - lk[0]);
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) e += __shfl_down(e, o);
+  const float s = __shfl(e, 0);
+  if (lane == 0) {
+    const float p0 = expf(lk[0] - lk[0]) / s;
+    int* info = g.md_info + (long)row * 2 * g.md_k;
+    info[0] = n;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      if (k < g.md_k) {
+        info[1 + k] = bins[k];
+        if (k > 0) info[g.md_k + k] = __float_as_int((expf(lk[k] - lk[0]) / s) / p0);
+      }
+    }
+    g.md_flags[row] = bins[0] >= g.md_min_bin ? 1 : 0;
+  }
+  return bins[0];
+}
+
+template <bool MD>
 __global__ __launch_bounds__(64) void prop_gather_kernel(GatherParams g) {
   const int n = blockIdx.y, j = blockIdx.x, lane = threadIdx.x;
-  if (n == g.N) {
+  if (!MD && n == g.N) {
     // fixed-capacity bookkeeping (one extra row of workgroups): total count, overflow flag, zero-fill of the unused rows so that
     // everything computed from them downstream stays finite (they are masked as attention keys, not removed)
     int M = 0, full = 0;
@@ -314,7 +386,11 @@ __global__ __launch_bounds__(64) void prop_gather_kernel(GatherParams g) {
   u = min(max(u, 0), g.wd - 1); v = min(max(v, 0), g.hd - 1);
   const float* dl = g.depth_logit + (((long)n * g.hd + v) * g.wd + u) * g.nd;
   int best = 0; float bv = dl[0];
-  for (int k = 1; k < g.nd; ++k) if (dl[k] > bv) { bv = dl[k]; best = k; }   // first maximum, like argmax
+  if constexpr (MD) {
+    best = md_topk_record(g, dl, lane, n, row);
+  } else {
+    for (int k = 1; k < g.nd; ++k) if (dl[k] > bv) { bv = dl[k]; best = k; }   // first maximum, like argmax
+  }
   const float q = (float)best / 0.5f + 1.f;
   const float d = g.depth_min + g.bin_size / 8.f * (q * q - 1.f);
   const float dm = fmaxf(d, 1e-5f);
@@ -400,8 +476,173 @@ extern "C" int far3d_proposal_gather(const float* const* reg, int nreg, int N, i
   for (int k = 0; k < 3; ++k) { g.pc_lo[k] = pc_range[k]; g.pc_span[k] = pc_range[3 + k] - pc_range[k]; }
   g.thr_logodds = logf(score_thr / (1.f - score_thr));
   g.N = N; g.rows_total = rows_total; g.m_out = m_out; g.overflow_out = overflow_out;
-  hipLaunchKernelGGL(prop_gather_kernel, dim3(cap, rows_total > 0 ? N + 1 : N), dim3(64), 0, (hipStream_t)stream, g);
+  hipLaunchKernelGGL(prop_gather_kernel<false>, dim3(cap, rows_total > 0 ? N + 1 : N), dim3(64), 0, (hipStream_t)stream, g);
   FAR3D_CHECK_LAUNCH("far3d_proposal_gather");
+  return FAR3D_OK;
+}
+
+// Multi-depth proposals, part 1 of 2 (per camera block): the primary rows of far3d_proposal_gather (same values, bit for bit) plus a
+// record per primary -- valid flag, camera, top-K bins, K-1 probability ratios -- that far3d_proposal_extra_rows turns into the extra
+// rows once every camera's primaries exist.  primary_rows > 0: primaries past it are dropped (fixed capacity; the extra-row launch
+// flags it); 0: N * cap rows.  No bookkeeping row here: the extra-row launch writes the count, the overflow flag and the hole.
+extern "C" int far3d_proposal_gather_md(const float* const* reg, int nreg, int N, int L, const int32_t* level_hw,
+                                        const int32_t* strides, const int* sel_idx, const int* sel_cnt,
+                                        int cap, const float* weights, const float* depth_logit, int hd, int wd, int nd,
+                                        int depth_stride, float depth_min, float depth_max, int depth_bins,
+                                        const float* img2lidar, const void* feat, int feat_dt, int C, const float* pc_range,
+                                        float score_thr, float* ref2d, float* ctx, float* box2d, float* score, int primary_rows,
+                                        int topk, int range_min_bin, int32_t* md_flags, int32_t* md_info, void* stream) {
+  FAR3D_CHECK_ARG(reg && level_hw && strides && sel_idx && sel_cnt && weights && depth_logit && img2lidar && feat &&
+                  pc_range && ref2d && ctx && box2d && score && md_flags && md_info, "far3d_proposal_gather_md: null argument");
+  FAR3D_CHECK_ARG(L >= 1 && L <= PROP_MAX_L && N > 0 && cap > 0 && primary_rows >= 0 && C > 0, "far3d_proposal_gather_md: bad sizes");
+  FAR3D_CHECK_ARG(topk >= 2 && topk <= 8 && topk <= nd && nd <= 64 * MD_SLOTS,
+                  "far3d_proposal_gather_md: need 2 <= topk <= 8, topk <= depth bins, depth bins <= %d", 64 * MD_SLOTS);
+  GatherParams g;
+  memset(&g, 0, sizeof(g));
+  const float* none[PROP_MAX_L] = {nullptr, nullptr, nullptr, nullptr};
+  fill_levels(g.lv, L, level_hw, strides, none, reg, 1, nreg);
+  g.sel_idx = sel_idx; g.sel_cnt = sel_cnt; g.wgt = weights; g.depth_logit = depth_logit;
+  g.img2lidar = img2lidar; g.feat = feat; g.feat_dt = feat_dt; g.ref2d = ref2d; g.ctx = ctx; g.box2d = box2d; g.score = score;
+  g.cap = cap; g.C = C; g.hd = hd; g.wd = wd; g.nd = nd; g.ds = depth_stride;
+  g.depth_min = depth_min;
+  g.bin_size = 2.f * (depth_max - depth_min) / ((float)depth_bins * (1.f + depth_bins));
+  for (int k = 0; k < 3; ++k) { g.pc_lo[k] = pc_range[k]; g.pc_span[k] = pc_range[3 + k] - pc_range[k]; }
+  g.thr_logodds = logf(score_thr / (1.f - score_thr));
+  g.N = N; g.rows_total = primary_rows;
+  g.md_k = topk; g.md_min_bin = range_min_bin; g.md_flags = md_flags; g.md_info = md_info;
+  hipLaunchKernelGGL(prop_gather_kernel<true>, dim3(cap, N), dim3(64), 0, (hipStream_t)stream, g);
+  FAR3D_CHECK_LAUNCH("far3d_proposal_gather_md");
+  return FAR3D_OK;
+}
+
+// Multi-depth proposals, part 2 of 2 (all cameras): rows [0, Mp) hold the primaries (Mp = min(sum sel_cnt, primary_rows)); for
+// k = 1 .. K-1 and every valid primary m in row order, extra row Mp + (k-1) * V + rank(m) holds m's box, its context features, its
+// log-odds times p_k / p_0 and the reference point of m's k-th depth bin (ref farhead.py:756-805, k-major).  Every workgroup
+// counts V and ranks the valid flags itself (ballot + popcount), then writes the extras of the valid primaries whose rank is
+// its own modulo the grid, and a share of the hole [M', rows_total).  The grid depends on the capacity only (graph-capturable).
+struct ExtraParams {
+  const int* sel_cnt; const int* flags; const int* info;
+  const float* img2lidar;
+  float* ref2d; float* ctx; float* box2d; float* score;
+  int N, sel_cap, P, K, C, rows_total, fill_hole;
+  float depth_min, bin_size, pc_lo[3], pc_span[3];
+  int* m_out; int* overflow_out;
+};
+
+#define EXTRA_THREADS 256
+__global__ __launch_bounds__(EXTRA_THREADS) void prop_extra_kernel(ExtraParams g) {
+  const int t = threadIdx.x, lane = t & 63, wv = t >> 6, G = gridDim.x, w = blockIdx.x;
+  __shared__ int s_part[EXTRA_THREADS / 64];
+  __shared__ int s_list[EXTRA_THREADS];        // (primary row << 8 | chunk-local slot) of this chunk's valid primaries owned here
+  __shared__ int s_rank[EXTRA_THREADS];
+  __shared__ int s_n;
+  int M = 0, full = 0;
+  for (int k = 0; k < g.N; ++k) { M += g.sel_cnt[k]; full |= g.sel_cnt[k] >= g.sel_cap; }
+  const int Mp = min(M, g.P);
+  // pass 1: V
+  int c = 0;
+  for (int m0 = 0; m0 < Mp; m0 += EXTRA_THREADS) {
+    const int m = m0 + t;
+    c += __popcll(__ballot(m < Mp && g.flags[m] != 0));
+  }
+  if (lane == 0) s_part[wv] = c;
+  __syncthreads();
+  int V = 0;
+#pragma unroll
+  for (int q = 0; q < EXTRA_THREADS / 64; ++q) V += s_part[q];
+  const long Mfull = (long)Mp + (long)(g.K - 1) * V;           // M' (rows of the reference, after the capacity of the primaries)
+  const int Mq = (int)min(Mfull, (long)g.rows_total);
+  if (w == 0 && t == 0) {
+    if (g.m_out) *g.m_out = Mq;
+    if (g.overflow_out) *g.overflow_out = (M > g.P || Mfull > g.rows_total || (g.sel_cap > 0 && full)) ? 1 : 0;
+  }
+  // pass 2: ranks, chunk by chunk; the valid primaries with rank % G == w are written by this workgroup (one wave per extra row)
+  int base = 0;
+  for (int m0 = 0; m0 < Mp; m0 += EXTRA_THREADS) {
+    const int m = m0 + t;
+    const bool vld = m < Mp && g.flags[m] != 0;
+    const unsigned long long bm = __ballot(vld);
+    const int before = __popcll(bm & ((1ull << lane) - 1ull));
+    __syncthreads();                                            // s_part / s_list of the previous chunk are consumed
+    if (lane == 0) s_part[wv] = __popcll(bm);
+    if (t == 0) s_n = 0;
+    __syncthreads();
+    int off = 0, tot = 0;
+#pragma unroll
+    for (int q = 0; q < EXTRA_THREADS / 64; ++q) { off += q < wv ? s_part[q] : 0; tot += s_part[q]; }
+    const int rank = base + off + before;
+    if (vld && rank % G == w) {
+      const int pos = atomicAdd(&s_n, 1);
+      s_list[pos] = m; s_rank[pos] = rank;
+    }
+    __syncthreads();
+    const int nl = s_n, nrow = nl * (g.K - 1);
+    for (int e = wv; e < nrow; e += EXTRA_THREADS / 64) {
+      const int p = e % nl, k = 1 + e / nl;
+      const int src = s_list[p];
+      const long dstl = (long)Mp + (long)(k - 1) * V + s_rank[p];
+      if (dstl >= g.rows_total) continue;                       // over capacity: dropped in reference order, flagged above
+      const int dst = (int)dstl;
+      const int* rec = g.info + (long)src * 2 * g.K;
+      const int n = rec[0], bin = rec[1 + k];
+      const float ratio = __int_as_float(rec[g.K + k]);
+      const float* sr = g.ctx + (long)src * (g.C + 1);
+      float* dr = g.ctx + (long)dst * (g.C + 1);
+      for (int cc = lane; cc < g.C; cc += 64) dr[cc] = sr[cc];  // rows are C + 1 = 257 floats: dword-aligned only
+      if (lane == 0) {
+        dr[g.C] = sr[g.C] * ratio;
+        const float bcx = g.box2d[src * 4 + 0], bcy = g.box2d[src * 4 + 1];
+        // the same operation order as prop_gather_kernel
+        const float q = (float)bin / 0.5f + 1.f;
+        const float d = g.depth_min + g.bin_size / 8.f * (q * q - 1.f);
+        const float dm = fmaxf(d, 1e-5f);
+        const float px = bcx * dm, py = bcy * dm;
+        const float* mm = g.img2lidar + n * 16;
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+          const float wv3 = mm[4 * r] * px + mm[4 * r + 1] * py + mm[4 * r + 2] * d + mm[4 * r + 3];
+          g.ref2d[dst * 3 + r] = (wv3 - g.pc_lo[r]) / g.pc_span[r];
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) g.box2d[dst * 4 + r] = g.box2d[src * 4 + r];
+        g.score[dst] = g.score[src];
+      }
+    }
+    base += tot;
+  }
+  if (!g.fill_hole) return;
+  // the hole [M', rows_total): zeros, so that everything computed from it downstream stays finite (masked, not removed)
+  for (int row = Mq + w * (EXTRA_THREADS / 64) + wv; row < g.rows_total; row += G * (EXTRA_THREADS / 64)) {
+    if (lane < 3) g.ref2d[row * 3 + lane] = 0.f;
+    if (lane < 4) g.box2d[row * 4 + lane] = 0.f;
+    if (lane == 0) g.score[row] = 0.f;
+    for (int cc = lane; cc <= g.C; cc += 64) g.ctx[(long)row * (g.C + 1) + cc] = 0.f;
+  }
+}
+
+extern "C" int far3d_proposal_extra_rows(const int* sel_cnt, int N, int sel_cap, int primary_rows, int topk, const int32_t* md_flags,
+                                         const int32_t* md_info, const float* img2lidar, float depth_min, float depth_max,
+                                         int depth_bins, const float* pc_range, int C, float* ref2d, float* ctx, float* box2d,
+                                         float* score, int rows_total, int fill_hole, int32_t* m_out, int32_t* overflow_out,
+                                         void* stream) {
+  FAR3D_CHECK_ARG(sel_cnt && md_flags && md_info && img2lidar && pc_range && ref2d && ctx && box2d && score,
+                  "far3d_proposal_extra_rows: null argument");
+  FAR3D_CHECK_ARG(N > 0 && primary_rows > 0 && C > 0 && rows_total >= primary_rows && depth_bins > 0,
+                  "far3d_proposal_extra_rows: bad sizes");
+  FAR3D_CHECK_ARG(topk >= 2 && topk <= 8 && topk <= depth_bins, "far3d_proposal_extra_rows: need 2 <= topk <= 8, topk <= depth bins");
+  ExtraParams g;
+  memset(&g, 0, sizeof(g));
+  g.sel_cnt = sel_cnt; g.flags = md_flags; g.info = md_info; g.img2lidar = img2lidar;
+  g.ref2d = ref2d; g.ctx = ctx; g.box2d = box2d; g.score = score;
+  g.N = N; g.sel_cap = sel_cap; g.P = primary_rows; g.K = topk; g.C = C; g.rows_total = rows_total; g.fill_hole = fill_hole;
+  g.depth_min = depth_min;
+  g.bin_size = 2.f * (depth_max - depth_min) / ((float)depth_bins * (1.f + depth_bins));
+  for (int k = 0; k < 3; ++k) { g.pc_lo[k] = pc_range[k]; g.pc_span[k] = pc_range[3 + k] - pc_range[k]; }
+  g.m_out = m_out; g.overflow_out = overflow_out;
+  // a workgroup per 16 primary rows, at most 256: each scans the flags (<= a few thousand) twice and writes 1/G of the extras
+  const int G = max(1, min((primary_rows + 15) / 16, 256));
+  hipLaunchKernelGGL(prop_extra_kernel, dim3(G), dim3(EXTRA_THREADS), 0, (hipStream_t)stream, g);
+  FAR3D_CHECK_LAUNCH("far3d_proposal_extra_rows");
   return FAR3D_OK;
 }
 

@@ -180,6 +180,10 @@ class ShardedFrame:
     reading them on another stream)."""
 
     def __init__(self, engine, group=None, use_graph=False, pipeline=False, decoder="replicated"):
+        if engine.md_k > 1:
+            # the extra rows need every camera's per-primary records, which the exchange does not carry
+            raise ValueError("camera sharding supports single-depth proposals only (multi_depth topk=1); this engine has topk=%d "
+                             "-- run it on one GPU" % engine.md_k)
         if engine.static_adaptive_rows() is None:
             raise ValueError("camera sharding needs static shapes: proposal_topk=K, or the fixed-capacity threshold mode "
                              "(proposal_capacity=rows); the legacy threshold mode syncs on a data-dependent M")

@@ -63,9 +63,27 @@ def default_cfg(**over):
         # decode, aggregation).  Graph-capturable, pipelinable, shardable -- no host sync; `check_proposal_overflow()` reports, after
         # the fact, a frame whose proposals did not fit.  None = legacy threshold mode (host sync on M, buffers grow).
         proposal_capacity=None,
+        # multi-depth 2D proposals (ref farhead.py:754-805): topk = K > 1 adds, for every primary whose best depth bin is at or beyond
+        # range_min (metres), K-1 adaptive queries at its next-best bins (K-major after all primaries).  topk 1 (or the reference's -1,
+        # plain argmax: the same numbers) keeps the single-depth path.
+        multi_depth=dict(topk=1, range_min=30),
+        # extra rows reserved for them in the static proposal modes (None = (K-1) x the primary rows: never overflows); a smaller
+        # value drops extras past it in reference order, reported by check_proposal_overflow().  The legacy threshold mode sizes
+        # them from its selection capacity and ignores this.
+        multi_depth_capacity=None,
     )
     cfg.update(over)
     return cfg
+
+
+def multi_depth_topk(cfg):
+    """K of cfg['multi_depth'] (1: single-depth proposals).  The reference's topk -1 (plain argmax) is the same computation as 1."""
+    md = cfg.get("multi_depth") or {}
+    k = md.get("topk", 1)
+    k = 1 if k is None or int(k) == -1 else int(k)
+    if not 1 <= k <= 8:
+        raise ValueError("multi_depth topk=%s: supported values are 1 ... 8 (or -1, the same as 1)" % md.get("topk"))
+    return k
 
 
 def pos2posemb(pos, num_pos_feats, temperature=10000):
@@ -176,6 +194,9 @@ class Far3DEngine:
                                     # Ignored where the chains do not apply (other decoder dtypes / geometries)
         self.mem = None
         self.prev_scene = None
+        self.md_k = multi_depth_topk(self.cfg)
+        self.md_min_bin = (ops.depth_range_min_bin(self.cfg["depthnet"], (self.cfg.get("multi_depth") or {}).get("range_min", -1))
+                           if self.md_k > 1 else None)
         self._prepare()
 
     # ------------------------------------------------------------------------------------------ weights
@@ -360,11 +381,20 @@ class Far3DEngine:
 
     def static_adaptive_rows(self, ncam=None):
         """Rows the adaptive queries occupy when that number is static (top-K mode: ncam * K; fixed-capacity threshold mode:
-        proposal_capacity), else None (legacy threshold mode: data-dependent, needs a host sync)."""
+        proposal_capacity; each + the multi-depth extra rows), else None (legacy threshold mode: data-dependent, needs a host sync)."""
         K = self.cfg["proposal_topk"]
         if K is not None:
-            return (self.cfg["num_cams"] if ncam is None else ncam) * K
-        return self.cfg.get("proposal_capacity")
+            P = (self.cfg["num_cams"] if ncam is None else ncam) * K
+        else:
+            P = self.cfg.get("proposal_capacity")
+        return None if P is None else P + self.md_extra_rows(P)
+
+    def md_extra_rows(self, primary_rows):
+        """Rows reserved for the multi-depth extra queries after `primary_rows` primary rows (0 when topk = 1)."""
+        if self.md_k <= 1:
+            return 0
+        X = self.cfg.get("multi_depth_capacity")
+        return (self.md_k - 1) * primary_rows if X is None else int(X)
 
     def bf16_tile_table(self):
         """The tile table the bf16 convolutions of this engine's launches consult (see tile_table)."""
@@ -841,7 +871,13 @@ class Far3DEngine:
                 break
             cap = min(2 * cap, tokens.shape[1])
         whole = n == cfg["num_cams"] and "head" in self.parts and block_rows is None
-        rows = n * cap if capT is None else (capT if block_rows is None else block_rows)
+        prim = n * cap if capT is None else (capT if block_rows is None else block_rows)
+        Kmd = self.md_k
+        if Kmd > 1 and block_rows is not None:
+            raise ValueError("multi-depth proposals (multi_depth topk=%d) are not supported on a camera shard" % Kmd)
+        # multi-depth: [primaries | extras | hole]; legacy threshold mode sizes the extras from the selection capacity (never overflows)
+        extra = 0 if Kmd <= 1 else (self.md_extra_rows(prim) if (K is not None or capT is not None) else (Kmd - 1) * prim)
+        rows = prim + extra
         if (K is not None or capT is not None) and whole:
             # every camera is local and the row count is static: the reference points land directly in the adaptive-query rows
             # of the head's query-major buffer (head_stage then has nothing to copy)
@@ -852,9 +888,23 @@ class Far3DEngine:
         out = (ref_out, self._buf(("ctx",), (rows, E + 1), torch.float32),
                self._buf(("box2d",), (rows, 4), torch.float32), self._buf(("score2d",), (rows,), torch.float32))
         m_dev = ovf = None
-        if capT is not None:
-            m_dev, ovf = self._buf(("m_dev",), (1,), torch.int32), self._buf(("ovf",), (1,), torch.int32)
-            self._overflow = ovf
+        if capT is not None or Kmd > 1:
+            m_dev = self._buf(("m_dev",), (1,), torch.int32)
+            if capT is not None or K is not None:
+                ovf = self._buf(("ovf",), (1,), torch.int32)
+                self._overflow = ovf
+        if Kmd > 1:
+            # part 1 of the multi-depth proposals: the primary rows + a record per primary; the extra rows are written by
+            # proposal_extra_rows at the start of the cross-camera part (_head_part), once every camera's primaries exist
+            rec = (self._buf(("md_flags",), (prim,), torch.int32), self._buf(("md_info",), (prim, 2 * Kmd), torch.int32))
+            i2l = self._buf(("md_i2l",), tuple(img2lidar.shape), torch.float32)
+            i2l.copy_(img2lidar)
+            ops.proposal_gather_md(reg, cfg["strides"], sel_idx, sel_cnt, wgt, depth_logit, cfg["depthnet"]["stride"], cfg["depthnet"],
+                                   img2lidar, tokens, cfg["pc_range"], Kmd, self.md_min_bin, rec, out,
+                                   primary_rows=prim if capT is not None else 0, score_thr=0.1)
+            md = dict(records=rec, img2lidar=i2l, primary_rows=prim, sel_cap=cap if capT is not None else 0, rows=rows)
+            return dict(ref2d=out[0], ctx=out[1], box2d=out[2], score2d=out[3], sel_idx=sel_idx, sel_cnt=sel_cnt, depth_logit=depth_logit,
+                        peak_weight=wgt, m_dev=m_dev, overflow=ovf, md=md)
         # the log-odds threshold is the reference's hard-coded 0.1 (farhead.py:577), not cfg score_thr
         ref2d, ctx, box2d, score2d = ops.proposal_gather(reg, cfg["strides"], sel_idx, sel_cnt, wgt, depth_logit,
                                                          cfg["depthnet"]["stride"], cfg["depthnet"], img2lidar, tokens,
@@ -976,12 +1026,33 @@ class Far3DEngine:
         cfg = self.cfg
         N = dd["img"].shape[0]
         M = self.static_adaptive_rows(N)
+        md = st.get("md")
+        m_dev = st["m_dev"]
+        if md is not None:
+            # part 2 of the multi-depth proposals (every camera's primaries exist): the extra rows, M' on the device, the hole
+            self.proposal_extra_rows(st, M is not None)
         if M is None:
-            M = int(st["sel_cnt"].sum().item())      # legacy threshold mode: the reference's data-dependent M, one host sync
-        outs = self.head_stage(st["tokens"], st["ref2d"], st["ctx"], M, dd, img_metas, st["hw"], st["starts"], pad_hw, m_dev=st["m_dev"])
-        outs.update(fpn=st["raw"], depth_logit=st["depth_logit"], bbox2d=st["box2d"][:M], bbox2d_scores=st["score2d"][:M],
+            if md is None:
+                M = int(st["sel_cnt"].sum().item())      # legacy threshold mode: the reference's data-dependent M, one host sync
+                Mb = M
+            else:
+                M, Mb = (int(v) for v in torch.stack([m_dev[0], st["sel_cnt"].sum(dtype=torch.int32)]).tolist())   # M' and M: one sync
+            m_dev = None                                 # exact shapes, no hole
+        else:
+            Mb = M if md is None else md["primary_rows"]
+        outs = self.head_stage(st["tokens"], st["ref2d"], st["ctx"], M, dd, img_metas, st["hw"], st["starts"], pad_hw, m_dev=m_dev)
+        outs.update(fpn=st["raw"], depth_logit=st["depth_logit"], bbox2d=st["box2d"][:Mb], bbox2d_scores=st["score2d"][:Mb],
                     sel_idx=st["sel_idx"], sel_cnt=st["sel_cnt"], proposal_overflow=st["overflow"])
+        if md is not None:
+            outs["md_records"] = md["records"]
         return outs
+
+    def proposal_extra_rows(self, st, fill_hole=True):
+        """The multi-depth extra rows of a frame whose primaries proposals() built (st: its result): one launch, no sync."""
+        md = st["md"]
+        ops.proposal_extra_rows(st["sel_cnt"], md["sel_cap"], md["primary_rows"], self.md_k, md["records"], md["img2lidar"],
+                                self.cfg["depthnet"], self.cfg["pc_range"], (st["ref2d"], st["ctx"], st["box2d"], st["score2d"]),
+                                fill_hole=fill_hole, m_out=st["m_dev"], overflow_out=st["overflow"])
 
     def _pipelined_frame(self, data, img_metas, pad_hw):
         """One steady-state frame in pipeline mode (see __init__).  Stream s_cam: [wait until the head that last used this

@@ -1059,6 +1059,85 @@ def proposal_gather(reg_maps, strides, sel_idx, sel_cnt, weights, depth_logit, d
     return ref2d, ctx, box2d, score
 
 
+def depth_range_min_bin(depth_cfg, range_min):
+    """The depth bin of `range_min` metres, as the reference computes it (farhead.py:521-531 with inverse=True, called at :758): the
+    inverse LID map on a one-element tensor in torch's default dtype, truncated to int64."""
+    dmin, dmax, nb = float(depth_cfg["depth_min"]), float(depth_cfg["depth_max"]), int(depth_cfg["num_depth_bins"])
+    bin_size = 2 * (dmax - dmin) / (nb * (1 + nb))
+    t = torch.tensor([range_min])
+    return int((-0.5 + 0.5 * torch.sqrt(1 + 8 * (t - dmin) / bin_size)).type(torch.int64).item())
+
+
+def proposal_gather_md(reg_maps, strides, sel_idx, sel_cnt, weights, depth_logit, depth_stride, depth_cfg, img2lidar, feat, pc_range,
+                       topk, range_min_bin, records, out, primary_rows=0, score_thr=0.1):
+    """Multi-depth proposals, part 1 (per camera block): the primary rows of proposal_gather, bit for bit, into out = (ref2d, ctx,
+    box2d, score) (rows [0, N*cap), or [0, primary_rows) in fixed-capacity mode), and a record per primary into records = (flags
+    (rows,) int32, info (rows, 2*topk) int32) for proposal_extra_rows.  2 <= topk <= 8."""
+    lib = _lib.require_device()
+    L = len(reg_maps)
+    N, cap = sel_idx.shape
+    hw = [(int(c.shape[1]), int(c.shape[2])) for c in reg_maps]
+    _chk(depth_logit, "depth_logit", torch.float32, 4)
+    _chk(img2lidar, "img2lidar", torch.float32, 3)
+    _chk(feat, "feat", ndim=3)
+    C = feat.shape[2]
+    ref2d, ctx, box2d, score = out
+    flags, info = records
+    _chk(flags, "md_flags", torch.int32, 1)
+    _chk(info, "md_info", torch.int32, 2)
+    rows = int(primary_rows) if primary_rows else N * cap
+    if ref2d.stride(0) != 3 or ctx.stride(0) != C + 1:
+        raise ValueError("proposal_gather_md: ref2d / ctx must be dense rows")
+    if min(ref2d.shape[0], ctx.shape[0], box2d.shape[0], score.shape[0], flags.shape[0], info.shape[0]) < rows or info.shape[1] != 2 * topk:
+        raise ValueError("proposal_gather_md: the output buffers and records need %d rows (info: %d columns)" % (rows, 2 * topk))
+    hk, hp = _host_i32([list(x) for x in hw])
+    sk, sp = _host_i32(list(strides))
+    pk, pp = _host_f32(list(pc_range))
+    ra = _ptr_array(reg_maps)
+    _, hd, wd, nd = depth_logit.shape
+    _lib.check(lib.far3d_proposal_gather_md(ra, reg_maps[0].shape[3], N, L, hp, sp, _ptr(sel_idx), _ptr(sel_cnt), cap,
+                                            _ptr(weights), _ptr(depth_logit), hd, wd, nd, int(depth_stride),
+                                            float(depth_cfg["depth_min"]), float(depth_cfg["depth_max"]),
+                                            int(depth_cfg["num_depth_bins"]), _ptr(img2lidar), _ptr(feat), _dt(feat), C, pp,
+                                            float(score_thr), _ptr(ref2d), _ptr(ctx), _ptr(box2d), _ptr(score), int(primary_rows),
+                                            int(topk), int(range_min_bin), _ptr(flags), _ptr(info), _stream(feat)),
+               "far3d_proposal_gather_md")
+    return ref2d, ctx, box2d, score
+
+
+def proposal_extra_rows(sel_cnt, sel_cap, primary_rows, topk, records, img2lidar, depth_cfg, pc_range, out, fill_hole=True,
+                        m_out=None, overflow_out=None):
+    """Multi-depth proposals, part 2 (all cameras): the extra rows after the Mp = min(sum sel_cnt, primary_rows) primaries of
+    out = (ref2d, ctx, box2d, score) (rows_total = their row count), in the reference's k-major order; fill_hole zeroes rows
+    [M', rows_total).  m_out / overflow_out: int32 device scalars for M' and the dropped-row flag (sel_cap > 0 also flags a camera
+    that filled its selection).  One launch, no sync."""
+    lib = _lib.require_device()
+    _chk(sel_cnt, "sel_cnt", torch.int32, 1)
+    _chk(img2lidar, "img2lidar", torch.float32, 3)
+    flags, info = records
+    _chk(flags, "md_flags", torch.int32, 1)
+    _chk(info, "md_info", torch.int32, 2)
+    ref2d, ctx, box2d, score = out
+    rows_total = ref2d.shape[0]
+    C = ctx.shape[1] - 1
+    if ref2d.stride(0) != 3 or ctx.stride(0) != C + 1 or min(ctx.shape[0], box2d.shape[0], score.shape[0]) < rows_total:
+        raise ValueError("proposal_extra_rows: ref2d / ctx / box2d / score must be dense rows, as many as ref2d's")
+    if min(flags.shape[0], info.shape[0]) < primary_rows or info.shape[1] != 2 * topk or img2lidar.shape[0] < sel_cnt.shape[0]:
+        raise ValueError("proposal_extra_rows: records need %d rows and %d columns, img2lidar one matrix per camera" % (primary_rows, 2 * topk))
+    for t in (m_out, overflow_out):
+        if t is not None:
+            _chk(t, "m_out / overflow_out", torch.int32)
+    pk, pp = _host_f32(list(pc_range))
+    _lib.check(lib.far3d_proposal_extra_rows(_ptr(sel_cnt), sel_cnt.shape[0], int(sel_cap), int(primary_rows), int(topk), _ptr(flags),
+                                             _ptr(info), _ptr(img2lidar), float(depth_cfg["depth_min"]), float(depth_cfg["depth_max"]),
+                                             int(depth_cfg["num_depth_bins"]), pp, C, _ptr(ref2d), _ptr(ctx), _ptr(box2d), _ptr(score),
+                                             int(rows_total), 1 if fill_hole else 0,
+                                             _ptr(m_out) if m_out is not None else None,
+                                             _ptr(overflow_out) if overflow_out is not None else None, _stream(ctx)),
+               "far3d_proposal_extra_rows")
+    return ref2d, ctx, box2d, score
+
+
 def compact_rows(src, counts, dst, m_out, overflow_out):
     """src (nblocks, rows_per_block, D) f32 with counts[b] valid rows in block b -> dst (dst_rows, D): the valid rows in block order,
     the rest zero; m_out = min(sum counts, dst_rows); overflow_out |= (sum counts > dst_rows).  One launch, no sync."""

@@ -468,7 +468,9 @@ class FarHead(_SchemaModule):
         super().__init__()
         assert with_ego_pos and add_query_from_2d and return_context_feat and return_bbox2d_scores, \
             "only the reference's FarHead configuration (2D-adaptive queries with context + score) is implemented"
-        assert (multi_depth_config or {}).get("topk", 1) == 1, "multi-depth proposals with topk > 1 are not implemented"
+        md = dict(multi_depth_config or {})
+        # topk in 1 ... 8 (-1, the reference's plain-argmax path, computes the same as 1); anything else raises a ValueError here
+        self.multi_depth_config = dict(topk=_engine.multi_depth_topk(dict(multi_depth=md)), range_min=md.get("range_min", -1))
         self.num_classes, self.embed_dims, self.num_query, self.memory_len = num_classes, embed_dims, num_query, memory_len
         self.topk_proposals, self.num_propagated, self.code_size = topk_proposals, num_propagated, code_size
         self.depthnet_config = dict(depthnet_config or {})
@@ -496,7 +498,8 @@ class FarHead(_SchemaModule):
                    num_pts=a["num_pts"], ffn_dim=a["ffn_dim"], pc_range=list(self.bbox_coder.pc_range), code_size=self.code_size,
                    max_num=self.bbox_coder.max_num,
                    depthnet=dict(num_depth_bins=self.depthnet_config.get("num_depth_bins", 50), depth_min=self.depthnet_config.get("depth_min", 0.1),
-                                 depth_max=self.depthnet_config.get("depth_max", 110.0), stride=self.depthnet_config.get("stride", 8)))
+                                 depth_max=self.depthnet_config.get("depth_max", 110.0), stride=self.depthnet_config.get("stride", 8)),
+                   multi_depth=dict(self.multi_depth_config))
         cfg.update(over)
         return _engine.default_cfg(**cfg)
 
@@ -539,9 +542,24 @@ class FarHead(_SchemaModule):
                 ops.row_affine_ln(x[n].view(-1, E), gamma[n:n + 1], beta[n:n + 1], do_ln=False,
                                   out=tokens[n, starts[l]:starts[l] + hw[l][0] * hw[l][1]])
         tokens = tokens.to(eng.prec["value"])
-        M = int(st["sel_cnt"].sum().item())
-        pr = ops.proposal_gather(st["reg"], eng.cfg["strides"], st["sel_idx"], st["sel_cnt"], st["peak_weight"], st["depth_logit"],
-                                 eng.cfg["depthnet"]["stride"], eng.cfg["depthnet"], img2lidar, tokens, eng.cfg["pc_range"], score_thr=0.1)
+        if eng.md_k > 1:
+            # multi-depth proposals (farhead.py:754-805): primaries + records, then the extra rows; one sync on M' like the reference's
+            n, cap = st["sel_idx"].shape
+            K, rows = eng.md_k, eng.md_k * n * cap
+            pr = (torch.empty((rows, 3), device=dev), torch.empty((rows, E + 1), device=dev), torch.empty((rows, 4), device=dev),
+                  torch.empty((rows,), device=dev))
+            rec = (torch.empty((n * cap,), dtype=torch.int32, device=dev), torch.empty((n * cap, 2 * K), dtype=torch.int32, device=dev))
+            m_dev = torch.empty((1,), dtype=torch.int32, device=dev)
+            ops.proposal_gather_md(st["reg"], eng.cfg["strides"], st["sel_idx"], st["sel_cnt"], st["peak_weight"], st["depth_logit"],
+                                   eng.cfg["depthnet"]["stride"], eng.cfg["depthnet"], img2lidar, tokens, eng.cfg["pc_range"], K,
+                                   eng.md_min_bin, rec, pr)
+            ops.proposal_extra_rows(st["sel_cnt"], 0, n * cap, K, rec, img2lidar, eng.cfg["depthnet"], eng.cfg["pc_range"], pr,
+                                    fill_hole=False, m_out=m_dev)
+            M = int(m_dev.item())
+        else:
+            M = int(st["sel_cnt"].sum().item())
+            pr = ops.proposal_gather(st["reg"], eng.cfg["strides"], st["sel_idx"], st["sel_cnt"], st["peak_weight"], st["depth_logit"],
+                                     eng.cfg["depthnet"]["stride"], eng.cfg["depthnet"], img2lidar, tokens, eng.cfg["pc_range"], score_thr=0.1)
         pad_hw = tuple(img_metas[0]["pad_shape"][0][:2])
         outs = eng.head_stage(tokens, pr[0], pr[1], M, dd, img_metas, hw, starts, pad_hw)
         self.last_outs = outs
@@ -610,7 +628,8 @@ class Far3D(nn.Module):
             code_size=h.code_size, max_num=h.bbox_coder.max_num,
             depthnet=dict(num_depth_bins=r.depthnet_config.get("num_depth_bins", 50), depth_min=r.depthnet_config.get("depth_min", 0.1),
                           depth_max=r.depthnet_config.get("depth_max", 110.0), stride=r.depthnet_config.get("stride", 8)),
-            score_thr=r.threshold_score, proposal_topk=self.proposal_topk, proposal_capacity=self.proposal_capacity)
+            score_thr=r.threshold_score, proposal_topk=self.proposal_topk, proposal_capacity=self.proposal_capacity,
+            multi_depth=dict(h.multi_depth_config))
 
     def prepare(self, device="cuda:0", precision="bf16"):
         """Fold BN, pack weights for the kernels, upload.  Must be called again after loading new weights."""

@@ -382,6 +382,31 @@ int far3d_proposal_gather(const float* const* reg, int nreg, int N, int L, const
                           const float* pc_range, float score_thr, float* ref2d, float* ctx, float* box2d, float* score,
                           int rows_total, int32_t* m_out, int32_t* overflow_out, void* stream);
 
+/* Multi-depth 2D proposals (ref farhead.py:754-805, multi_depth_config.topk = K in [2, 8]), part 1 of 2, per camera block: the
+ * primary rows exactly as far3d_proposal_gather writes them (bit for bit), plus a record per primary for part 2:
+ * md_flags (rows) int32 = 1 when the primary's best depth bin >= range_min_bin; md_info (rows, 2K) int32 = camera, the K best bins
+ * (by logit, lower bin first on ties; the first is far3d_proposal_gather's bin), then the K-1 ratios p_k / p_0 of the fp32 softmax
+ * probabilities (float bits).  primary_rows > 0: rows past it are dropped (fixed capacity); 0: N * cap rows.  nd <= 256.
+ * Writes no count, flag or hole: far3d_proposal_extra_rows does, after every camera's primaries exist. */
+int far3d_proposal_gather_md(const float* const* reg, int nreg, int N, int L, const int32_t* level_hw, const int32_t* strides,
+                             const int* sel_idx, const int* sel_cnt, int cap, const float* weights,
+                             const float* depth_logit, int hd, int wd, int nd, int depth_stride, float depth_min,
+                             float depth_max, int depth_bins, const float* img2lidar, const void* feat, int feat_dt, int C,
+                             const float* pc_range, float score_thr, float* ref2d, float* ctx, float* box2d, float* score,
+                             int primary_rows, int topk, int range_min_bin, int32_t* md_flags, int32_t* md_info, void* stream);
+
+/* Multi-depth 2D proposals, part 2 of 2, all cameras: with Mp = min(sum sel_cnt, primary_rows) primaries in rows [0, Mp) and V of
+ * them valid, rows [Mp, Mp + (K-1) V) receive the extra rows in the reference's k-major order (k = 1 .. K-1, valid primaries in
+ * row order): the primary's box2d / score / ctx[:C], ctx[C] = its log-odds * p_k / p_0, ref2d from the box centre, bin k's depth
+ * and the camera's img2lidar.  Rows past rows_total are dropped in that order.  fill_hole: zero rows [M', rows_total).
+ * m_out (optional) = M' = min(Mp + (K-1) V, rows_total); overflow_out (optional) = 1 when a row was dropped (sum sel_cnt >
+ * primary_rows, M' > rows_total, or -- sel_cap > 0 -- a camera reached its selection capacity sel_cap), else 0.  The grid depends
+ * on primary_rows only; no host sync. */
+int far3d_proposal_extra_rows(const int* sel_cnt, int N, int sel_cap, int primary_rows, int topk, const int32_t* md_flags,
+                              const int32_t* md_info, const float* img2lidar, float depth_min, float depth_max, int depth_bins,
+                              const float* pc_range, int C, float* ref2d, float* ctx, float* box2d, float* score, int rows_total,
+                              int fill_hole, int32_t* m_out, int32_t* overflow_out, void* stream);
+
 /* Blocks of rows -> one compact run (camera-sharded fixed-capacity mode): src (nblocks, rows_per_block, D) f32 of which the first
  * counts[b] rows of block b are valid; dst (dst_rows, D): rows [0, M) the valid rows in block order, the rest zero,
  * *m_out = M = min(sum counts, dst_rows); *overflow_out is OR-ed with (sum counts > dst_rows) (initialise it). */
