@@ -222,9 +222,10 @@ extern "C" int far3d_memory_post_update(const float* m_emb, const float* m_ref, 
                                         const float* m_velo, const int64_t* topk_idx, const float* dec_last, const float* box_last,
                                         const float* ego_pose, const double* timestamp, int L, int E, int K, int code_size,
                                         float* emb, float* ref, double* ts, float* pose, float* velo, void* stream) {
-  FAR3D_CHECK_ARG(m_emb && m_ref && m_ts && m_pose && m_velo && topk_idx && dec_last && box_last && ego_pose && timestamp && emb && ref &&
-                  ts && pose && velo, "far3d_memory_post_update: null argument");
-  FAR3D_CHECK_ARG(L > 0 && K >= 0 && K <= L && code_size >= 5, "far3d_memory_post_update: bad sizes");
+  FAR3D_CHECK_ARG(L > 0 && E > 0 && K >= 0 && K <= L && code_size >= 5, "far3d_memory_post_update: bad sizes");
+  // K = 0 pushes nothing (the queue is only warped): an empty index / query set has no storage and may be null
+  FAR3D_CHECK_ARG(m_emb && m_ref && m_ts && m_pose && m_velo && ego_pose && timestamp && emb && ref && ts && pose && velo &&
+                  (K == 0 || (topk_idx && dec_last && box_last)), "far3d_memory_post_update: null argument");
   MemPostParams p;
   p.m_emb = m_emb; p.m_ref = m_ref; p.m_ts = m_ts; p.m_pose = m_pose; p.m_velo = m_velo; p.topk = (const long*)topk_idx;
   p.dec_last = dec_last; p.box_last = box_last; p.ego_pose = ego_pose; p.timestamp = timestamp; p.emb = emb; p.ref = ref; p.ts = ts;

@@ -1156,19 +1156,31 @@ def compact_rows(src, counts, dst, m_out, overflow_out):
 
 
 def row_affine_ln(x, gamma, beta, add=None, do_ln=True, eps=1e-5, out=None):
-    """out[r] = gamma[r] * LN(x[r]) + beta[r] (+ add[r]); gamma/beta/add may be a single row (broadcast).  C = 256."""
+    """out[r] = gamma[r] * LN(x[r]) + beta[r] (+ add[r]); gamma/beta/add may be a single row (broadcast).  C = 256.
+    x / out / gamma / beta / add may be row-strided views (unit stride along the channels, row strides multiples of 4)."""
     lib = _lib.require_device()
+    if x.dim() != 2:
+        raise ValueError("row_affine_ln: x must be (rows, C) (got %s)" % (tuple(x.shape),))
     rows, C = x.shape
     bc = lambda t: 0 if (t.dim() == 1 or t.shape[0] == 1) else t.stride(0)
     if out is None:
         out = torch.empty((rows, C), dtype=torch.float32, device=x.device)
+    if tuple(out.shape) != (rows, C):
+        raise ValueError("row_affine_ln: out must be (%d, %d) (got %s)" % (rows, C, tuple(out.shape)))
+    for t, name in ((x, "x"), (gamma, "gamma"), (beta, "beta"), (add, "add"), (out, "out")):
+        if t is None:
+            continue
+        if not t.is_cuda or t.dtype != torch.float32:
+            raise TypeError("row_affine_ln: %s must be a float32 tensor on the HIP device" % name)
+        if t.dim() not in (1, 2) or t.shape[-1] != C or t.stride(-1) != 1 or (t.dim() == 2 and t.shape[0] not in (1, rows)):
+            raise ValueError("row_affine_ln: %s must be (%d, %d) or one row of %d, unit stride along the channels (got %s, strides %s)"
+                             % (name, rows, C, C, tuple(t.shape), t.stride()))
     if bc(gamma) != bc(beta):
         raise ValueError("row_affine_ln: gamma and beta must broadcast alike")
     _lib.check(lib.far3d_row_affine_ln(_ptr(x), _ptr(gamma), _ptr(beta), _ptr(add) if add is not None else None, _ptr(out),
                                        rows, C, x.stride(0), bc(gamma), bc(add) if add is not None else 0, out.stride(0),
                                        float(eps), 1 if do_ln else 0, _stream(x)), "far3d_row_affine_ln")
     return out
-
 
 
 def camera_sorted_order(ref, lidar2img, pc_range, pad_hw, spatial=True):
@@ -1204,11 +1216,41 @@ def posemb3d(pos, dim_t128):
     return out
 
 
+_MEM_KEYS = (("emb", torch.float32, 3), ("ref", torch.float32, 3), ("ts", torch.float64, 3), ("pose", torch.float32, 4), ("velo", torch.float32, 3))
+
+
+def _chk_memory(d, name, L=None, E=None):
+    """A memory dict emb (1,L,E) ref (1,L,3) ts (1,L,1) f64 pose (1,L,4,4) velo (1,L,2): the kernels index dense buffers."""
+    for k, dt, nd in _MEM_KEYS:
+        _chk(d[k], "%s[%r]" % (name, k), dt, nd)
+    L = d["emb"].shape[1] if L is None else L
+    E = d["emb"].shape[2] if E is None else E
+    want = dict(emb=(1, L, E), ref=(1, L, 3), ts=(1, L, 1), pose=(1, L, 4, 4), velo=(1, L, 2))
+    for k, shp in want.items():
+        if tuple(d[k].shape) != shp:
+            raise ValueError("%s[%r] must be %s (got %s)" % (name, k, shp, tuple(d[k].shape)))
+    return L, E
+
+
 def memory_prepare(state, ego_pose_inv, timestamp, pseudo_ref, dim_t256, prev_exists, fresh, pc_range, num_propagated,
                    temp_ref_out=None):
     """state: dict emb (1,L,E) ref (1,L,3) ts (1,L,1) f64 pose (1,L,4,4) velo (1,L,2).  Returns (m dict, temp_ref, nerf, tpos)."""
     lib = _lib.require_device()
-    L, E = state["emb"].shape[1], state["emb"].shape[2]
+    L, E = _chk_memory(state, "memory_prepare: state")
+    P = int(num_propagated)
+    _chk(ego_pose_inv, "ego_pose_inv", torch.float32)
+    _chk(timestamp, "timestamp", torch.float64)
+    _chk(dim_t256, "dim_t256", torch.float32)
+    if ego_pose_inv.numel() != 16 or timestamp.numel() != 1 or dim_t256.numel() != 256:
+        raise ValueError("memory_prepare: ego_pose_inv must hold 16 values, timestamp one, dim_t256 256")
+    if not 0 <= P <= L:
+        raise ValueError("memory_prepare: num_propagated=%d outside [0, L=%d]" % (P, L))
+    if P > 0:
+        if pseudo_ref is None:
+            raise ValueError("memory_prepare: num_propagated > 0 needs pseudo_ref")
+        _chk(pseudo_ref, "pseudo_ref", torch.float32, 2)
+        if pseudo_ref.shape[0] < P or pseudo_ref.shape[1] != 3:
+            raise ValueError("memory_prepare: pseudo_ref must be (>= %d, 3) (got %s)" % (P, tuple(pseudo_ref.shape)))
     dev = state["emb"].device
     m = {k: torch.empty_like(v) for k, v in state.items()}
     temp_ref = temp_ref_out if temp_ref_out is not None else torch.empty((L, 3), dtype=torch.float32, device=dev)
@@ -1218,8 +1260,8 @@ def memory_prepare(state, ego_pose_inv, timestamp, pseudo_ref, dim_t256, prev_ex
     tpos = torch.empty((L, 256), dtype=torch.float32, device=dev)
     pk, pp = _host_f32(list(pc_range))
     _lib.check(lib.far3d_memory_prepare(_ptr(state["emb"]), _ptr(state["ref"]), _ptr(state["ts"]), _ptr(state["pose"]), _ptr(state["velo"]),
-                                        _ptr(ego_pose_inv), _ptr(timestamp), _ptr(pseudo_ref) if pseudo_ref is not None else None,
-                                        _ptr(dim_t256), float(prev_exists), 1 if fresh else 0, pp, L, E, int(num_propagated),
+                                        _ptr(ego_pose_inv), _ptr(timestamp), _ptr(pseudo_ref) if P > 0 else None,
+                                        _ptr(dim_t256), float(prev_exists), 1 if fresh else 0, pp, L, E, P,
                                         _ptr(m["emb"]), _ptr(m["ref"]), _ptr(m["ts"]), _ptr(m["pose"]), _ptr(m["velo"]),
                                         _ptr(temp_ref), _ptr(nerf), _ptr(tpos), _stream(temp_ref)), "far3d_memory_prepare")
     return m, temp_ref, nerf, tpos
@@ -1243,11 +1285,28 @@ def head_finalize(reg, ref, cls_all, pc_range, layers, num_classes, hole=None):
 
 
 def memory_post_update(m, topk_idx, dec_last, box_last, ego_pose, timestamp, state):
+    """state <- [the K = len(topk_idx) selected queries (dec_last / box_last rows), then the first L - K slots of m], warped by ego_pose
+    (K <= L; K = 0 only warps).  m and state are distinct memory dicts of the same shapes; every element of state is written."""
     lib = _lib.require_device()
-    L, E = state["emb"].shape[1], state["emb"].shape[2]
+    L, E = _chk_memory(state, "memory_post_update: state")
+    _chk_memory(m, "memory_post_update: m", L, E)
     _chk(topk_idx, "topk_idx", torch.int64, 1)
+    _chk(dec_last, "dec_last", torch.float32, 2)
+    _chk(box_last, "box_last", torch.float32, 2)
+    _chk(ego_pose, "ego_pose", torch.float32)
+    _chk(timestamp, "timestamp", torch.float64)
+    K = topk_idx.numel()
+    if K > L:
+        raise ValueError("memory_post_update: %d selected queries do not fit the %d memory slots" % (K, L))
+    if dec_last.shape[1] != E or dec_last.shape[0] != box_last.shape[0] or box_last.shape[1] < 5:
+        raise ValueError("memory_post_update: dec_last must be (A, %d) and box_last (A, code >= 5) (got %s, %s)"
+                         % (E, tuple(dec_last.shape), tuple(box_last.shape)))
+    if ego_pose.numel() != 16 or timestamp.numel() != 1:
+        raise ValueError("memory_post_update: ego_pose must hold 16 values, timestamp one")
+    if any(m[k].data_ptr() == state[k].data_ptr() for k, _, _ in _MEM_KEYS):
+        raise ValueError("memory_post_update: m and state must be different buffers (slots are shifted, not updated in place)")
     _lib.check(lib.far3d_memory_post_update(_ptr(m["emb"]), _ptr(m["ref"]), _ptr(m["ts"]), _ptr(m["pose"]), _ptr(m["velo"]), _ptr(topk_idx),
-                                            _ptr(dec_last), _ptr(box_last), _ptr(ego_pose), _ptr(timestamp), L, E, topk_idx.numel(),
+                                            _ptr(dec_last), _ptr(box_last), _ptr(ego_pose), _ptr(timestamp), L, E, K,
                                             box_last.shape[1], _ptr(state["emb"]), _ptr(state["ref"]), _ptr(state["ts"]),
                                             _ptr(state["pose"]), _ptr(state["velo"]), _stream(dec_last)), "far3d_memory_post_update")
 

@@ -1,5 +1,6 @@
 """GPU: 2D proposal selection (C ABI far3d_proposal_select) -- the static top-K mode against a sort of the kernel's own
-peak-weight map (the threshold mode is pinned by the golden sequence in test_engine_gpu.py)."""
+peak-weight map.  The weight map itself, the threshold mode, the top-K mode against the float64 peak map and far3d_proposal_gather
+are checked against a float64 reference in test_proposals_gpu.py."""
 import numpy as np
 import pytest
 import torch
