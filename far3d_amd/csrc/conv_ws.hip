@@ -15,24 +15,25 @@ extern "C" int far3d_conv_ws_set_ablate(int mask) { g_ws_ablate.store(mask); ret
 
 int far3d_conv_ws_launch(const IgemmParams& P, int tile, hipStream_t st) {
   switch (tile) {
-    // (consumer grid WGM x WGN, tiles per consumer WM x WN, producers, pair, double-buffered fragments)
+    // (consumer grid WGM x WGN, tiles per consumer WM x WN, producers, pair, double-buffered fragments[, ring stages, FLAGS, taps per
+    // hand-over, deferred epilogue])
     case 400: return launch_conv3x3_ws<2, 4, 2, 2, 4, true, true>(P, st);    // 128 ch x 8 rows: 8 consumers of 64 ch x 2 rows + 4 producers
     case 401: return launch_conv3x3_ws<1, 8, 2, 1, 4, true, true>(P, st);    // 64 ch x 8 rows: 8 consumers of 64 ch x 1 row (Cout 64)
     case 402: return launch_conv3x3_ws<1, 8, 5, 1, 4, true, false>(P, st);   // 160 ch x 8 rows: 8 consumers of 160 ch x 1 row (stage 3)
     case 403: return launch_conv3x3_ws<2, 4, 3, 1, 4, true, true>(P, st);    // 192 ch x 4 rows: 8 consumers of 96 ch x 1 row (stage 4)
-    case 404: return launch_conv3x3_ws<2, 2, 1, 2, 2, true, true>(P, st);    // 64 ch x 4 rows: 4 consumers of 32 ch x 2 rows + 2 producers (2 per CU)
-    case 405: return launch_conv3x3_ws<2, 4, 2, 1, 4, true, true>(P, st);    // 128 ch x 4 rows: 8 consumers of 64 ch x 1 row
-    case 406: return launch_conv3x3_ws<2, 4, 1, 2, 4, true, true>(P, st);    // 64 ch x 8 rows: 8 consumers of 32 ch x 2 rows
+    case 404: return launch_conv3x3_ws<2, 2, 1, 2, 2, true, true, 3, false, 1, true>(P, st); // 64 ch x 4 rows: 4 consumers of 32 ch x 2 rows + 2 producers (2 per CU)
+    case 405: return launch_conv3x3_ws<2, 4, 2, 1, 4, true, true, 3, false, 1, true>(P, st); // 128 ch x 4 rows: 8 consumers of 64 ch x 1 row
+    case 406: return launch_conv3x3_ws<2, 4, 1, 2, 4, true, true, 3, false, 1, true>(P, st); // 64 ch x 8 rows: 8 consumers of 32 ch x 2 rows
     case 407: return launch_conv3x3_ws<1, 4, 5, 1, 2, true, false>(P, st);   // 160 ch x 4 rows: 4 consumers of 160 ch x 1 row + 2 producers
     case 408: return launch_conv3x3_ws<1, 4, 3, 1, 2, true, true>(P, st);    // 96 ch x 4 rows: 4 consumers + 2 producers (2 per CU)
     case 409: return launch_conv3x3_ws<2, 4, 2, 2, 2, true, true>(P, st);    // 400 with 2 producers
     // deeper weight rings (the producers run NSW - 1 steps ahead)
     case 410: return launch_conv3x3_ws<2, 4, 2, 2, 4, true, true, 4>(P, st);   // 400 with 4 stages (154 KB)
     case 411: return launch_conv3x3_ws<2, 4, 2, 1, 4, true, true, 6>(P, st);   // 405 (128 ch x 4 rows) with 6 stages
-    case 412: return launch_conv3x3_ws<2, 4, 1, 2, 4, true, true, 8>(P, st);   // 406 (64 ch x 8 rows) with 8 stages
+    case 412: return launch_conv3x3_ws<2, 4, 1, 2, 4, true, true, 8, false, 1, true>(P, st); // 406 (64 ch x 8 rows) with 8 stages
     case 413: return launch_conv3x3_ws<1, 8, 2, 1, 4, true, true, 8>(P, st);   // 401 (64 ch x 8 rows, Cout 64) with 8 stages
     case 414: return launch_conv3x3_ws<1, 4, 5, 1, 2, true, false, 5>(P, st);  // 407 (160 ch x 4 rows) with 5 stages
-    case 415: return launch_conv3x3_ws<2, 2, 1, 2, 2, true, true, 6>(P, st);   // 404 (64 ch x 4 rows, 2 per CU) with 6 stages
+    case 415: return launch_conv3x3_ws<2, 2, 1, 2, 2, true, true, 6, false, 1, true>(P, st); // 404 (64 ch x 4 rows, 2 per CU) with 6 stages
     case 416: return launch_conv3x3_ws<2, 4, 3, 1, 4, true, true, 4>(P, st);   // 403 (192 ch x 4 rows) with 4 stages
     case 417: return launch_conv3x3_ws<2, 4, 2, 1, 4, true, true, 4>(P, st);   // 405 with 4 stages
     case 418: return launch_conv3x3_ws<4, 2, 2, 2, 4, true, true, 3>(P, st);   // 256 ch x 4 rows: 8 consumers of 64 ch x 2 rows (148 KB)
@@ -44,24 +45,30 @@ int far3d_conv_ws_launch(const IgemmParams& P, int tile, hipStream_t st) {
     case 444: return launch_conv3x3_ws<2, 2, 1, 2, 2, true, true, 3, true>(P, st);   // 404 (64 ch x 4 rows, 2 per CU)
     case 445: return launch_conv3x3_ws<2, 4, 2, 1, 4, true, true, 6, true>(P, st);   // 411 (128 ch x 4 rows, 6 stages)
     // one barrier per KERNEL ROW (3 taps) instead of per tap, ring of 2 or 3 rows (GRP = 3)
-    case 450: return launch_conv3x3_ws<2, 4, 2, 1, 4, true, true, 6, false, 3>(P, st);   // 128 ch x 4 rows, ring of 2 rows (149 KB)
-    case 451: return launch_conv3x3_ws<2, 4, 1, 2, 4, true, true, 6, false, 3>(P, st);   // 64 ch x 8 rows, ring of 2 rows
-    case 452: return launch_conv3x3_ws<2, 4, 1, 2, 4, true, true, 9, false, 3>(P, st);   // 64 ch x 8 rows, ring of 3 rows (160 KB)
-    case 453: return launch_conv3x3_ws<1, 8, 2, 1, 4, true, true, 6, false, 3>(P, st);   // 64 ch x 8 rows (Cout 64), ring of 2 rows
+    case 450: return launch_conv3x3_ws<2, 4, 2, 1, 4, true, true, 6, false, 3, true>(P, st); // 128 ch x 4 rows, ring of 2 rows (149 KB)
+    case 451: return launch_conv3x3_ws<2, 4, 1, 2, 4, true, true, 6, false, 3, true>(P, st); // 64 ch x 8 rows, ring of 2 rows
+    case 452: return launch_conv3x3_ws<2, 4, 1, 2, 4, true, true, 9, false, 3, true>(P, st); // 64 ch x 8 rows, ring of 3 rows (160 KB)
+    case 453: return launch_conv3x3_ws<1, 8, 2, 1, 4, true, true, 6, false, 3, true>(P, st); // 64 ch x 8 rows (Cout 64), ring of 2 rows
     case 454: return launch_conv3x3_ws<1, 8, 2, 1, 4, true, true, 9, false, 3>(P, st);   // 64 ch x 8 rows (Cout 64), ring of 3 rows
     case 455: return launch_conv3x3_ws<1, 7, 2, 1, 4, true, true, 9, false, 3>(P, st);   // 64 ch x 7 rows: stage 4's 40 rows = 6 x 7 -> 252 items on 256 CUs
-    case 456: return launch_conv3x3_ws<2, 7, 1, 1, 2, true, true, 9, false, 3>(P, st);   // 64 ch x 7 rows, 14 consumers of 32 ch x 1 row + 2 producers
-    case 457: return launch_conv3x3_ws<2, 2, 1, 2, 2, true, true, 6, false, 3>(P, st);   // 64 ch x 4 rows, 4 consumers + 2 producers
+    case 456: return launch_conv3x3_ws<2, 7, 1, 1, 2, true, true, 9, false, 3, true>(P, st); // 64 ch x 7 rows, 14 consumers of 32 ch x 1 row + 2 producers
+    case 457: return launch_conv3x3_ws<2, 2, 1, 2, 2, true, true, 6, false, 3, true>(P, st); // 64 ch x 4 rows, 4 consumers + 2 producers
     case 458: return launch_conv3x3_ws<1, 4, 3, 1, 2, true, true, 6, false, 3>(P, st);   // 96 ch x 4 rows, 4 consumers + 2 producers
-    case 459: return launch_conv3x3_ws<2, 4, 1, 1, 4, true, true, 9, false, 3>(P, st);   // 64 ch x 4 rows, 8 consumers of 32 ch x 1 row, ring of 3 rows
+    case 459: return launch_conv3x3_ws<2, 4, 1, 1, 4, true, true, 9, false, 3, true>(P, st); // 64 ch x 4 rows, 8 consumers of 32 ch x 1 row, ring of 3 rows
     case 420: return launch_conv3x3_ws<2, 4, 2, 2, 4, false, true>(P, st);   // plain bf16: 128 ch x 8 rows
-    case 421: return launch_conv3x3_ws<1, 8, 2, 1, 4, false, true>(P, st);   // plain bf16: 64 ch x 8 rows
+    case 421: return launch_conv3x3_ws<1, 8, 2, 1, 4, false, true, 3, false, 1, true>(P, st); // plain bf16: 64 ch x 8 rows
     case 422: return launch_conv3x3_ws<1, 8, 5, 1, 4, false, true>(P, st);   // plain bf16: 160 ch x 8 rows
     case 423: return launch_conv3x3_ws<2, 4, 3, 1, 4, false, true>(P, st);   // plain bf16: 192 ch x 4 rows
     default: break;
   }
   far3d_set_error("far3d_conv2d_nhwc: unknown wave-specialised tile %d", tile);
   return FAR3D_ERR_ARG;
+}
+
+// The item dealing of a single-problem launch, for tests (include/far3d_hip.h): the inline function the kernel evaluates.
+extern "C" int far3d_ws_deal(int n_full, int n_light, int grid, int wg, int k) {
+  if (n_full < 0 || n_light < 0 || grid < 1 || wg < 0 || wg >= grid) return -1;
+  return ws_deal_item(n_full, n_light, grid, wg, k);
 }
 
 // The wave-specialised persistent 1x1 GEMM on pair-stored maps (gemm1x1_ws_kernel), tile ids 460-477:
@@ -95,9 +102,9 @@ static int far3d_conv_ws_grouped_launch(const IgemmParams& P, const WsGroup& G, 
   switch (tile) {
     case 500: return launch_conv3x3_ws_grouped<2, 4, 2, 2, 4, true, true>(P, G, st);                 // 400: 128 ch x 8 rows
     case 505: return launch_conv3x3_ws_grouped<2, 4, 2, 1, 4, true, true>(P, G, st);                 // 405: 128 ch x 4 rows
-    case 552: return launch_conv3x3_ws_grouped<2, 4, 1, 2, 4, true, true, 9, false, 3>(P, G, st);    // 452: 64 ch x 8 rows, ring of 3 rows
-    case 556: return launch_conv3x3_ws_grouped<2, 7, 1, 1, 2, true, true, 9, false, 3>(P, G, st);    // 456: 64 ch x 7 rows, 14 consumers
-    case 559: return launch_conv3x3_ws_grouped<2, 4, 1, 1, 4, true, true, 9, false, 3>(P, G, st);    // 459: 64 ch x 4 rows, ring of 3 rows
+    case 552: return launch_conv3x3_ws_grouped<2, 4, 1, 2, 4, true, true, 9, false, 3, true>(P, G, st); // 452: 64 ch x 8 rows, ring of 3 rows
+    case 556: return launch_conv3x3_ws_grouped<2, 7, 1, 1, 2, true, true, 9, false, 3, true>(P, G, st); // 456: 64 ch x 7 rows, 14 consumers
+    case 559: return launch_conv3x3_ws_grouped<2, 4, 1, 1, 4, true, true, 9, false, 3, true>(P, G, st); // 459: 64 ch x 4 rows, ring of 3 rows
     default: break;
   }
   far3d_set_error("far3d_conv2d_nhwc_grouped: unknown grouped tile %d", tile);

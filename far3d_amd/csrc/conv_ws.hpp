@@ -12,7 +12,7 @@
 //   * WGM x WGN CONSUMER waves never issue a vector-memory instruction inside the K loop: fragments come from LDS (double-buffered
 //     in registers, the loads of one k-half under the MFMAs of the previous one, ACROSS the step barrier), WM x WN tiles of 32 x 32
 //     per wave on v_mfma_f32_32x32x16_bf16;
-//   * the workgroup is PERSISTENT: it walks its tiles (static round-robin over the launch's tile list) as ONE stream of steps, so
+//   * the workgroup is PERSISTENT: it walks its tiles (a closed-form deal of the launch's tile list, ws_deal_* below) as ONE stream of steps, so
 //     the producers fill the ring for the first steps of tile t+1 while the consumers finish tile t; the epilogue has no LDS
 //     staging and no barrier -- bias / activation / hi-lo split in registers, v_permlane32_swap pairs the half-waves' 8-byte pieces
 //     into 16-byte stores -- so it costs its own instructions only and the next tile's operands are already resident when it ends.
@@ -52,7 +52,9 @@ __device__ __forceinline__ void wait_vmcnt_dyn(int n) {      // s_waitcnt vmcnt(
 }
 
 // Timing-only ablation switch of the probes (tools/probe/ws_conv_ab.py; results are WRONG when set): bit 0 the producers issue no DMA,
-// bit 1 the consumers skip fragment reads and MFMAs.  PROFILING BUILD ONLY (libfar3d_hip_prof.so, -DFAR3D_PROFILING): the shipped
+// bit 1 the consumers skip fragment reads and MFMAs.  Two further bits leave the results RIGHT and switch one part of the 3x3 kernel back,
+// for on / off timings of that part alone (tools/probe/ws_conv_parts.py): bit 4 (16) every epilogue runs in place (no deferral), bit 5 (32)
+// the items are dealt blockIdx + k * gridDim as before the cost deal.  PROFILING BUILD ONLY (libfar3d_hip_prof.so, -DFAR3D_PROFILING): the shipped
 // library has neither the switch nor the setter, its kernels get a constant 0.
 #ifdef FAR3D_PROFILING
 extern std::atomic<int> g_ws_ablate;
@@ -83,7 +85,66 @@ struct WsSingle {};
 // id, 1 s_memtime at entry, 2 first step's operands landed (consumer wave 0 past the first barrier), 3 s_memtime at the end of consumer
 // wave 0, 4 tiles processed, 5 steps, 6 / 7 s_memrealtime (100 MHz) at entry / end, 8 cycles consumer wave 0 spent between arriving at a
 // step's barrier and leaving it, 9 cycles it spent in the steps' bodies (fragment reads + MFMA issue), 10 cycles in the epilogues.
-template <int WGM, int WGN, int WM, int WN, int NP, bool PAIR, bool DBUF, int NSW = 3, bool FLAGS = false, int GRP = 1, class GT = WsSingle>
+//
+// Padded channel slices (Cout no multiple of the channel tile: stage 3's 160 = 64 + 64 + 32, stage 5's 224): a consumer reads no weight
+// fragment and issues no MFMA for a 32-channel slice that lies beyond Cout -- it only keeps the hand-overs -- and the producers describe
+// the weight rows up to Cout only, so that the ring rows nobody reads are zero-filled by the descriptor without memory traffic (the DMA
+// count per tap stays what the counted vmcnt waits expect).  The products of every STORED element and their order are untouched.
+// The skip is compiled for the consumers of at most two 32 x 32 tiles (WM * WN <= 2: the BM = 64 tiles and 405 / 450); the wider ones
+// run at the register limit, where neither a branch per slice nor a second copy of the steps fits without scratch, and keep the padded MFMAs.
+//
+// Dealing by cost (single-problem launches): an item of the last, partly empty channel tile is LIGHT.  ws_deal_* below is the one mapping
+// (workgroup, ordinal of the workgroup's item) -> launch item that the producers' decode and the consumers' loop share; it is closed-form,
+// so nothing is read, counted or polled at run time and a captured launch replays it.  Cost model: a light item = HALF a full one
+// (FAR3D_WS_DEAL_FULL : FAR3D_WS_DEAL_LIGHT = 2 : 1).  The F full items go first, round-robin: workgroup b gets the fulls b, b + G, ...
+// -- the first F % G workgroups one more than the others.  The others then get up to two lights each (round-robin among THEM), which
+// levels the grid under the cost model, and what is left goes round-robin over all workgroups.  That is what greedy longest-first gives
+// for costs 2 : 1 up to the order of ties, so the heaviest workgroup is within one light item of its bound (tests/test_ws_deal_cpu.py).
+#define FAR3D_WS_DEAL_FULL 2
+#define FAR3D_WS_DEAL_LIGHT 1
+// ws_deal_prepare does the divisions once per workgroup; ws_deal_at is a compare and a multiply-add per item.
+struct WsDeal {
+  int F, G, b;             // full items of the launch, workgroups, this workgroup
+  int nf, n1, n2;          // this workgroup's full items, levelling lights, remaining lights
+  int p, Nn, L1;           // its rank among the Nn workgroups that take levelling lights; levelling lights of the launch
+};
+__host__ __device__ inline WsDeal ws_deal_prepare(int F, int L, int G, int b) {
+  WsDeal d;
+  d.F = F; d.G = G; d.b = b;
+  const int rem = F % G;
+  d.Nn = G - rem;
+  const int lvl = (FAR3D_WS_DEAL_FULL / FAR3D_WS_DEAL_LIGHT) * d.Nn;      // lights that level the grid
+  d.L1 = rem ? (L < lvl ? L : lvl) : 0;
+  const int L2 = L - d.L1;
+  d.nf = F > b ? (F - b + G - 1) / G : 0;
+  d.p = b - rem;
+  d.n1 = (rem && d.p >= 0 && d.L1 > d.p) ? (d.L1 - d.p + d.Nn - 1) / d.Nn : 0;
+  d.n2 = L2 > b ? (L2 - b + G - 1) / G : 0;
+  return d;
+}
+__host__ __device__ inline int ws_deal_count(const WsDeal& d) { return d.nf + d.n1 + d.n2; }
+// the k-th item of the workgroup: 0 .. F - 1 = that full item, F .. F + L - 1 = light item (value - F); -1 = it has no k-th item
+__host__ __device__ inline int ws_deal_at(const WsDeal& d, int k) {
+  if (k < 0) return -1;
+  if (k < d.nf) return d.b + k * d.G;
+  k -= d.nf;
+  if (k < d.n1) return d.F + d.p + k * d.Nn;
+  k -= d.n1;
+  return k < d.n2 ? d.F + d.L1 + d.b + k * d.G : -1;
+}
+__host__ __device__ inline int ws_deal_item(int F, int L, int G, int b, int k) { return ws_deal_at(ws_deal_prepare(F, L, G, b), k); }
+
+// Deferred epilogue (DEFER; tiles whose consumers hold a second accumulator set without scratch): the workgroup is persistent, so at the
+// end of an item the next item's operands are already resident and nothing but program order kept the epilogue's stores -- all eight
+// consumers at the same step, through the CU's one texture-address path, the matrix pipe idle -- out of the next item's steps.  With
+// DEFER the accumulators and the coordinates of item k become PENDING and the wave goes straight to item k + 1's first hand-over; after
+// the MFMA issue of each hand-over group of that item's FIRST chunk it emits SPG slices of the pending epilogue (a slice = one
+// (i, j, quad pair): activation, split, permlane32_swap, its 16-byte stores).  The epilogue's first operation, accumulator + bias, is
+// done when the item ends and the SUM is what stays pending, so that no bias value has to live through the steps.
+// A chunk has 9 / GRP hand-over groups and SPG = ceil(slices / (9 / GRP)), so the pending set always drains inside the first chunk:
+// nothing is left to flush when the item ends.  The last item's epilogue runs in place.  The arithmetic is the same code in both places.
+template <int WGM, int WGN, int WM, int WN, int NP, bool PAIR, bool DBUF, int NSW = 3, bool FLAGS = false, int GRP = 1, class GT = WsSingle,
+          bool DEFER = false>
 __global__ __launch_bounds__(64 * (WGM * WGN + NP)) void conv3x3_ws_kernel(IgemmParams P, int tiles_x, int tiles_y, int n_mt, int n_items, int ablate,
                                                                           GT GP) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -126,7 +187,36 @@ __global__ __launch_bounds__(64 * (WGM * WGN + NP)) void conv3x3_ws_kernel(Igemm
   const int t = threadIdx.x, lane = t & 63, wv = __builtin_amdgcn_readfirstlane(t >> 6);
   const int nchunks = P.cin_pad / 32;
   const int spt = 9 * nchunks;                                                   // steps per tile
-  const int my_items = (n_items - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x;
+  static_assert(!DEFER || (!FLAGS && WM * WN * 16 <= 32), "the deferred epilogue: barrier hand-over, at most 32 accumulators per lane");
+  // single-problem launches deal their items by cost (ws_deal_*): the items of a partly empty last channel tile are light
+  // (only where the padded slices are skipped, SKIP below: on the wider tiles such an item costs what a full one does)
+  constexpr bool SKIP = WM * WN <= 2;
+  [[maybe_unused]] int deal_f = n_items, deal_l = 0;
+  if constexpr (!GROUPED && SKIP) {
+    if (P.Cout % BM) { deal_l = n_items / n_mt; deal_f = n_items - deal_l; }
+#ifdef FAR3D_PROFILING
+    if (ablate & 32) { deal_l = 0; deal_f = n_items; }
+#endif
+  }
+#ifdef FAR3D_PROFILING
+  const bool defer_on = DEFER && !(ablate & 16);
+#else
+  constexpr bool defer_on = DEFER;
+#endif
+  const WsDeal deal = ws_deal_prepare(deal_f, deal_l, (int)gridDim.x, (int)blockIdx.x);
+  const int my_items = GROUPED ? (n_items - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x : ws_deal_count(deal);
+  // ordinal k of this workgroup's items -> item of the problem as (channel tile, pixel tile); grouped launches: the launch item
+  auto item_of = [&](int k, int& mt, int& pt) __attribute__((always_inline)) {
+    if constexpr (GROUPED) {
+      return (int)blockIdx.x + k * (int)gridDim.x;
+    } else {
+      const int o = ws_deal_at(deal, k);
+      if (deal_l == 0) { mt = o % n_mt; pt = o / n_mt; }
+      else if (o >= deal_f) { mt = n_mt - 1; pt = o - deal_f; }      // a light item: the last channel tile
+      else { const int nfm = n_mt - 1; mt = o % nfm; pt = o / nfm; }
+      return o;
+    }
+  };
   const int total_steps = my_items * spt, total_chunks = my_items * nchunks;
   const int Ktot = 9 * P.cin_pad * PLD;               // elements of a packed weight row
   // launch item -> (problem q, item of the problem li, the problem's tile grid); a single-problem launch is problem 0 of the arguments
@@ -170,10 +260,11 @@ __global__ __launch_bounds__(64 * (WGM * WGN + NP)) void conv3x3_ws_kernel(Igemm
     const bf16_t* w_base = nullptr;                    // first weight row of the weight cursor's tile
     long w_bytes = 0;
     auto decode = [&](int k, int& n, int& y0, int& x0, int& m0, int& q) __attribute__((always_inline)) {
-      const int item = (int)blockIdx.x + k * (int)gridDim.x;
+      int mt = 0, pt = 0;
+      const int item = item_of(k, mt, pt);
       int li, txs, tys, nmt;
       locate(item, q, li, txs, tys, nmt);
-      const int mt = li % nmt, pt = li / nmt;
+      if constexpr (GROUPED) { mt = li % nmt; pt = li / nmt; }
       const int tx = pt % txs, r = pt / txs;
       const int ty = r % tys;
       n = __builtin_amdgcn_readfirstlane(r / tys); y0 = __builtin_amdgcn_readfirstlane(ty * TH);
@@ -186,7 +277,8 @@ __global__ __launch_bounds__(64 * (WGM * WGN + NP)) void conv3x3_ws_kernel(Igemm
       int Cout = P.Cout;
       if constexpr (GROUPED) { w = GP.p[q].w; Cout = GP.p[q].Cout; }
       w_base = reinterpret_cast<const bf16_t*>(w) + (long)m0 * Ktot;
-      w_bytes = w_tile_bytes(BM, m0, Cout, Ktot);
+      const int rows = Cout - m0;                      // rows beyond Cout: zero fill by the descriptor, no memory traffic (nobody reads them)
+      w_bytes = (long)(rows < BM ? (rows > 0 ? rows : 0) : BM) * Ktot * 2;
     };
     auto set_p_tile = [&](int k) __attribute__((always_inline)) {
       int n, y0, x0, m0, q;
@@ -325,69 +417,168 @@ __global__ __launch_bounds__(64 * (WGM * WGN + NP)) void conv3x3_ws_kernel(Igemm
     }
   f32x16_t acc[WM][WN];
   u32x4_t fa[2][PLD][WM], fb[2][PLD][WN];              // fragment sets X = [0], Y = [1]
+  // valid 32-channel slices of this wave in the current item (wave-uniform; slice i covers channels m0 + (wm * WM + i) * 32 ..): the
+  // slices beyond Cout get neither fragment reads nor MFMAs
+  int nv = WM;
 
-  // Fragment loads of one k-half, split into the weight (A) and the patch (B) part, and the products of one k-half split by term: a step
-  // interleaves them so that no more than 12 ds_read_b128 are ever outstanding -- lgkmcnt is a 4-bit counter, and with the 16 reads of
-  // two full sets in flight hipcc falls back to `s_waitcnt lgkmcnt(0)` before the first MFMA of the newer set, which exposed a whole LDS
-  // round trip per step (~240 cycles of a 770-cycle body: tools/probe/ws_conv_prof.py, round 6).
-  auto load_a = [&](int set, int soff, int kk) __attribute__((always_inline)) {      // soff: byte offset of the ring stage (wave-uniform)
-#ifdef FAR3D_PROFILING
-    if (ablate & 4) return;                              // timing-only: MFMAs on stale registers
-#endif
-    const int x32 = kk * 32;
+
+  // ---- epilogue in registers: lane (l31, hi) holds, per 32 x 32 tile and quad q, channels 8q + 4hi .. + 3 of pixel (row, l31).
+  // v_permlane32_swap hands the upper half-wave's quad q to the lower lanes and the lower's quad q + 1 to the upper ones: every lane
+  // then owns 8 consecutive channels = one 16-byte store per plane and quad pair.  A SLICE is one (i, j, quad pair) of an item; epi_bias
+  // fetches the bias values of its two quads; epi_slice<BIASED> takes a set that already holds accumulator + bias (the pending set).
+  auto epi_bias = [&](int i, int qp, int m0, int prob, float4 (&b4)[2]) __attribute__((always_inline)) {
+    const float* bias = P.bias;
+    int Cout = P.Cout;
+    if constexpr (GROUPED) { bias = GP.p[prob].bias; Cout = GP.p[prob].Cout; }
+    const int cb = m0 + (wm * WM + i) * 32;
 #pragma unroll
-    for (int pl = 0; pl < PLD; ++pl)
-#pragma unroll
-      for (int i = 0; i < WM; ++i) fa[set][pl][i] = *reinterpret_cast<const u32x4_t*>(smem + pl * WST + ((aaddr[i] ^ x32) + soff));
+    for (int u = 0; u < 2; ++u) {
+      b4[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (bias && cb < Cout) b4[u] = *reinterpret_cast<const float4*>(bias + cb + 8 * (2 * qp + u) + 4 * hi);
+    }
   };
-  auto load_b = [&](int set, int tap, int kk) __attribute__((always_inline)) {
-#ifdef FAR3D_PROFILING
-    if (ablate & 4) return;
-#endif
-    const int ky = tap / 3, kx = tap - 3 * ky, x32 = kk * 32;
+  auto epi_slice = [&](auto biased_tag, const f32x16_t (&A)[WM][WN], int i, int j, int qp, int n, int y0, int x0, int m0, int prob,
+                       const float4 (*b4)[2] = nullptr) __attribute__((always_inline)) {
+    constexpr bool BIASED = decltype(biased_tag)::value;      // A already holds accumulator + bias (the pending set of the deferred form)
+    const int px = x0 + l31;
+    void* y = P.y;
+    long yis = P.y_img_stride;
+    int Ho = P.Ho, Wo = P.Wo, ldy = P.ldy, Cout = P.Cout, act = P.act;
+    [[maybe_unused]] float* y2 = nullptr;
+    [[maybe_unused]] const float *y2s = nullptr, *y2h = nullptr;
+    [[maybe_unused]] long y2is = 0;
+    [[maybe_unused]] int ldy2 = 0;
+    if constexpr (GROUPED) {
+      const WsProblem& pq = GP.p[prob];
+      y = pq.y; yis = pq.y_img_stride; Ho = pq.H; Wo = pq.W; ldy = pq.ldy; Cout = pq.Cout; act = pq.act;
+      y2 = pq.y2; y2s = pq.y2_scale; y2h = pq.y2_shift; y2is = pq.y2_img_stride; ldy2 = pq.ldy2;
+    }
+    unsigned char* yb = reinterpret_cast<unsigned char*>(y);
+    const int py = y0 + wn * WN + j;
+    const bool ok = py < Ho && px < Wo;
+    const long pix_b = ((long)n * yis + ((long)py * Wo + px) * ldy) * 2;      // bytes
+    const int cb = m0 + (wm * WM + i) * 32;              // first channel of this 32-channel block
+    if (cb >= Cout) return;                              // wave-uniform (Cout % 32 == 0)
+    uint2 h[2], l[2];
 #pragma unroll
-    for (int pl = 0; pl < PLD; ++pl)
+    for (int u = 0; u < 2; ++u) {                        // quad pairs (0,1) and (2,3)
+      const int q = 2 * qp + u;
+      float v[4];
 #pragma unroll
-      for (int j = 0; j < WN; ++j) fb[set][pl][j] = *reinterpret_cast<const u32x4_t*>(smem + pl * PATCH_B + (baddr[j + ky][kx] ^ x32));
+      for (int e = 0; e < 4; ++e) v[e] = A[i][j][4 * q + e];
+      if constexpr (!BIASED) { const float4 bq = (*b4)[u]; v[0] += bq.x; v[1] += bq.y; v[2] += bq.z; v[3] += bq.w; }
+      if (act == ACT_RELU) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
+      } else if (act == ACT_SWISH) {
+        if constexpr (PAIR) {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) v[e] = v[e] * (1.f / (1.f + expf(-v[e])));
+        } else {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) v[e] = v[e] * __frcp_rn(1.f + __expf(-v[e]));
+        }
+      }
+      if constexpr (GROUPED) {
+        if (y2 && ok) {                                  // fp32 second output of this lane's 4 channels: one 16-byte store
+          const int m = cb + 8 * q + 4 * hi;
+          const long so = (long)n * Cout + m;
+          float w4[4];
+#pragma unroll
+          for (int e = 0; e < 4; ++e) w4[e] = y2s[so + e] * v[e] + y2h[so + e];
+          *reinterpret_cast<float4*>(y2 + n * y2is + ((long)py * Wo + px) * ldy2 + m) = make_float4(w4[0], w4[1], w4[2], w4[3]);
+        }
+      }
+      if constexpr (PAIR) split4f(v[0], v[1], v[2], v[3], h[u], l[u]);
+      else { h[u] = make_uint2(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3])); l[u] = make_uint2(0u, 0u); }
+    }
+    // lower lanes: [own quad 2qp | upper's quad 2qp]; upper lanes: [lower's quad 2qp+1 | own quad 2qp+1]
+    u32x4_t oh, ol;
+    {
+      const auto sx = __builtin_amdgcn_permlane32_swap(h[0].x, h[1].x, false, false);
+      const auto sy = __builtin_amdgcn_permlane32_swap(h[0].y, h[1].y, false, false);
+      oh = u32x4_t{sx[0], sy[0], sx[1], sy[1]};
+    }
+    const int qoff = (2 * qp + hi) * 16;                 // byte offset of the lane's 8 channels inside a 64-byte plane row
+    if constexpr (PAIR) {
+      const auto sx = __builtin_amdgcn_permlane32_swap(l[0].x, l[1].x, false, false);
+      const auto sy = __builtin_amdgcn_permlane32_swap(l[0].y, l[1].y, false, false);
+      ol = u32x4_t{sx[0], sy[0], sx[1], sy[1]};
+      if (ok) {
+        unsigned char* d = yb + pix_b + (long)(cb >> 5) * 128 + qoff;
+        *reinterpret_cast<u32x4_t*>(d) = oh;
+        *reinterpret_cast<u32x4_t*>(d + 64) = ol;
+      }
+    } else {
+      if (ok) *reinterpret_cast<u32x4_t*>(yb + pix_b + (long)cb * 2 + qoff) = oh;
+    }
   };
-  auto load_set = [&](int set, int soff, int tap, int kk) __attribute__((always_inline)) { load_a(set, soff, kk); load_b(set, tap, kk); };
-  // pair mode: term 0 = lo*hi', 1 = hi*lo', 2 = hi*hi' (small terms first; term-major so that consecutive MFMAs hit different accumulators)
-  auto mma_term = [&](int set, int term) __attribute__((always_inline)) {
-    const int pa = (PAIR && term == 0) ? 1 : 0, pb = (PAIR && term == 1) ? 1 : 0;
-#pragma unroll
-    for (int i = 0; i < WM; ++i)
-#pragma unroll
-      for (int j = 0; j < WN; ++j) mma<bf16_t>(acc[i][j], fa[set][pa][i], fb[set][pb][j]);
-  };
-  auto mma_set = [&](int set) __attribute__((always_inline)) {
-    if constexpr (PAIR) { mma_term(set, 0); mma_term(set, 1); }
-    mma_term(set, 2);
-  };
+  // the pending item of the deferred epilogue: its accumulators, coordinates and (grouped launches) problem
+  constexpr int NSL = WM * WN * 2, NHG = 9 / GRP, SPG = (NSL + NHG - 1) / NHG;      // slices, hand-over groups of a chunk, slices per group
+  [[maybe_unused]] f32x16_t pacc[DEFER ? WM : 1][DEFER ? WN : 1];                  // accumulator + bias: the first operation of the epilogue
+  [[maybe_unused]] int pd_n = 0, pd_y0 = 0, pd_x0 = 0, pd_m0 = 0, pd_prob = 0;
 
   int G = 0;                                             // global chunk ordinal of this workgroup (patch buffer = G & 1)
   int soff = 0;                                          // ring stage of the current step, in bytes
   [[maybe_unused]] int Sg = 0;                           // FLAGS: global step ordinal
   [[maybe_unused]] u32x4_t pfl = {0u, 0u, 0u, 0u};       // FLAGS: the producers' counters as last read
 #ifdef FAR3D_PROFILING
-  unsigned long long pf_ta = 0, pf_tb = 0, pf_wait = 0, pf_body = 0, pf_epi = 0;
+  unsigned long long pf_ta = 0, pf_tb = 0, pf_wait = 0, pf_body = 0, pf_epi = 0, pf_dg = 0;      // pf_dg: deferred-epilogue cycles inside the current group
   const bool pf_on = P.prof != nullptr && wv == 0;
 #endif
-  for (int k = 0; k < my_items; ++k) {
-    const int item = (int)blockIdx.x + k * (int)gridDim.x;
-    int prob, li, txs, tys, nmt;
-    locate(item, prob, li, txs, tys, nmt);
-    const int mt = li % nmt, pt = li / nmt;
-    const int tx = pt % txs, rr = pt / txs;
-    const int ty = rr % tys, n = rr / tys;
-    const int x0 = tx * 32, y0 = ty * TH, m0 = mt * BM;
-#pragma unroll
-    for (int i = 0; i < WM; ++i)
-#pragma unroll
-      for (int j = 0; j < WN; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  // The steps of one item.  NVC: the wave's valid 32-channel slices as a compile-time count -- every slice, or, where the skip is
+  // compiled (SKIP), each smaller count: the steps stay straight-line code (a run-time branch per slice inside the step cost registers,
+  // scheduling freedom and scratch).
+  auto run_chunks = [&](auto nvc_tag, int k) __attribute__((always_inline)) {
+    constexpr int NVC = decltype(nvc_tag)::value;
+    auto slice_on = [&](int i) __attribute__((always_inline)) { return i < NVC; };
 
-    for (int c = 0; c < nchunks; ++c, ++G) {
+    // Fragment loads of one k-half, split into the weight (A) and the patch (B) part, and the products of one k-half split by term: a step
+    // interleaves them so that no more than 12 ds_read_b128 are ever outstanding -- lgkmcnt is a 4-bit counter, and with the 16 reads of
+    // two full sets in flight hipcc falls back to `s_waitcnt lgkmcnt(0)` before the first MFMA of the newer set, which exposed a whole LDS
+    // round trip per step (~240 cycles of a 770-cycle body: tools/probe/ws_conv_prof.py, round 6).
+    auto load_a = [&](int set, int soff, int kk) __attribute__((always_inline)) {      // soff: byte offset of the ring stage (wave-uniform)
+#ifdef FAR3D_PROFILING
+      if (ablate & 4) return;                              // timing-only: MFMAs on stale registers
+#endif
+      const int x32 = kk * 32;
+#pragma unroll
+      for (int pl = 0; pl < PLD; ++pl)
+#pragma unroll
+        for (int i = 0; i < WM; ++i)
+          if (slice_on(i)) fa[set][pl][i] = *reinterpret_cast<const u32x4_t*>(smem + pl * WST + ((aaddr[i] ^ x32) + soff));
+    };
+    auto load_b = [&](int set, int tap, int kk) __attribute__((always_inline)) {
+#ifdef FAR3D_PROFILING
+      if (ablate & 4) return;
+#endif
+      if (!slice_on(0)) return;                                 // no valid slice: nobody multiplies the patch
+      const int ky = tap / 3, kx = tap - 3 * ky, x32 = kk * 32;
+#pragma unroll
+      for (int pl = 0; pl < PLD; ++pl)
+#pragma unroll
+        for (int j = 0; j < WN; ++j) fb[set][pl][j] = *reinterpret_cast<const u32x4_t*>(smem + pl * PATCH_B + (baddr[j + ky][kx] ^ x32));
+    };
+    auto load_set = [&](int set, int soff, int tap, int kk) __attribute__((always_inline)) { load_a(set, soff, kk); load_b(set, tap, kk); };
+    // pair mode: term 0 = lo*hi', 1 = hi*lo', 2 = hi*hi' (small terms first; term-major so that consecutive MFMAs hit different accumulators)
+    auto mma_term = [&](int set, int term) __attribute__((always_inline)) {
+      const int pa = (PAIR && term == 0) ? 1 : 0, pb = (PAIR && term == 1) ? 1 : 0;
+#pragma unroll
+      for (int i = 0; i < WM; ++i)
+        if (slice_on(i)) {
+#pragma unroll
+          for (int j = 0; j < WN; ++j) mma<bf16_t>(acc[i][j], fa[set][pa][i], fb[set][pb][j]);
+        }
+    };
+    auto mma_set = [&](int set) __attribute__((always_inline)) {
+      if constexpr (PAIR) { mma_term(set, 0); mma_term(set, 1); }
+      mma_term(set, 2);
+    };
+
+    // one 32-channel chunk = nine taps.  FIRST: the item's first chunk, compiled apart -- it has no previous step's second k-half to
+    // multiply, and it carries the pending epilogue of the deferred form; the other chunks are one rolled loop without either.
+    auto chunk = [&](auto first_tag) __attribute__((always_inline)) {
+      constexpr bool FIRST = decltype(first_tag)::value;
 #pragma unroll
       for (int tap = 0; tap < 9; ++tap) {
         const int stage = soff;
@@ -399,7 +590,7 @@ __global__ __launch_bounds__(64 * (WGM * WGN + NP)) void conv3x3_ws_kernel(Igemm
 #ifdef FAR3D_PROFILING
         if (pf_on) {                                     // stamps are read here, where the wave waits for lgkmcnt(0) anyway
           const unsigned long long now = __builtin_amdgcn_s_memtime();
-          if (pf_tb) { pf_wait += pf_tb - pf_ta; pf_body += now - pf_tb; }
+          if (pf_tb) { pf_wait += pf_tb - pf_ta; pf_body += now - pf_tb - pf_dg; pf_dg = 0; }      // deferred epilogue slices count as epilogue
           pf_ta = now;
         }
 #endif
@@ -430,14 +621,14 @@ __global__ __launch_bounds__(64 * (WGM * WGN + NP)) void conv3x3_ws_kernel(Igemm
         __builtin_amdgcn_sched_barrier(0);
 #ifdef FAR3D_PROFILING
         if (pf_on) pf_tb = __builtin_amdgcn_s_memtime();
-        if (tap == 0 && c == 0 && k == 0 && P.prof && t == 0) P.prof[(long)blockIdx.x * 16 + 2] = (unsigned long long)__builtin_amdgcn_s_memtime();
+        if (tap == 0 && FIRST && k == 0 && P.prof && t == 0) P.prof[(long)blockIdx.x * 16 + 2] = (unsigned long long)__builtin_amdgcn_s_memtime();
 #endif
         }
         if (ablate & 2) { soff = soff == (NSW - 1) * WSTAGE ? 0 : soff + WSTAGE; continue; }      // timing-only: barriers alone
         if constexpr (DBUF) {
           load_set(0, stage, tap, 0);                    // X <- (S, k-half 0): 2 PLD (WM + WN) reads
           __builtin_amdgcn_sched_barrier(0);
-          if (tap > 0 || c > 0) mma_set(1);              // Y = (S - 1, k-half 1): its latency-free MFMAs cover X's LDS round trip
+          if (tap > 0 || !FIRST) mma_set(1);              // Y = (S - 1, k-half 1): its latency-free MFMAs cover X's LDS round trip
           __builtin_amdgcn_sched_barrier(0);
           load_a(1, stage, 1);                           // Y's weight fragments; X has landed by now, the counter never holds two full sets
           if constexpr (FLAGS) pfl = *reinterpret_cast<volatile u32x4_t*>(smem + FLAGB);      // the producers' counters, for the next step's check
@@ -468,6 +659,23 @@ __global__ __launch_bounds__(64 * (WGM * WGN + NP)) void conv3x3_ws_kernel(Igemm
           __builtin_amdgcn_sched_barrier(0);
           soff = soff == (NSW - 1) * WSTAGE ? 0 : soff + WSTAGE;
         }
+        if constexpr (DEFER) {
+          if (tap % GRP == GRP - 1 && k > 0 && FIRST && defer_on) {   // behind the MFMA issue of a hand-over group: SPG slices of the pending epilogue
+#ifdef FAR3D_PROFILING
+            unsigned long long pf_d0 = 0;
+            if (pf_on) pf_d0 = __builtin_amdgcn_s_memtime();
+#endif
+#pragma unroll
+            for (int u = 0; u < SPG; ++u) {
+              const int sl = (tap / GRP) * SPG + u;
+              if (sl < NSL) epi_slice(std::true_type{}, pacc, (sl >> 1) % WM, (sl >> 1) / WM, sl & 1, pd_n, pd_y0, pd_x0, pd_m0, pd_prob);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+#ifdef FAR3D_PROFILING
+            if (pf_on) { const unsigned long long dd = __builtin_amdgcn_s_memtime() - pf_d0; pf_epi += dd; pf_dg += dd; }
+#endif
+          }
+        }
       }
       // the next chunk's patch lives in the other buffer
       const int d = (G & 1) ? -PBUF : PBUF;
@@ -475,105 +683,81 @@ __global__ __launch_bounds__(64 * (WGM * WGN + NP)) void conv3x3_ws_kernel(Igemm
       for (int r = 0; r < RB; ++r)
 #pragma unroll
         for (int kx = 0; kx < 3; ++kx) baddr[r][kx] += d;
-    }
+    };
+    chunk(std::true_type{});
+    ++G;
+#pragma unroll 1
+    for (int c = 1; c < nchunks; ++c, ++G) chunk(std::false_type{});
     if constexpr (DBUF) mma_set(1);                      // the last step's second k-half
+  };
+  for (int k = 0; k < my_items; ++k) {
+    int mt = 0, pt = 0;
+    const int item = item_of(k, mt, pt);
+    int prob, li, txs, tys, nmt;
+    locate(item, prob, li, txs, tys, nmt);
+    if constexpr (GROUPED) { mt = li % nmt; pt = li / nmt; }
+    const int tx = pt % txs, rr = pt / txs;
+    const int ty = rr % tys, n = rr / tys;
+    const int x0 = tx * 32, y0 = ty * TH, m0 = mt * BM;
+    {
+      int Cout = P.Cout;
+      if constexpr (GROUPED) Cout = GP.p[prob].Cout;
+      const int left = (Cout - m0) / 32 - wm * WM;       // Cout % 32 == 0, m0 < Cout
+      nv = __builtin_amdgcn_readfirstlane(left < 0 ? 0 : (left > WM ? WM : left));
+    }
+#pragma unroll
+    for (int i = 0; i < WM; ++i)
+#pragma unroll
+      for (int j = 0; j < WN; ++j)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+
+    // the steps of the item, in the form compiled for this wave's count of valid slices
+    if constexpr (SKIP) {
+      if (nv == WM) run_chunks(std::integral_constant<int, WM>{}, k);
+      else if (WM == 2 && nv == 1) run_chunks(std::integral_constant<int, 1>{}, k);
+      else run_chunks(std::integral_constant<int, 0>{}, k);
+    } else {
+      run_chunks(std::integral_constant<int, WM>{}, k);
+    }
     __builtin_amdgcn_sched_barrier(0);
 #ifdef FAR3D_PROFILING
     unsigned long long pf_e0 = 0;
     if (pf_on) {
       pf_e0 = __builtin_amdgcn_s_memtime();
-      if (pf_tb) { pf_wait += pf_tb - pf_ta; pf_body += pf_e0 - pf_tb; pf_tb = 0; }
+      if (pf_tb) { pf_wait += pf_tb - pf_ta; pf_body += pf_e0 - pf_tb - pf_dg; pf_dg = 0; pf_tb = 0; }
     }
 #endif
 
-    // ---- epilogue in registers: lane (l31, hi) holds, per 32 x 32 tile and quad q, channels 8q + 4hi .. + 3 of pixel (row, l31).
-    // v_permlane32_swap hands the upper half-wave's quad q to the lower lanes and the lower's quad q + 1 to the upper ones: every lane
-    // then owns 8 consecutive channels = one 16-byte store per plane and quad pair.
-    {
-      const int px = x0 + l31;
-      void* y = P.y;
-      const float* bias = P.bias;
-      long yis = P.y_img_stride;
-      int Ho = P.Ho, Wo = P.Wo, ldy = P.ldy, Cout = P.Cout, act = P.act;
-      [[maybe_unused]] float* y2 = nullptr;
-      [[maybe_unused]] const float *y2s = nullptr, *y2h = nullptr;
-      [[maybe_unused]] long y2is = 0;
-      [[maybe_unused]] int ldy2 = 0;
-      if constexpr (GROUPED) {
-        const WsProblem& pq = GP.p[prob];
-        y = pq.y; bias = pq.bias; yis = pq.y_img_stride; Ho = pq.H; Wo = pq.W; ldy = pq.ldy; Cout = pq.Cout; act = pq.act;
-        y2 = pq.y2; y2s = pq.y2_scale; y2h = pq.y2_shift; y2is = pq.y2_img_stride; ldy2 = pq.ldy2;
-      }
-      unsigned char* yb = reinterpret_cast<unsigned char*>(y);
+    if (defer_on && k + 1 < my_items) {
+      // the epilogue of this item rides in the first chunk of the next one; its first operation, accumulator + bias, is done here, so
+      // that no bias value has to live through the steps
 #pragma unroll
-      for (int j = 0; j < WN; ++j) {
-        const int py = y0 + wn * WN + j;
-        const bool ok = py < Ho && px < Wo;
-        const long pix_b = ((long)n * yis + ((long)py * Wo + px) * ldy) * 2;      // bytes
+      for (int i = 0; i < WM; ++i) {
+        float4 b4[2][2];
+        epi_bias(i, 0, m0, prob, b4[0]);
+        epi_bias(i, 1, m0, prob, b4[1]);
 #pragma unroll
-        for (int i = 0; i < WM; ++i) {
-          const int cb = m0 + (wm * WM + i) * 32;        // first channel of this 32-channel block
-          if (cb >= Cout) continue;                      // wave-uniform (Cout % 32 == 0)
+        for (int j = 0; j < WN; ++j)
 #pragma unroll
-          for (int qp = 0; qp < 2; ++qp) {               // quad pairs (0,1) and (2,3)
-            uint2 h[2], l[2];
-#pragma unroll
-            for (int u = 0; u < 2; ++u) {
-              const int q = 2 * qp + u;
-              float4 b4 = make_float4(0.f, 0.f, 0.f, 0.f);
-              if (bias) b4 = *reinterpret_cast<const float4*>(bias + cb + 8 * q + 4 * hi);
-              float v[4];
-#pragma unroll
-              for (int e = 0; e < 4; ++e) v[e] = acc[i][j][4 * q + e];
-              v[0] += b4.x; v[1] += b4.y; v[2] += b4.z; v[3] += b4.w;
-              if (act == ACT_RELU) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
-              } else if (act == ACT_SWISH) {
-                if constexpr (PAIR) {
-#pragma unroll
-                  for (int e = 0; e < 4; ++e) v[e] = v[e] * (1.f / (1.f + expf(-v[e])));
-                } else {
-#pragma unroll
-                  for (int e = 0; e < 4; ++e) v[e] = v[e] * __frcp_rn(1.f + __expf(-v[e]));
-                }
-              }
-              if constexpr (GROUPED) {
-                if (y2 && ok) {                          // fp32 second output of this lane's 4 channels: one 16-byte store
-                  const int m = cb + 8 * q + 4 * hi;
-                  const long so = (long)n * Cout + m;
-                  float w4[4];
-#pragma unroll
-                  for (int e = 0; e < 4; ++e) w4[e] = y2s[so + e] * v[e] + y2h[so + e];
-                  *reinterpret_cast<float4*>(y2 + n * y2is + ((long)py * Wo + px) * ldy2 + m) = make_float4(w4[0], w4[1], w4[2], w4[3]);
-                }
-              }
-              if constexpr (PAIR) split4f(v[0], v[1], v[2], v[3], h[u], l[u]);
-              else { h[u] = make_uint2(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3])); l[u] = make_uint2(0u, 0u); }
-            }
-            // lower lanes: [own quad 2qp | upper's quad 2qp]; upper lanes: [lower's quad 2qp+1 | own quad 2qp+1]
-            u32x4_t oh, ol;
-            {
-              const auto sx = __builtin_amdgcn_permlane32_swap(h[0].x, h[1].x, false, false);
-              const auto sy = __builtin_amdgcn_permlane32_swap(h[0].y, h[1].y, false, false);
-              oh = u32x4_t{sx[0], sy[0], sx[1], sy[1]};
-            }
-            const int qoff = (2 * qp + hi) * 16;           // byte offset of the lane's 8 channels inside a 64-byte plane row
-            if constexpr (PAIR) {
-              const auto sx = __builtin_amdgcn_permlane32_swap(l[0].x, l[1].x, false, false);
-              const auto sy = __builtin_amdgcn_permlane32_swap(l[0].y, l[1].y, false, false);
-              ol = u32x4_t{sx[0], sy[0], sx[1], sy[1]};
-              if (ok) {
-                unsigned char* d = yb + pix_b + (long)(cb >> 5) * 128 + qoff;
-                *reinterpret_cast<u32x4_t*>(d) = oh;
-                *reinterpret_cast<u32x4_t*>(d + 64) = ol;
-              }
-            } else {
-              if (ok) *reinterpret_cast<u32x4_t*>(yb + pix_b + (long)cb * 2 + qoff) = oh;
-            }
+          for (int q = 0; q < 4; ++q) {
+            const float4 bq = b4[q >> 1][q & 1];
+            pacc[i][j][4 * q + 0] = acc[i][j][4 * q + 0] + bq.x; pacc[i][j][4 * q + 1] = acc[i][j][4 * q + 1] + bq.y;
+            pacc[i][j][4 * q + 2] = acc[i][j][4 * q + 2] + bq.z; pacc[i][j][4 * q + 3] = acc[i][j][4 * q + 3] + bq.w;
           }
-        }
       }
+      pd_n = n; pd_y0 = y0; pd_x0 = x0; pd_m0 = m0; pd_prob = prob;
+    } else {
+#pragma unroll
+      for (int j = 0; j < WN; ++j)
+#pragma unroll
+        for (int i = 0; i < WM; ++i)
+#pragma unroll
+          for (int qp = 0; qp < 2; ++qp) {
+            float4 b4[2];
+            epi_bias(i, qp, m0, prob, b4);
+            epi_slice(std::false_type{}, acc, i, j, qp, n, y0, x0, m0, prob, &b4);
+          }
     }
 #ifdef FAR3D_PROFILING
     if (pf_on) pf_epi += __builtin_amdgcn_s_memtime() - pf_e0;
@@ -1046,7 +1230,10 @@ static int launch_gemm1x1_ws(const IgemmParams& P, hipStream_t st) {
   return 0;
 }
 
-template <int WGM, int WGN, int WM, int WN, int NP, bool PAIR, bool DBUF, int NSW = 3, bool FLAGS = false, int GRP = 1>
+// DEFER (the deferred epilogue) is chosen per tile in conv_ws.hip: only consumers of at most 32 accumulators per lane can hold a second
+// set inside the 168 registers that 12 waves per CU leave a lane, and of those only the tiles whose compiler resource report shows no
+// scratch got it (the WM = 2 tiles with a deep ring or a wide consumer row spill a few registers around the item loop and stay as they were).
+template <int WGM, int WGN, int WM, int WN, int NP, bool PAIR, bool DBUF, int NSW = 3, bool FLAGS = false, int GRP = 1, bool DEFER = false>
 static int launch_conv3x3_ws(const IgemmParams& P, hipStream_t st) {
   constexpr int BM = 32 * WGM * WM, TH = WGN * WN, PLD = PAIR ? 2 : 1;
   constexpr int PG = (34 * (TH + 2) + 15) / 16;
@@ -1066,8 +1253,8 @@ static int launch_conv3x3_ws(const IgemmParams& P, hipStream_t st) {
   const int grid = n_items < cus * wg_per_cu ? n_items : cus * wg_per_cu;
   static std::atomic<unsigned long long> lds_ok{0};
   if constexpr (lds > 65536)
-    if (const int rc = far3d_allow_lds(reinterpret_cast<const void*>(&conv3x3_ws_kernel<WGM, WGN, WM, WN, NP, PAIR, DBUF, NSW, FLAGS, GRP>), (int)lds, lds_ok, "far3d_conv2d_nhwc")) return rc;
-  hipLaunchKernelGGL((conv3x3_ws_kernel<WGM, WGN, WM, WN, NP, PAIR, DBUF, NSW, FLAGS, GRP>), dim3((unsigned)grid), dim3(64 * (WGM * WGN + NP)), lds, st, P, tiles_x, tiles_y, n_mt,
+    if (const int rc = far3d_allow_lds(reinterpret_cast<const void*>(&conv3x3_ws_kernel<WGM, WGN, WM, WN, NP, PAIR, DBUF, NSW, FLAGS, GRP, WsSingle, DEFER>), (int)lds, lds_ok, "far3d_conv2d_nhwc")) return rc;
+  hipLaunchKernelGGL((conv3x3_ws_kernel<WGM, WGN, WM, WN, NP, PAIR, DBUF, NSW, FLAGS, GRP, WsSingle, DEFER>), dim3((unsigned)grid), dim3(64 * (WGM * WGN + NP)), lds, st, P, tiles_x, tiles_y, n_mt,
                      n_items, FAR3D_WS_ABLATE_ARG, WsSingle{});
   return 0;
 }
@@ -1075,7 +1262,7 @@ static int launch_conv3x3_ws(const IgemmParams& P, hipStream_t st) {
 // Grouped launch of the same workgroup shape: G holds the problems (sizes, pointers); this orders them largest first, fills in their tile
 // grids and item ranges, and launches min(items, resident workgroups) persistent workgroups over the concatenated item list.  P carries
 // what the problems share (cin_pad).
-template <int WGM, int WGN, int WM, int WN, int NP, bool PAIR, bool DBUF, int NSW = 3, bool FLAGS = false, int GRP = 1>
+template <int WGM, int WGN, int WM, int WN, int NP, bool PAIR, bool DBUF, int NSW = 3, bool FLAGS = false, int GRP = 1, bool DEFER = false>
 static int launch_conv3x3_ws_grouped(const IgemmParams& P, const WsGroup& G0, hipStream_t st) {
   constexpr int BM = 32 * WGM * WM, TH = WGN * WN, PLD = PAIR ? 2 : 1;
   constexpr int PG = (34 * (TH + 2) + 15) / 16;
@@ -1108,9 +1295,9 @@ static int launch_conv3x3_ws_grouped(const IgemmParams& P, const WsGroup& G0, hi
   const int grid = n_items < cus * wg_per_cu ? (int)n_items : cus * wg_per_cu;
   static std::atomic<unsigned long long> lds_ok{0};
   if constexpr (lds > 65536)
-    if (const int rc = far3d_allow_lds(reinterpret_cast<const void*>(&conv3x3_ws_kernel<WGM, WGN, WM, WN, NP, PAIR, DBUF, NSW, FLAGS, GRP, WsGroup>), (int)lds, lds_ok,
+    if (const int rc = far3d_allow_lds(reinterpret_cast<const void*>(&conv3x3_ws_kernel<WGM, WGN, WM, WN, NP, PAIR, DBUF, NSW, FLAGS, GRP, WsGroup, DEFER>), (int)lds, lds_ok,
                                        "far3d_conv2d_nhwc_grouped")) return rc;
-  hipLaunchKernelGGL((conv3x3_ws_kernel<WGM, WGN, WM, WN, NP, PAIR, DBUF, NSW, FLAGS, GRP, WsGroup>), dim3((unsigned)grid), dim3(64 * (WGM * WGN + NP)), lds, st, P,
+  hipLaunchKernelGGL((conv3x3_ws_kernel<WGM, WGN, WM, WN, NP, PAIR, DBUF, NSW, FLAGS, GRP, WsGroup, DEFER>), dim3((unsigned)grid), dim3(64 * (WGM * WGN + NP)), lds, st, P,
                      G.p[0].tiles_x, G.p[0].tiles_y, G.p[0].n_mt, (int)n_items, FAR3D_WS_ABLATE_ARG, G);
   return 0;
 }

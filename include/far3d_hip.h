@@ -211,6 +211,13 @@ typedef struct {
  * FAR3D_WS_GROUP_MAX problems, unaligned rows or an unknown tile are errors; nothing is launched then. */
 int far3d_conv2d_nhwc_grouped(const far3d_conv_problem* probs, int n, int tile, void* stream);
 
+/* How a single-problem launch of the persistent 3x3 kernel deals its items to its workgroups (host arithmetic, no device needed; the
+ * kernel evaluates the same inline function).  A launch has n_full full items and n_light light ones (the items of a partly empty last
+ * channel tile, costed at half a full item).  Returns the k-th item of workgroup wg of grid: 0 .. n_full - 1 = that full item,
+ * n_full .. n_full + n_light - 1 = a light item, -1 = the workgroup has fewer than k + 1 items.  Bad arguments (grid < 1, wg outside
+ * the grid, negative counts) also return -1. */
+int far3d_ws_deal(int n_full, int n_light, int grid, int wg, int k);
+
 /* Multi-head self-attention core: out = softmax(q k^T * scale) v per head (flash-style, no score tensor in HBM).
  * Replaces the bmm/softmax/bmm inside torch.nn.MultiheadAttention as wrapped by mmcv's MultiheadAttention
  *   (ref cfg projects/configs/far3d.py:112-116; call site models/utils/detr3d_transformer.py:385-394; in-tree
