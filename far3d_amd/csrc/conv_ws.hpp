@@ -1192,14 +1192,8 @@ __global__ __launch_bounds__(64 * (WGM * WGN + NP)) void gemm1x1_ws_kernel(Igemm
 #endif
 }
 
-template <int WGM, int WGN, int WM, int WN, int NP, int NSW, int GRP>
-static int launch_gemm1x1_ws(const IgemmParams& P, hipStream_t st) {
-  constexpr int BM = 32 * WGM * WM, BP = 32 * WGN * WN;
-  constexpr size_t lds = (size_t)NSW * 2 * (BM + BP) * 64 + 4 * BM * 8;      // ring + lsum[2][2][BM]
-  static_assert(lds <= 163840, "LDS budget");
-  const long Npix = (long)P.N * P.Ho * P.Wo;
-  const int npt = (int)((Npix + BP - 1) / BP), nct = (P.Cout + BM - 1) / BM;
-  static std::atomic<unsigned long long> lds_ok_s{0};
+// Compute units of the current device (asked once; 256 if the runtime will not say)
+static int ws_cu_count() {
   static std::atomic<int> n_cu{0};
   int cus = n_cu.load(std::memory_order_relaxed);
   if (cus == 0) {
@@ -1208,9 +1202,30 @@ static int launch_gemm1x1_ws(const IgemmParams& P, hipStream_t st) {
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
     n_cu.store(cus, std::memory_order_relaxed);
   }
-  constexpr int wg_per_cu = lds <= 81920 && 64 * (WGM * WGN + NP) <= 1024 ? 2 : 1;
+  return cus;
+}
+// Persistent workgroups resident per CU: two where LDS and threads leave room for a second one
+constexpr int ws_wg_per_cu(size_t lds, int threads) { return lds <= 81920 && threads <= 1024 ? 2 : 1; }
+
+template <int WGM, int WGN, int WM, int WN, int NP, int NSW, int GRP>
+struct Gemm1x1WsShape {
+  static constexpr int BM = 32 * WGM * WM, BP = 32 * WGN * WN, THREADS = 64 * (WGM * WGN + NP);
+  static constexpr size_t lds = (size_t)NSW * 2 * (BM + BP) * 64 + 4 * BM * 8;      // ring + lsum[2][2][BM]
+  static constexpr int wg_per_cu = ws_wg_per_cu(lds, THREADS);
+  static constexpr int caps = tile_caps(FAR3D_TILE_1X1, FAR3D_TILE_PAIR, BP, FAR3D_TILE_LDS_DMA | FAR3D_TILE_PERSISTENT | FAR3D_TILE_SUMS);
+};
+
+template <int WGM, int WGN, int WM, int WN, int NP, int NSW, int GRP>
+static int launch_gemm1x1_ws(const IgemmParams& P, hipStream_t st) {
+  using S = Gemm1x1WsShape<WGM, WGN, WM, WN, NP, NSW, GRP>;
+  constexpr int BM = S::BM, BP = S::BP;
+  constexpr size_t lds = S::lds;
+  static_assert(lds <= 163840, "LDS budget");
+  const long Npix = (long)P.N * P.Ho * P.Wo;
+  const int npt = (int)((Npix + BP - 1) / BP), nct = (P.Cout + BM - 1) / BM;
+  static std::atomic<unsigned long long> lds_ok_s{0};
   const long items = (long)((npt + 7) / 8 * 8) * nct;
-  long grid = (long)cus * wg_per_cu;
+  long grid = (long)ws_cu_count() * S::wg_per_cu;
   grid = (grid + 7) / 8 * 8;
   if (items < grid) grid = items;                       // items is a multiple of 8
   static std::atomic<unsigned long long> lds_ok{0};
@@ -1223,56 +1238,58 @@ static int launch_gemm1x1_ws(const IgemmParams& P, hipStream_t st) {
       far3d_set_error("far3d_conv2d_nhwc: channel sums on this wave-specialised GEMM tile need Ho*Wo (%d) >= %d pixels and Cin >= %d", P.sums_hw, BP, 64 * GRP);
       return FAR3D_ERR_ARG;
     }
-    hipLaunchKernelGGL((gemm1x1_ws_kernel<WGM, WGN, WM, WN, NP, NSW, GRP, true>), dim3((unsigned)grid), dim3(64 * (WGM * WGN + NP)), lds, st, P, npt, nct, FAR3D_WS_ABLATE_ARG);
+    hipLaunchKernelGGL((gemm1x1_ws_kernel<WGM, WGN, WM, WN, NP, NSW, GRP, true>), dim3((unsigned)grid), dim3(S::THREADS), lds, st, P, npt, nct, FAR3D_WS_ABLATE_ARG);
   } else {
-    hipLaunchKernelGGL((gemm1x1_ws_kernel<WGM, WGN, WM, WN, NP, NSW, GRP, false>), dim3((unsigned)grid), dim3(64 * (WGM * WGN + NP)), lds, st, P, npt, nct, FAR3D_WS_ABLATE_ARG);
+    hipLaunchKernelGGL((gemm1x1_ws_kernel<WGM, WGN, WM, WN, NP, NSW, GRP, false>), dim3((unsigned)grid), dim3(S::THREADS), lds, st, P, npt, nct, FAR3D_WS_ABLATE_ARG);
   }
   return 0;
 }
 
-// DEFER (the deferred epilogue) is chosen per tile in conv_ws.hip: only consumers of at most 32 accumulators per lane can hold a second
+// DEFER (the deferred epilogue) is chosen per tile in conv_tiles.hpp: only consumers of at most 32 accumulators per lane can hold a second
 // set inside the 168 registers that 12 waves per CU leave a lane, and of those only the tiles whose compiler resource report shows no
 // scratch got it (the WM = 2 tiles with a deep ring or a wide consumer row spill a few registers around the item loop and stay as they were).
 template <int WGM, int WGN, int WM, int WN, int NP, bool PAIR, bool DBUF, int NSW = 3, bool FLAGS = false, int GRP = 1, bool DEFER = false>
-static int launch_conv3x3_ws(const IgemmParams& P, hipStream_t st) {
-  constexpr int BM = 32 * WGM * WM, TH = WGN * WN, PLD = PAIR ? 2 : 1;
-  constexpr int PG = (34 * (TH + 2) + 15) / 16;
-  constexpr size_t lds = (size_t)NSW * PLD * BM * 64 + (size_t)2 * PLD * PG * 1024 + (FLAGS ? 128 : 0);
-  static_assert(lds <= 163840, "LDS budget");
-  const int tiles_x = (P.Wo + 31) / 32, tiles_y = (P.Ho + TH - 1) / TH, n_mt = (P.Cout + BM - 1) / BM;
-  const int n_items = P.N * tiles_x * tiles_y * n_mt;
-  static std::atomic<int> n_cu{0};
-  int cus = n_cu.load(std::memory_order_relaxed);
-  if (cus == 0) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-    n_cu.store(cus, std::memory_order_relaxed);
-  }
-  constexpr int wg_per_cu = lds <= 81920 && 64 * (WGM * WGN + NP) <= 1024 ? 2 : 1;
-  const int grid = n_items < cus * wg_per_cu ? n_items : cus * wg_per_cu;
+struct Conv3x3WsShape {
+  static constexpr int BM = 32 * WGM * WM, TH = WGN * WN, PLD = PAIR ? 2 : 1, THREADS = 64 * (WGM * WGN + NP);
+  static constexpr int PG = (34 * (TH + 2) + 15) / 16;
+  static constexpr size_t lds = (size_t)NSW * PLD * BM * 64 + (size_t)2 * PLD * PG * 1024 + (FLAGS ? 128 : 0);
+  static constexpr int wg_per_cu = ws_wg_per_cu(lds, THREADS);
+  static constexpr int caps = tile_caps(FAR3D_TILE_3X3, PAIR ? FAR3D_TILE_PAIR : FAR3D_TILE_BF16, 32 * TH, FAR3D_TILE_LDS_DMA | FAR3D_TILE_PERSISTENT);
+};
+
+// min(items, resident workgroups) persistent workgroups of the tile's kernel over n_items items; G: WsSingle{} (one problem, its tile grid
+// in tiles_x / tiles_y / n_mt) or the WsGroup of a grouped launch.  DEFER_OK = false keeps the epilogue in place whatever the row says.
+template <bool DEFER_OK, int WGM, int WGN, int WM, int WN, int NP, bool PAIR, bool DBUF, int NSW = 3, bool FLAGS = false, int GRP = 1, bool DEFER = false, class GT>
+static int launch_conv3x3_ws_items(const IgemmParams& P, hipStream_t st, int tiles_x, int tiles_y, int n_mt, int n_items, const GT& G, const char* who) {
+  using S = Conv3x3WsShape<WGM, WGN, WM, WN, NP, PAIR, DBUF, NSW, FLAGS, GRP, DEFER>;
+  static_assert(S::lds <= 163840, "LDS budget");
+  const int resident = ws_cu_count() * S::wg_per_cu;
+  const int grid = n_items < resident ? n_items : resident;
   static std::atomic<unsigned long long> lds_ok{0};
-  if constexpr (lds > 65536)
-    if (const int rc = far3d_allow_lds(reinterpret_cast<const void*>(&conv3x3_ws_kernel<WGM, WGN, WM, WN, NP, PAIR, DBUF, NSW, FLAGS, GRP, WsSingle, DEFER>), (int)lds, lds_ok, "far3d_conv2d_nhwc")) return rc;
-  hipLaunchKernelGGL((conv3x3_ws_kernel<WGM, WGN, WM, WN, NP, PAIR, DBUF, NSW, FLAGS, GRP, WsSingle, DEFER>), dim3((unsigned)grid), dim3(64 * (WGM * WGN + NP)), lds, st, P, tiles_x, tiles_y, n_mt,
-                     n_items, FAR3D_WS_ABLATE_ARG, WsSingle{});
+  if constexpr (S::lds > 65536)
+    if (const int rc = far3d_allow_lds(reinterpret_cast<const void*>(&conv3x3_ws_kernel<WGM, WGN, WM, WN, NP, PAIR, DBUF, NSW, FLAGS, GRP, GT, DEFER && DEFER_OK>), (int)S::lds, lds_ok, who)) return rc;
+  hipLaunchKernelGGL((conv3x3_ws_kernel<WGM, WGN, WM, WN, NP, PAIR, DBUF, NSW, FLAGS, GRP, GT, DEFER && DEFER_OK>), dim3((unsigned)grid), dim3(S::THREADS), S::lds, st, P, tiles_x, tiles_y,
+                     n_mt, n_items, FAR3D_WS_ABLATE_ARG, G);
   return 0;
 }
 
+template <int WGM, int WGN, int WM, int WN, int NP, bool PAIR, bool DBUF, auto... MORE>
+static int launch_conv3x3_ws(const IgemmParams& P, hipStream_t st) {
+  using S = Conv3x3WsShape<WGM, WGN, WM, WN, NP, PAIR, DBUF, MORE...>;
+  const int tiles_x = (P.Wo + 31) / 32, tiles_y = (P.Ho + S::TH - 1) / S::TH, n_mt = (P.Cout + S::BM - 1) / S::BM;
+  return launch_conv3x3_ws_items<true, WGM, WGN, WM, WN, NP, PAIR, DBUF, MORE...>(P, st, tiles_x, tiles_y, n_mt, P.N * tiles_x * tiles_y * n_mt, WsSingle{}, "far3d_conv2d_nhwc");
+}
+
 // Grouped launch of the same workgroup shape: G holds the problems (sizes, pointers); this orders them largest first, fills in their tile
-// grids and item ranges, and launches min(items, resident workgroups) persistent workgroups over the concatenated item list.  P carries
-// what the problems share (cin_pad).
-template <int WGM, int WGN, int WM, int WN, int NP, bool PAIR, bool DBUF, int NSW = 3, bool FLAGS = false, int GRP = 1, bool DEFER = false>
+// grids and item ranges, and launches over the concatenated item list.  P carries what the problems share (cin_pad).
+template <bool DEFER_OK, int WGM, int WGN, int WM, int WN, int NP, bool PAIR, bool DBUF, auto... MORE>
 static int launch_conv3x3_ws_grouped(const IgemmParams& P, const WsGroup& G0, hipStream_t st) {
-  constexpr int BM = 32 * WGM * WM, TH = WGN * WN, PLD = PAIR ? 2 : 1;
-  constexpr int PG = (34 * (TH + 2) + 15) / 16;
-  constexpr size_t lds = (size_t)NSW * PLD * BM * 64 + (size_t)2 * PLD * PG * 1024 + (FLAGS ? 128 : 0);
-  static_assert(lds <= 163840, "LDS budget");
+  using S = Conv3x3WsShape<WGM, WGN, WM, WN, NP, PAIR, DBUF, MORE...>;
   WsGroup G = G0;
   long items[FAR3D_WS_GROUP_MAX];
   for (int i = 0; i < G.n; ++i) {
     WsProblem& q = G.p[i];
-    q.tiles_x = (q.W + 31) / 32; q.tiles_y = (q.H + TH - 1) / TH; q.n_mt = (q.Cout + BM - 1) / BM;
+    q.tiles_x = (q.W + 31) / 32; q.tiles_y = (q.H + S::TH - 1) / S::TH; q.n_mt = (q.Cout + S::BM - 1) / S::BM;
     items[i] = (long)q.N * q.tiles_x * q.tiles_y * q.n_mt;
   }
   for (int i = 1; i < G.n; ++i)                        // largest problem first (stable insertion sort of at most 16 entries)
@@ -1283,21 +1300,5 @@ static int launch_conv3x3_ws_grouped(const IgemmParams& P, const WsGroup& G0, hi
   long n_items = 0;
   for (int i = 0; i < G.n; ++i) { G.p[i].item0 = (int)n_items; n_items += items[i]; }
   if (n_items >= (1L << 31) - 4096) { far3d_set_error("far3d_conv2d_nhwc_grouped: %ld items", n_items); return FAR3D_ERR_ARG; }
-  static std::atomic<int> n_cu{0};
-  int cus = n_cu.load(std::memory_order_relaxed);
-  if (cus == 0) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-    n_cu.store(cus, std::memory_order_relaxed);
-  }
-  constexpr int wg_per_cu = lds <= 81920 && 64 * (WGM * WGN + NP) <= 1024 ? 2 : 1;
-  const int grid = n_items < cus * wg_per_cu ? (int)n_items : cus * wg_per_cu;
-  static std::atomic<unsigned long long> lds_ok{0};
-  if constexpr (lds > 65536)
-    if (const int rc = far3d_allow_lds(reinterpret_cast<const void*>(&conv3x3_ws_kernel<WGM, WGN, WM, WN, NP, PAIR, DBUF, NSW, FLAGS, GRP, WsGroup, DEFER>), (int)lds, lds_ok,
-                                       "far3d_conv2d_nhwc_grouped")) return rc;
-  hipLaunchKernelGGL((conv3x3_ws_kernel<WGM, WGN, WM, WN, NP, PAIR, DBUF, NSW, FLAGS, GRP, WsGroup, DEFER>), dim3((unsigned)grid), dim3(64 * (WGM * WGN + NP)), lds, st, P,
-                     G.p[0].tiles_x, G.p[0].tiles_y, G.p[0].n_mt, (int)n_items, FAR3D_WS_ABLATE_ARG, G);
-  return 0;
+  return launch_conv3x3_ws_items<DEFER_OK, WGM, WGN, WM, WN, NP, PAIR, DBUF, MORE...>(P, st, G.p[0].tiles_x, G.p[0].tiles_y, G.p[0].n_mt, (int)n_items, G, "far3d_conv2d_nhwc_grouped");
 }

@@ -16,6 +16,8 @@
 // one barrier per K step.
 #pragma once
 #include "common.hpp"
+#include "conv_tiles.hpp"
+#include "far3d_hip.h"   // FAR3D_TILE_*
 #include <stdlib.h>
 
 typedef __attribute__((__vector_size__(8 * sizeof(__bf16)))) __bf16 bf16x8_t;
@@ -70,6 +72,29 @@ struct IgemmParams {
   unsigned long long* prof;   // tools/conv_phase_times.py: 8 x 64-bit stamps per workgroup (never in libfar3d_hip.so)
 #endif
 };
+
+// What far3d_conv_tile_caps says about a tile (include/far3d_hip.h, FAR3D_TILE_*).  Every launcher below has a ...Shape struct of the
+// same template arguments that holds the launcher's compile-time constants and its `caps`, so the two cannot disagree.
+constexpr int tile_caps(int geom, int store, int pixels, int flags = 0) { return geom | store << 2 | flags | pixels << 16; }
+
+// Does the layer have the geometry the tile takes?
+static inline bool tile_geom_fits(int caps, const IgemmParams& P) {
+  const bool k3 = P.KH == 3 && P.KW == 3 && P.pad == 1;
+  switch (caps & FAR3D_TILE_GEOM) {
+    case FAR3D_TILE_1X1: return P.KH == 1 && P.KW == 1 && P.stride == 1 && P.pad == 0;
+    case FAR3D_TILE_3X3: return k3 && P.stride == 1 && P.Ho == P.H && P.Wo == P.W;
+    case FAR3D_TILE_3X3S2: return k3 && P.stride == 2 && P.Ho == (P.H - 1) / 2 + 1 && P.Wo == (P.W - 1) / 2 + 1;
+    default: return true;
+  }
+}
+
+// tile 0 on the register-staged / ring kernels (1 128x128, 2 64x128, 3 64x64, 4 128x64 channels x pixels): the fallback heuristic;
+// far3d_amd/data/tuning_mi355x.json holds measured per-shape winners
+static inline int igemm_auto_tile(long Npix, int Cout) {
+  if (Cout <= 64) return (Npix >= 128 * 512) ? 2 : 3;
+  if (((Npix + 127) / 128) * ((Cout + 127) / 128) >= 512) return 1;
+  return (((Npix + 63) / 64) * ((Cout + 127) / 128) >= 512) ? 4 : 3;
+}
 
 // Profiling build only (-DFAR3D_PROFILING, libfar3d_hip_prof.so): thread 0 of every workgroup records s_memtime at the phase boundaries
 // -- slot 0 hardware id (HW_ID | XCC_ID << 32), 1 kernel entry, 2 set-up done (addresses, descriptors, first DMA issued), 3 first step's
@@ -617,14 +642,33 @@ __global__ __launch_bounds__(256) void igemm_kernel(IgemmParams P) {
   igemm_epilogue<WM, WN>(P, acc, p0, m0, wm, wn, l31, hi, HoWo, Npix);
 }
 
+template <int WGM, int WGN, int WM, int WN>
+struct IgemmShape {      // any storage: far3d_conv_tile_caps adds the one it was asked about
+  static constexpr int BM = 32 * WGM * WM, BP = 32 * WGN * WN;
+  static constexpr int caps = tile_caps(FAR3D_TILE_ANY, 0, BP);
+};
+
 template <typename TIn, typename TC, int WGM, int WGN, int WM, int WN>
 static int launch_igemm(const IgemmParams& P, hipStream_t st) {
-  constexpr int BM = 32 * WGM * WM, BP = 32 * WGN * WN;
+  using S = IgemmShape<WGM, WGN, WM, WN>;
+  constexpr int BM = S::BM, BP = S::BP;
   const long Npix = (long)P.N * P.Ho * P.Wo;
   dim3 grid((unsigned)((Npix + BP - 1) / BP), (unsigned)((P.Cout + BM - 1) / BM));
   const size_t lds = (size_t)2 * (BM + BP) * Cfg<TC>::ROWB;
   hipLaunchKernelGGL((igemm_kernel<TIn, TC, WGM, WGN, WM, WN>), grid, dim3(256), lds, st, P);
   return 0;
+}
+
+// ids 1-5 (conv_tiles.hpp) for one pair of storage types
+template <typename TIn, typename TC>
+static int launch_igemm_tile(const IgemmParams& P, int tile, hipStream_t st) {
+#define TILE_LAUNCH_IGEMM(a, id, ...) case id: return launch_igemm<TIn, TC, __VA_ARGS__>(P, st);
+  switch (tile) {
+    FAR3D_TILES_IGEMM(TILE_LAUNCH_IGEMM, )
+    default: break;
+  }
+  far3d_set_error("far3d_conv2d_nhwc: unknown tile %d", tile);
+  return FAR3D_ERR_ARG;
 }
 
 
@@ -773,8 +817,15 @@ __global__ __launch_bounds__(256) void igemm_dma_kernel(IgemmParams P) {
 }
 
 template <int WGM, int WGN, int WM, int WN, int NS, int KPS = 1>
+struct IgemmDmaShape {
+  static constexpr int BM = 32 * WGM * WM, BP = 32 * WGN * WN;
+  static constexpr int caps = tile_caps(FAR3D_TILE_ANY, FAR3D_TILE_BF16, BP, FAR3D_TILE_LDS_DMA);
+};
+
+template <int WGM, int WGN, int WM, int WN, int NS, int KPS = 1>
 static int launch_igemm_dma(const IgemmParams& P, hipStream_t st) {
-  constexpr int BM = 32 * WGM * WM, BP = 32 * WGN * WN;
+  using S = IgemmDmaShape<WGM, WGN, WM, WN, NS, KPS>;
+  constexpr int BM = S::BM, BP = S::BP;
   const long Npix = (long)P.N * P.Ho * P.Wo;
   dim3 grid((unsigned)((Npix + BP - 1) / BP), (unsigned)((P.Cout + BM - 1) / BM));
   constexpr size_t lds = (size_t)NS * KPS * (BM + BP) * 64;
@@ -1111,8 +1162,16 @@ __global__ __launch_bounds__(64 * WGM * WGN) void conv3x3_pipe_kernel(IgemmParam
 }
 
 template <int WGM, int WGN, int WM, int WN, int NSW = 2, int RPS = 1, int NT = 1, bool PAIR = false, int STRIDE = 1>
+struct Conv3x3PipeShape {
+  static constexpr int BM = 32 * WGM * WM, TH = WGN * WN;
+  static constexpr int caps = tile_caps(STRIDE == 1 ? FAR3D_TILE_3X3 : FAR3D_TILE_3X3S2, PAIR ? FAR3D_TILE_PAIR : FAR3D_TILE_BF16, 32 * TH,
+                                        FAR3D_TILE_LDS_DMA | (PAIR && NT == 1 ? FAR3D_TILE_HI_ONLY : 0));
+};
+
+template <int WGM, int WGN, int WM, int WN, int NSW = 2, int RPS = 1, int NT = 1, bool PAIR = false, int STRIDE = 1>
 static int launch_conv3x3_pipe(const IgemmParams& P, hipStream_t st) {
-  constexpr int BM = 32 * WGM * WM, TH = WGN * WN, PLD = NT == 3 ? 2 : 1;
+  using S = Conv3x3PipeShape<WGM, WGN, WM, WN, NSW, RPS, NT, PAIR, STRIDE>;
+  constexpr int BM = S::BM, TH = S::TH, PLD = NT == 3 ? 2 : 1;
   constexpr int PG = ((STRIDE == 1 ? 34 : 66) * (STRIDE * TH + 3 - STRIDE) + 15) / 16;
   constexpr size_t lds_ring = (size_t)(RPS == 3 ? NSW : 2) * PLD * PG * 1024 + (size_t)NSW * 3 * RPS * PLD * BM * 64;
   constexpr size_t lds_out = (size_t)TH * 32 * (BM * (PAIR ? 4 : 2) + 16);
@@ -1531,38 +1590,41 @@ __global__ __launch_bounds__(64 * WGM * WGN * KS) void gemm1x1_pipe_kernel(Igemm
 }
 
 // far3d_conv2d_nhwc with channel sums: what a GEMM tile needs (a refusal is an error of the call, never a silent fallback)
-template <int BM, int BP, int NTHREADS>
-static bool gemm_sums_ok(const IgemmParams& P, size_t lds_sums) {
-  static_assert(BP / (NTHREADS / 64) <= 64, "32-bit per-wave sums hold 64 pixels of |v| < 2^(24 - FRAC_BITS)");
+// S: the tile's shape (S::sums: what the tile itself allows).  What is left depends on the call.
+template <class S>
+static bool gemm_sums_ok(const IgemmParams& P) {
+  static_assert(S::BP / (S::THREADS / 64) <= 64, "32-bit per-wave sums hold 64 pixels of |v| < 2^(24 - FRAC_BITS)");
+  if (!S::sums) { far3d_set_error("far3d_conv2d_nhwc: this %d x %d tile takes no channel sums (no LDS left for their scratch, channel rows that are no power of two, K groups or fp32 rows)", S::BM, S::BP); return false; }
   if (!P.y_rows16) { far3d_set_error("far3d_conv2d_nhwc: channel sums need the coalesced bf16 / pair output path (16-byte aligned rows, no residual / second output)"); return false; }
-  if (P.sums_hw < BP) { far3d_set_error("far3d_conv2d_nhwc: channel sums need Ho*Wo (%d) >= the tile's %d pixels", P.sums_hw, BP); return false; }
-  if (lds_sums > 163840) { far3d_set_error("far3d_conv2d_nhwc: this tile has no LDS left for the channel-sum scratch"); return false; }
+  if (P.sums_hw < S::BP) { far3d_set_error("far3d_conv2d_nhwc: channel sums need Ho*Wo (%d) >= the tile's %d pixels", P.sums_hw, S::BP); return false; }
   return true;
 }
 
 template <int WGM, int WGN, int WM, int WN, int NT = 1, bool PAIR = false, int NS = 2, bool F32B = false, bool F32X = false, int KS = 1>
+struct Gemm1x1PipeShape {
+  static constexpr int BM = 32 * WGM * WM, BP = 32 * WGN * WN, THREADS = 64 * WGM * WGN;      // THREADS: of one K group
+  static constexpr size_t lds_part = (size_t)(KS - 1) * WGM * WGN * WM * WN * 4096;      // K groups: the partial tiles of groups 1 .. KS-1
+  static constexpr size_t lds_ring = (size_t)KS * NS * 2 * (BM + BP) * 64 > lds_part ? (size_t)KS * NS * 2 * (BM + BP) * 64 : lds_part;
+  static constexpr size_t lds_out = KS > 1 ? 0 : (size_t)BP * (BM * (PAIR ? 4 : 2) + 16);
+  static constexpr size_t lds0 = lds_ring > lds_out ? lds_ring : lds_out, lds_sums = lds0 + 2 * BM * sizeof(long long);
+  static constexpr int CPP = BM * (PAIR ? 4 : 2) / 16;        // 16-byte chunks of a staged output row (epilogue_rows16)
+  // channel sums: LDS left for their scratch, power-of-two channel rows, one K group, a bf16 or pair map (fp32 rows have no sums)
+  static constexpr bool sums = lds_sums <= 163840 && THREADS % CPP == 0 && (CPP & (CPP - 1)) == 0 && CPP <= 64 && KS == 1 && !F32B;
+  static constexpr int caps = tile_caps(FAR3D_TILE_1X1, F32X ? FAR3D_TILE_F32 : F32B ? FAR3D_TILE_F32_SPLIT : PAIR ? FAR3D_TILE_PAIR : FAR3D_TILE_BF16, BP,
+                                        FAR3D_TILE_LDS_DMA | (sums ? FAR3D_TILE_SUMS : 0) | (PAIR && !F32B && NT == 1 ? FAR3D_TILE_HI_ONLY : 0));
+};
+
+template <int WGM, int WGN, int WM, int WN, int NT = 1, bool PAIR = false, int NS = 2, bool F32B = false, bool F32X = false, int KS = 1>
 static int launch_gemm1x1_pipe(const IgemmParams& P, hipStream_t st) {
-  constexpr int BM = 32 * WGM * WM, BP = 32 * WGN * WN;
+  using S = Gemm1x1PipeShape<WGM, WGN, WM, WN, NT, PAIR, NS, F32B, F32X, KS>;
+  constexpr int BM = S::BM, BP = S::BP;
+  constexpr size_t lds0 = S::lds0, lds_sums = S::lds_sums;
   const long Npix = (long)P.N * P.Ho * P.Wo;
   const int npt = (int)((Npix + BP - 1) / BP), nct = (P.Cout + BM - 1) / BM;
-  constexpr size_t lds_part = (size_t)(KS - 1) * WGM * WGN * WM * WN * 4096;      // K groups: the partial tiles of groups 1 .. KS-1
-  constexpr size_t lds_ring = (size_t)KS * NS * 2 * (BM + BP) * 64 > lds_part ? (size_t)KS * NS * 2 * (BM + BP) * 64 : lds_part;
-  constexpr size_t lds_out = KS > 1 ? 0 : (size_t)BP * (BM * (PAIR ? 4 : 2) + 16);
-  static_assert(lds_ring <= 163840, "LDS budget");
+  static_assert(S::lds_ring <= 163840, "LDS budget");
   static_assert(64 * WGM * WGN * KS <= 1024, "workgroup size");
-  constexpr size_t lds0 = lds_ring > lds_out ? lds_ring : lds_out, lds_sums = lds0 + 2 * BM * sizeof(long long);
-  if constexpr (KS > 1) {
-    if (P.chan_sums) { far3d_set_error("far3d_conv2d_nhwc: the K-group tiles of the exact-fp32 GEMM take no channel sums"); return FAR3D_ERR_ARG; }
-  }
   const size_t lds = P.chan_sums ? lds_sums : lds0;
-  if (P.chan_sums && !gemm_sums_ok<BM, BP, 64 * WGM * WGN>(P, lds_sums)) return FAR3D_ERR_ARG;
-  {
-    constexpr int CPP = BM * (PAIR ? 4 : 2) / 16;        // 16-byte chunks of a staged output row (epilogue_rows16)
-    if (P.chan_sums && !((64 * WGM * WGN) % CPP == 0 && (CPP & (CPP - 1)) == 0 && CPP <= 64)) {
-      far3d_set_error("far3d_conv2d_nhwc: this tile's %d-channel rows do not take channel sums (power-of-two channel tiles only)", BM);
-      return FAR3D_ERR_ARG;
-    }
-  }
+  if (P.chan_sums && !gemm_sums_ok<S>(P)) return FAR3D_ERR_ARG;
   static std::atomic<unsigned long long> lds_ok{0};
   if constexpr (lds_sums > 65536)
     if (const int rc = far3d_allow_lds(reinterpret_cast<const void*>(&gemm1x1_pipe_kernel<WGM, WGN, WM, WN, NT, PAIR, NS, F32B, F32X, KS>),
@@ -1759,15 +1821,24 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gemm1x1_wide_kernel(IgemmParam
 }
 
 template <int WGM, int WGN, int WM, int WN, int NS = 2>
+struct Gemm1x1WideShape {
+  static constexpr int BM = 32 * WGM * WM, BP = 32 * WGN * WN, THREADS = 64 * WGM * WGN;
+  static constexpr size_t lds_ring = (size_t)NS * (BM + BP) * 128, lds_out = (size_t)BP * (BM * 2 + 16);
+  static constexpr size_t lds0 = lds_ring > lds_out ? lds_ring : lds_out, lds_sums = lds0 + 2 * BM * sizeof(long long);
+  static constexpr bool sums = lds_sums <= 163840;
+  static constexpr int caps = tile_caps(FAR3D_TILE_1X1, FAR3D_TILE_BF16, BP, FAR3D_TILE_LDS_DMA | (sums ? FAR3D_TILE_SUMS : 0));
+};
+
+template <int WGM, int WGN, int WM, int WN, int NS = 2>
 static int launch_gemm1x1_wide(const IgemmParams& P, hipStream_t st) {
-  constexpr int BM = 32 * WGM * WM, BP = 32 * WGN * WN;
+  using S = Gemm1x1WideShape<WGM, WGN, WM, WN, NS>;
+  constexpr int BM = S::BM, BP = S::BP;
+  constexpr size_t lds0 = S::lds0, lds_sums = S::lds_sums;
   const long Npix = (long)P.N * P.Ho * P.Wo;
   const int npt = (int)((Npix + BP - 1) / BP), nct = (P.Cout + BM - 1) / BM;
-  constexpr size_t lds_ring = (size_t)NS * (BM + BP) * 128, lds_out = (size_t)BP * (BM * 2 + 16);
-  static_assert(lds_ring <= 163840, "LDS budget");
-  constexpr size_t lds0 = lds_ring > lds_out ? lds_ring : lds_out, lds_sums = lds0 + 2 * BM * sizeof(long long);
+  static_assert(S::lds_ring <= 163840, "LDS budget");
   const size_t lds = P.chan_sums ? lds_sums : lds0;
-  if (P.chan_sums && !gemm_sums_ok<BM, BP, 64 * WGM * WGN>(P, lds_sums)) return FAR3D_ERR_ARG;
+  if (P.chan_sums && !gemm_sums_ok<S>(P)) return FAR3D_ERR_ARG;
   static std::atomic<unsigned long long> lds_ok{0};
   if constexpr (lds_sums > 65536)
     if (const int rc = far3d_allow_lds(reinterpret_cast<const void*>(&gemm1x1_wide_kernel<WGM, WGN, WM, WN, NS>),
@@ -1977,16 +2048,24 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gemm1x1_split_kernel(IgemmPara
 }
 
 template <int WGM, int WGN, int WM, int WN, int NSA, int NSB>
+struct Gemm1x1SplitShape {
+  static constexpr int BM = 32 * WGM * WM, BP = 32 * WGN * WN, THREADS = 64 * WGM * WGN;
+  static constexpr size_t lds_ring = (size_t)NSA * BM * 128 + (size_t)NSB * BP * 128, lds_out = (size_t)BP * (BM * 2 + 16);
+  static constexpr size_t lds_out_sums = lds_out + 2 * BM * sizeof(long long);
+  static constexpr size_t lds = lds_ring > lds_out_sums ? lds_ring : lds_out_sums;
+  static constexpr bool sums = lds <= 163840;          // the epilogue's LDS always includes the scratch of the sums
+  static constexpr int caps = tile_caps(FAR3D_TILE_1X1, FAR3D_TILE_BF16, BP, FAR3D_TILE_LDS_DMA | (sums ? FAR3D_TILE_SUMS : 0));
+};
+
+template <int WGM, int WGN, int WM, int WN, int NSA, int NSB>
 static int launch_gemm1x1_split(const IgemmParams& P, hipStream_t st) {
-  constexpr int BM = 32 * WGM * WM, BP = 32 * WGN * WN;
+  using S = Gemm1x1SplitShape<WGM, WGN, WM, WN, NSA, NSB>;
+  constexpr int BM = S::BM, BP = S::BP;
+  constexpr size_t lds = S::lds;
   const long Npix = (long)P.N * P.Ho * P.Wo;
   const int npt = (int)((Npix + BP - 1) / BP), nct = (P.Cout + BM - 1) / BM;
-  constexpr size_t lds_ring = (size_t)NSA * BM * 128 + (size_t)NSB * BP * 128, lds_out = (size_t)BP * (BM * 2 + 16);
-  static_assert(lds_ring <= 163840, "LDS budget");
-  constexpr size_t lds_out_sums = lds_out + 2 * BM * sizeof(long long);
-  static_assert(lds_out_sums <= 163840, "LDS budget (epilogue)");
-  constexpr size_t lds = lds_ring > lds_out_sums ? lds_ring : lds_out_sums;
-  if (P.chan_sums && !gemm_sums_ok<BM, BP, 64 * WGM * WGN>(P, lds)) return FAR3D_ERR_ARG;
+  static_assert(S::lds_ring <= 163840 && S::lds_out_sums <= 163840, "LDS budget (ring, epilogue)");
+  if (P.chan_sums && !gemm_sums_ok<S>(P)) return FAR3D_ERR_ARG;
   static std::atomic<unsigned long long> lds_ok{0};
   if constexpr (lds > 65536)
     if (const int rc = far3d_allow_lds(reinterpret_cast<const void*>(&gemm1x1_split_kernel<WGM, WGN, WM, WN, NSA, NSB>), (int)lds, lds_ok, "far3d_conv2d_nhwc")) return rc;

@@ -5,6 +5,9 @@ events / graphs see the kernels) and never synchronises.
 """
 import contextlib
 import ctypes
+import functools
+import json
+import os
 import threading
 
 import numpy as np
@@ -274,10 +277,53 @@ def use_tile_tables(bf16_table, pair_table=None):
         _TABLE_SEL.cur = prev
 
 
-WS_TILES = set(range(400, 478)) | set(range(500, 560))   # persistent wave-specialised kernels (csrc/conv_ws.hpp; 400-459 3x3, 460-477 1x1 GEMM on pair maps; 479-481 are fp32-row GEMM tiles): bias + activation + pair / bf16 store only; 500-559 grouped 3x3 launches (conv2d_nhwc_grouped)
-GROUP_TILES = range(500, 560)
 GROUP_MAX = 16                  # FAR3D_WS_GROUP_MAX in include/far3d_hip.h
 GROUP_TILE_TABLE = "tuning_mi355x_groups.json"
+
+# far3d_conv_tile_caps (include/far3d_hip.h, FAR3D_TILE_*): what a tile id is.  The table itself is csrc/conv_tiles.hpp.
+TILE_ANY, TILE_1X1, TILE_3X3, TILE_3X3S2 = 0, 1, 2, 3                  # caps & 3: the layer geometry the tile takes
+TILE_HI_ONLY, TILE_PERSISTENT, TILE_HAS_GROUP, TILE_GROUPED, TILE_SUMS, TILE_LDS_DMA = 32, 64, 128, 256, 512, 1024
+_STORAGES = ((DT_BF16, DT_BF16), (DT_BF16_PAIR, DT_F32_BF16X3), (DT_F32, DT_F32_BF16X3), (DT_F32, DT_F32), (DT_F32, DT_BF16))
+
+
+@functools.lru_cache(maxsize=None)
+def tile_caps(tile, x_dt=None, w_dt=None):
+    """The FAR3D_TILE_* mask of a tile id for activations x_dt and weights w_dt, -1 = no such tile for that storage; without a storage,
+    for the first storage that has the tile (an id above 5 belongs to one).  (caps >> 2) & 7 is the storage, caps >> 16 the pixels per
+    tile.  Asks the library, which is loaded at the first query (no device needed)."""
+    if x_dt is None:
+        return next((c for c in (tile_caps(tile, *st) for st in _STORAGES) if c >= 0), -1)
+    return _lib.load().far3d_conv_tile_caps(int(tile), x_dt, w_dt)
+
+
+def is_ws_tile(tile):
+    """A persistent wave-specialised tile (csrc/conv_ws.hpp; bias + activation + store only), grouped ids included."""
+    return tile_caps(tile) >= 0 and bool(tile_caps(tile) & TILE_PERSISTENT)
+
+
+def is_group_tile(tile):
+    """An id of conv2d_nhwc_grouped."""
+    return tile_caps(tile) >= 0 and bool(tile_caps(tile) & TILE_GROUPED)
+
+
+def tile_takes_sums(tile, pair):
+    """Can the tile add the channel sums of its output (conv2d_nhwc(sums=...)) on a bf16 (pair: pair-stored) map?"""
+    c = tile_caps(tile, DT_BF16_PAIR, DT_F32_BF16X3) if pair else tile_caps(tile, DT_BF16, DT_BF16)
+    return c >= 0 and bool(c & TILE_SUMS)
+
+
+def _table(name, groups=False):
+    """far3d_amd/data/<name>, read once (a missing file is an empty table): {key without its pixel count: [(pixel count, entry)]}; the
+    key is the layer's (Cout, Cin, k, stride), or the group's name (groups)."""
+    tab = _TUNING.get(name)
+    if tab is None:
+        path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "data", name)
+        tab = _TUNING[name] = {}
+        for key, tile in (json.load(open(path)) if os.path.exists(path) else {}).items():
+            k, npx = key.rsplit(",", 1)
+            tab.setdefault(k if groups else tuple(int(v) for v in k.split(",")), []).append(
+                (int(npx), tuple(int(t) for t in tile) if isinstance(tile, (list, tuple)) else int(tile)))
+    return tab
 
 
 def _tuned_tile(Cout, Cin, k, stride, npix, table=None, ws_ok=False):
@@ -287,19 +333,7 @@ def _tuned_tile(Cout, Cin, k, stride, npix, table=None, ws_ok=False):
     An entry may be a pair [ws tile, other tile]: the wave-specialised kernel where the call allows it (ws_ok: no residual, second
     output or channel sums, same storage in and out), else the fastest of the general kernels -- an explicit choice per call, the
     library itself never substitutes a kernel."""
-    if table is None:
-        table = tile_tables()[0]
-    tab = _TUNING.get(table)
-    if tab is None:
-        import json
-        import os
-        path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "data", table)
-        raw = json.load(open(path)) if os.path.exists(path) else {}
-        tab = _TUNING[table] = {}
-        for key, tile in raw.items():
-            co, ci, kk, st, npx = (int(v) for v in key.split(","))
-            tab.setdefault((co, ci, kk, st), []).append((npx, tuple(int(t) for t in tile) if isinstance(tile, (list, tuple)) else int(tile)))
-    cands = tab.get((Cout, Cin, k, stride))
+    cands = _table(table or tile_tables()[0]).get((Cout, Cin, k, stride))
     if not cands:
         return 0
     npx, tile = min(cands, key=lambda c: abs(c[0] - npix))
@@ -373,26 +407,45 @@ def _is_pair_input(x, pc):
     return pc.w_code == DT_F32_BF16X3 and x.dtype == torch.bfloat16
 
 
-_HI_ONLY_TILE = {160: 260, 165: 265, 152: 252, 179: 279, 180: 280}
-
-
 def _pair_tile(pc, Cin, npix, tile, ws_ok=False):
     """Tile id for a pair-stored input: the measured split-product tile (far3d_amd/data/tuning_mi355x_pair.json, ids 150+, 0 = the
-    library default), mapped to a hi-planes-only kernel when the layer is assigned a single bf16 product (pc.terms == 1)."""
+    library default), mapped to a hi-planes-only kernel when the layer is assigned a single bf16 product (pc.terms == 1): tile + 100
+    where that is the hi-only form of the tile (conv_tiles.hpp), else the default hi-only tile of the layer's kernel size."""
     fast = pc.stride == 1 and ((pc.KH == 3 and pc.pad == 1) or (pc.KH == 1 and pc.pad == 0))
     if tile == 0:
         tile = _tuned_tile(pc.Cout, Cin, pc.KH, pc.stride, npix, tile_tables()[1], ws_ok=ws_ok and pc.terms != 1)
     if pc.terms == 1 and fast and (tile == 0 or 150 <= tile < 200):
-        tile = _HI_ONLY_TILE.get(tile, 260 if pc.KH == 3 else 279)
+        c, hi = tile_caps(tile, DT_BF16_PAIR, DT_F32_BF16X3), tile_caps(tile + 100, DT_BF16_PAIR, DT_F32_BF16X3)
+        tile = tile + 100 if c >= 0 and hi >= 0 and hi & TILE_HI_ONLY and (hi & 3) == (c & 3) else (260 if pc.KH == 3 else 279)
     return tile
 
 
-def conv_tile(x, pc):
-    """The tile conv2d_nhwc(tile=0) will use for this input (0 = kernel heuristic)."""
-    N, H, W, Cin = x.shape
-    if _is_pair_input(x, pc):
-        return _pair_tile(pc, Cin // 2, N * H * W, 0)
-    return _tuned_tile(pc.Cout, Cin, pc.KH, pc.stride, N * H * W) if x.dtype == torch.bfloat16 else 0
+def _conv_plan(x, pc, out_dtype, res=None, y2=None, sums=None, tile=0, out=None):
+    """What conv2d_nhwc launches for this call: (pair_in, ws_ok, tile).  out_dtype: the dtype of the call's output; out: the output view
+    when there is one (a fresh output is dense and aligned); sums: anything but None = the call asks for channel sums.
+    ws_ok -- what the persistent wave-specialised kernels cover (anything else takes the table's general tile) -- exists only here."""
+    N, H, W, Cx = x.shape
+    pair_in = _is_pair_input(x, pc)
+    Cin = Cx // 2 if pair_in else Cx
+    Ho, Wo = pc.out_hw(H, W)
+    dense = (out is None or (out.stride(2) % 8 == 0 and out.stride(0) % 8 == 0 and out.data_ptr() % 16 == 0)) and \
+        x.stride(2) % 8 == 0 and x.stride(0) % 8 == 0 and x.data_ptr() % 16 == 0
+    ws_ok = (res is None and y2 is None and pc.stride == 1 and
+             ((pc.KH == 3 and pc.KW == 3 and pc.pad == 1 and sums is None) or
+              (pc.KH == 1 and pc.KW == 1 and pc.pad == 0 and pair_in and (sums is None or (Ho * Wo >= 256 and Cin >= 192)))) and
+             Cin % 32 == 0 and pc.Cout % 32 == 0 and out_dtype == torch.bfloat16 and dense)
+    if pair_in:
+        tile = _pair_tile(pc, Cin, N * H * W, tile, ws_ok)
+    elif tile == 0 and x.dtype == torch.bfloat16:
+        tile = _tuned_tile(pc.Cout, Cin, pc.KH, pc.stride, N * H * W, ws_ok=ws_ok)
+    elif tile == 0 and pc.w_code == DT_F32_BF16X3:
+        tile = _tuned_tile(pc.Cout, Cin, pc.KH, pc.stride, N * H * W, "tuning_mi355x_bf16x3.json")
+    return pair_in, ws_ok, tile
+
+
+def conv_tile(x, pc, out_dtype=None, res=None, y2=None, sums=None, out=None):
+    """The tile conv2d_nhwc(x, pc, tile=0, ...) with the same optional arguments will use (0 = kernel heuristic)."""
+    return _conv_plan(x, pc, out.dtype if out is not None else out_dtype or x.dtype, res, y2, sums, 0, out)[2]
 
 
 def conv2d_nhwc(x, pc, out=None, act=None, out_dtype=None, res=None, y2=None, y2_scale=None, y2_shift=None, tile=0, sums=None):
@@ -433,18 +486,7 @@ def conv2d_nhwc(x, pc, out=None, act=None, out_dtype=None, res=None, y2=None, y2
         if y2_scale.numel() != N * pc.Cout or y2_shift.numel() != N * pc.Cout or tuple(y2.shape) != (N, Ho, Wo, pc.Cout):
             raise ValueError("conv2d_nhwc: y2/scale/shift shapes inconsistent")
         y2p, y2dt, sp, hp = _ptr(y2), _dt(y2), _ptr(y2_scale), _ptr(y2_shift)
-    # what the wave-specialised kernels cover (anything else takes the table's general tile)
-    ws_ok = (res is None and y2 is None and pc.stride == 1 and
-             ((pc.KH == 3 and pc.KW == 3 and pc.pad == 1 and sums is None) or
-              (pc.KH == 1 and pc.KW == 1 and pc.pad == 0 and pair_in and (sums is None or (Ho * Wo >= 256 and Cin >= 192)))) and
-             Cin % 32 == 0 and pc.Cout % 32 == 0 and out.dtype == torch.bfloat16 and ldx % 8 == 0 and ldy % 8 == 0 and
-             x.data_ptr() % 16 == 0 and out.data_ptr() % 16 == 0 and xs % 8 == 0 and ys % 8 == 0)
-    if pair_in:
-        tile = _pair_tile(pc, Cin, N * H * W, tile, ws_ok)
-    elif tile == 0 and x.dtype == torch.bfloat16:
-        tile = _tuned_tile(pc.Cout, Cin, pc.KH, pc.stride, N * H * W, ws_ok=ws_ok)
-    elif tile == 0 and pc.w_code == DT_F32_BF16X3:
-        tile = _tuned_tile(pc.Cout, Cin, pc.KH, pc.stride, N * H * W, "tuning_mi355x_bf16x3.json")
+    tile = _conv_plan(x, pc, out.dtype, res, y2, sums, tile, out)[2]
     _lib.check(lib.far3d_conv2d_nhwc(
         _ptr(x), DT_BF16_PAIR if pair_in else _dt(x), _ptr(pc.w), pc.w_code, _ptr(pc.bias) if pc.bias is not None else None, _ptr(out),
         DT_BF16_PAIR if pair_out else _dt(out),
@@ -477,18 +519,7 @@ def group_tile(name, npix, table=None):
     """The grouped tile measured for the named layer group (far3d_amd/data/tuning_mi355x_groups.json, key "<group>,<level-0 pixels>";
     tools/tune_conv.py GROUPS=1), or 0 = the group is launched layer by layer.  Like a persistent single-layer tile, an entry holds only
     near the pixel count it was measured at: the group replaces the per-layer launches only where it was measured to win."""
-    table = table or GROUP_TILE_TABLE
-    tab = _TUNING.get(table)
-    if tab is None:
-        import json
-        import os
-        path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "data", table)
-        raw = json.load(open(path)) if os.path.exists(path) else {}
-        tab = _TUNING[table] = {}
-        for key, tile in raw.items():
-            g, npx = key.rsplit(",", 1)
-            tab.setdefault(g, []).append((int(npx), int(tile)))
-    cands = tab.get(name)
+    cands = _table(table or GROUP_TILE_TABLE, groups=True).get(name)
     if not cands:
         return 0
     npx, tile = min(cands, key=lambda c: abs(c[0] - npix))
@@ -503,7 +534,7 @@ def conv2d_nhwc_grouped(problems, tile):
     lib = _lib.require_device()
     if not 1 <= len(problems) <= GROUP_MAX:
         raise ValueError("conv2d_nhwc_grouped: %d problems (1..%d)" % (len(problems), GROUP_MAX))
-    if tile not in GROUP_TILES:
+    if not is_group_tile(tile):
         raise ValueError("conv2d_nhwc_grouped: tile %r is not a grouped tile" % (tile,))
     arr = (_ConvProblem * len(problems))()
     outs = []
@@ -559,8 +590,6 @@ def f32x_linear_tile(cout, K):
         return 489
     return F32X_LINEAR_TILE if cout >= 1024 else 493
 SUMS_FRAC_BITS = 18      # FAR3D_SUMS_FRAC_BITS in include/far3d_hip.h
-# GEMM tiles that exist AND leave LDS for the channel-sum scratch (114 / 115 fill the 160 KB with their ring; 118 / 119 are no kernels)
-_GEMM_TILES = set(range(70, 90)) | {110, 111, 112, 113, 116, 117} | set(range(120, 130)) | set(range(140, 146)) | set(range(170, 182)) | set(range(185, 189)) | {279, 280} | set(range(460, 478))
 _GEMM_TILE_PIXELS = 512  # no GEMM tile holds more pixels
 
 
@@ -581,11 +610,10 @@ def conv_can_fuse_sums(x, pc, out_dtype=torch.bfloat16):
     if H * W < _GEMM_TILE_PIXELS or pc.Cout % 8:
         return False
     pair_in = _is_pair_input(x, pc)
-    Cin = Cx // 2 if pair_in else Cx
-    if Cin % 32:
+    if (Cx // 2 if pair_in else Cx) % 32:
         return False
-    tile = _pair_tile(pc, Cin, N * H * W, 0) if pair_in else _tuned_tile(pc.Cout, Cin, 1, 1, N * H * W)
-    return tile in _GEMM_TILES or (pair_in and tile == 0)
+    tile = _conv_plan(x, pc, out_dtype, sums=True)[2]
+    return tile_takes_sums(tile, pair_in) or (pair_in and tile == 0)
 
 
 def linear(x, pc, act=None, res=None, out=None, out_dtype=torch.float32, tile=0):

@@ -144,36 +144,22 @@ int far3d_agg_tables(const float* Vc, float* tables, int layers, int N, int J, v
  * y2 (optional, y2_dt): second output y2 = y2_scale[n][m] * v + y2_shift[n][m] (FarHead's camera-aware MLN,
  *    ref: models/utils/misc.py:182-190, models/dense_heads/farhead.py:553-563) so that the FPN output conv writes
  *    the modulated token-major value maps directly.
- * tile: 0 auto (host callers pass the measured choice of far3d_amd/data/tuning_mi355x.json).  Any dtype: 1 128x128, 2 64x128,
- *    3 64x64, 4 128x64, 5 64x256 (channels x pixels).  bf16 with Cin % 32 == 0 only: 18, 43, 46, 48 (LDS-DMA ring variants, any
- *    kernel size / stride); 50-67, 90-97, 100-103 pipelined 3x3/s1/p1 kernel (channels x rows of 32 pixels, 4/8/16 waves, 2- or 3-deep
- *    weight ring, one kernel row or -- 100-103 -- all 9 taps per barrier step); 70-81 pipelined 1x1/s1 GEMM kernel.
- *    x_dt = FAR3D_DT_BF16_PAIR (w_dt must be FAR3D_DT_F32_BF16X3; y_dt pair or f32; res_dt any): 1-5 register-staged kernel (any
- *    kernel size / stride); 150-168, 191-197 the pipelined 3x3 shapes 50-68 / 91-97 with split products (169 / 190 / 198: 7-row
- *    forms); 170-181 the pipelined 1x1 shapes (185 / 186 128 x 160, 187 / 188 64 x 96 for the small maps); 252, 260, 265, 279, 280: the hi halves only (ONE bf16 product per term: a single-bf16 layer inside a pair-stored
- *    network).  An id the layer cannot use is an error, not a silent fallback.
- *    bf16, 1x1/s1 only: 82-89 the GEMM tiles with 3- / 4-deep LDS rings, 110-117 256 x 256 (and other large) tiles, 120-129 the
- *    GEMM with full-line LDS-DMA pieces (8 rows x 128 bytes per piece instead of 16 x 64), 140-145 split weight / activation rings;
- *    30-35 the 3x3 / stride 2 / pad 1 layers on the LDS-patch kernel (pair: 330, 331).
- *    x_dt = FAR3D_DT_F32 with w_dt = FAR3D_DT_F32_BF16X3, 1x1/s1, Cin % 32 == 0, x 16-byte aligned with strides that are multiples
- *    of 4 floats: 479-481 (auto) the pipelined GEMM kernel on fp32 rows -- 32 floats are the 128 bytes of a pair-stored block, so
- *    the LDS-DMA pattern is the pair kernel's and the hi / lo split of the rows happens in registers (same three products).
- *    x_dt = w_dt = FAR3D_DT_F32, 1x1/s1, Cin % 32 == 0, same alignment: 482-494 the pipelined GEMM kernel with the EXACT fp32 MFMA
- *    (v_mfma_f32_32x32x2_f32) on fp32 rows of both operands -- exact products, fp32 accumulation, another summation order than the
- *    register-staged kernel (tiles 1-5); 482 / 483 64 x 64 (2 / 4 LDS stages), 484 / 485 128 x 128, 486 64 x 128; 487-494 split K
- *    between 2-8 wave groups INSIDE the workgroup (each group its own LDS ring, partial tiles added in group order through LDS):
- *    487 / 488 / 494 64 x 64 (2 / 4 / 2 groups), 489 / 493 32 x 64 (4 / 2), 490 64 x 32 (4), 491 / 492 32 x 32 (4 / 8).  The bits
- *    of an output row depend on the tile and on Cin only, never on the number of rows in the call.
- *    3x3/s1/p1, Cin % 32 == 0, Cout % 32 == 0, same storage in and out, 16-byte aligned rows, NO res / y2 / chan_sums: the PERSISTENT
- *    wave-specialised kernel (csrc/conv_ws.hpp: producer waves issue every LDS-DMA, consumer waves only read LDS and run MFMAs, one
- *    workgroup per CU walks several tiles, 16-byte stores straight from the MFMA registers) -- pair storage 400-419 (one hand-over
- *    per tap), 450-459 (one per kernel row), 440 / 444 / 445 (LDS counters instead of the barrier; measured slower), bf16 420-423.
- *    Results are bit-identical to the pipelined 3x3 kernel (same products in the same order).
- *    1x1/s1 on pair-stored maps (x and y pair storage, Cin % 32 == 0, Cout % 32 == 0, 16-byte aligned rows, input below 2 GB, NO res /
- *    y2): 460-476 the persistent wave-specialised GEMM (gemm1x1_ws_kernel: the producers stream weights AND activation rows through one
- *    LDS ring; 460-463, 465, 469 128 x 128, 464 / 471 / 473 256 x 128, 470 / 476 128 x 256, 474 192 x 128, 466-468 64 x 128), bit-identical to
- *    the pipelined GEMM; chan_sums allowed when Ho*Wo >= the tile's pixels and Cin >= 64 x the tile's steps per hand-over.
- * chan_sums (optional, DEVICE int64 [N][Cout]; 1x1/s1 layers on a pipelined GEMM tile with a bf16 or pair output, Ho*Wo >= the
+ * tile: 0 auto (host callers pass the measured choice of far3d_amd/data/tuning_mi355x*.json), else an id of the table in
+ *    far3d_amd/csrc/conv_tiles.hpp -- one row per id with its workgroup shape; far3d_conv_tile_caps answers what an id takes.
+ *    The families: 1-5 register-staged kernel (any dtype, kernel size and stride).  bf16 x bf16 with Cin % 32 == 0 (LDS-DMA): 1-4,
+ *    18, 43-48 ring kernel (any kernel size / stride), 30-35 3x3/s2/p1, 50-139 3x3/s1/p1 LDS-patch kernel, 70-145 1x1/s1 pipelined
+ *    GEMMs.  x_dt = FAR3D_DT_BF16_PAIR (w_dt must be FAR3D_DT_F32_BF16X3; y_dt pair or f32; res_dt any): bf16 id + 100 = the same
+ *    shape with split products (150-198, 330 / 331), + 200 = the hi halves only (252, 260, 265, 279, 280: ONE bf16 product per term, a
+ *    single-bf16 layer inside a pair-stored network).  x_dt = FAR3D_DT_F32, 1x1/s1, Cin % 32 == 0, x 16-byte aligned with strides
+ *    that are multiples of 4 floats: 479-481 (auto) with w_dt = FAR3D_DT_F32_BF16X3 -- the pair GEMM on fp32 rows, hi / lo split in
+ *    registers; 482-494 with w_dt = FAR3D_DT_F32 -- the EXACT fp32 MFMA on the same kernel (487-494 split K between wave groups inside
+ *    the workgroup); the bits of an output row depend on the tile and on Cin only, never on the number of rows in the call.
+ *    400-459 (3x3/s1/p1; pair storage, 420-423 bf16) and 460-476 (1x1/s1, pair storage): the PERSISTENT wave-specialised kernels
+ *    (csrc/conv_ws.hpp) -- Cin % 32 == 0, Cout % 32 == 0, same storage in and out, 16-byte aligned rows, NO res / y2 (3x3: no
+ *    chan_sums either; 1x1: chan_sums when Ho*Wo >= the tile's pixels and Cin >= 64 x the tile's steps per hand-over, input below
+ *    2 GB); bit-identical to the pipelined kernels (same products in the same order).
+ *    An id the layer cannot use is an error (FAR3D_ERR_ARG, nothing launched), never a silent fallback.
+ * chan_sums (optional, DEVICE int64 [N][Cout]; 1x1/s1 layers on a tile with FAR3D_TILE_SUMS, bf16 or pair output, Ho*Wo >= the
  *    tile's pixel count): every STORED output element v (for a pair output: its hi and its lo half) ADDS
  *    rint(v * 2^FAR3D_SUMS_FRAC_BITS) to chan_sums[n][channel] -- the global average pool of VoVNet's eSE block (ref
  *    models/backbones/vovnet.py:173-185) comes out of the concat convolution's epilogue instead of a second pass over its output.
@@ -210,6 +196,30 @@ typedef struct {
  * adds the same products in the same order).  tile: 500-559, the workgroup of persistent tile (tile - 100).  Mixed Cin, more than
  * FAR3D_WS_GROUP_MAX problems, unaligned rows or an unknown tile are errors; nothing is launched then. */
 int far3d_conv2d_nhwc_grouped(const far3d_conv_problem* probs, int n, int tile, void* stream);
+
+/* What tile id `tile` of far3d_conv2d_nhwc / far3d_conv2d_nhwc_grouped is, for activations x_dt and weights w_dt: a mask of the bits
+ * below, or -1 when there is no such tile for that storage (0 = auto is no tile).  Host arithmetic on the table of
+ * far3d_amd/csrc/conv_tiles.hpp and the launchers' own compile-time constants; no device needed.  Ids 1-5 exist for every storage
+ * far3d_conv2d_nhwc accepts (on bf16 x bf16, 1-4 are the LDS-DMA ring kernel where rows are aligned). */
+#define FAR3D_TILE_GEOM 3          /* caps & 3: the layer geometry the tile takes */
+#define FAR3D_TILE_ANY 0           /*   any kernel size / stride / padding */
+#define FAR3D_TILE_1X1 1           /*   1x1 / stride 1 / pad 0 */
+#define FAR3D_TILE_3X3 2           /*   3x3 / stride 1 / pad 1 */
+#define FAR3D_TILE_3X3S2 3         /*   3x3 / stride 2 / pad 1 */
+#define FAR3D_TILE_STORE(caps) (((caps) >> 2) & 7)   /* input storage: */
+#define FAR3D_TILE_BF16 0          /*   bf16 x bf16 */
+#define FAR3D_TILE_PAIR 1          /*   pair-stored x split weights */
+#define FAR3D_TILE_F32_SPLIT 2     /*   fp32 rows x split weights */
+#define FAR3D_TILE_F32 3           /*   fp32 x fp32, exact */
+#define FAR3D_TILE_F32_BF16 4      /*   fp32 x bf16 weights (ids 1-5 only) */
+#define FAR3D_TILE_HI_ONLY 32      /* pair storage, the hi planes only (one bf16 product per term) */
+#define FAR3D_TILE_PERSISTENT 64   /* persistent wave-specialised kernel: bias + activation + store only (no res / y2) */
+#define FAR3D_TILE_HAS_GROUP 128   /* tile + 100 launches the same workgroup through far3d_conv2d_nhwc_grouped */
+#define FAR3D_TILE_GROUPED 256     /* an id of far3d_conv2d_nhwc_grouped (geometry and storage of tile - 100) */
+#define FAR3D_TILE_SUMS 512        /* chan_sums possible (the map must still hold a pixel tile) */
+#define FAR3D_TILE_LDS_DMA 1024    /* operands go to LDS by DMA: Cin % 32 == 0 */
+#define FAR3D_TILE_PIXELS(caps) ((caps) >> 16)       /* output pixels per workgroup tile */
+int far3d_conv_tile_caps(int tile, int x_dt, int w_dt);
 
 /* How a single-problem launch of the persistent 3x3 kernel deals its items to its workgroups (host arithmetic, no device needed; the
  * kernel evaluates the same inline function).  A launch has n_full full items and n_light light ones (the items of a partly empty last

@@ -1,47 +1,31 @@
-"""CPU: the measured tile table (far3d_amd/data/tuning_mi355x.json) must only name tiles the dispatcher of
-far3d_conv2d_nhwc implements for that kind of layer -- a stale id would only surface as a runtime error on the GPU box."""
+"""CPU: the measured tile tables (far3d_amd/data/tuning_mi355x*.json) must only name tiles the library has for that kind of layer
+and storage (far3d_conv_tile_caps of the built library) -- a stale id would only surface as a runtime error on the GPU box."""
 import json
 import os
-import re
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _dispatch_ids():
-    src = open(os.path.join(ROOT, "far3d_amd", "csrc", "igemm.hip")).read()
-    ids = {"igemm": set(), "dma": set(), "patch": set(), "pipe3": set(), "gemm": set()}
-    for m in re.finditer(r"case (\d+): (?:rc = |return )?(launch_[a-z0-9_]+)<", src):
-        tile, fn = int(m.group(1)), m.group(2)
-        key = {"launch_igemm": "igemm", "launch_igemm_dma": "dma", "launch_conv3x3_patch": "patch",
-               "launch_conv3x3_pipe": "pipe3", "launch_gemm1x1_pipe": "gemm", "launch_gemm1x1_wide": "gemm", "launch_gemm1x1_split": "gemm"}[fn]
-        ids[key].add(tile)
-    return ids
-
 
 import pytest
 
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GEOM = {(1, 1): 1, (3, 1): 2, (3, 2): 3}       # (kernel size, stride) -> FAR3D_TILE_1X1 / _3X3 / _3X3S2
+
+
+def _takes(caps, k, stride):
+    """The tile exists for the storage asked about and takes the layer's geometry (any-geometry tiles take every layer)."""
+    return caps >= 0 and (caps & 3) in (0, GEOM.get((k, stride), 0))
+
 
 @pytest.mark.parametrize("name", ["tuning_mi355x.json", "tuning_mi355x_tput.json"])      # tuned alone / under the frame pipeline's 3-stream concurrency
-def test_tuning_table_names_only_implemented_tiles(name):
-    ids = _dispatch_ids()
-    assert ids["pipe3"] and ids["gemm"] and ids["dma"], ids
+def test_tuning_table_names_only_implemented_tiles(name, hip_lib):
+    from far3d_amd import ops
     table = json.load(open(os.path.join(ROOT, "far3d_amd", "data", name)))
     assert table, "empty tuning table"
     assert set(table) == set(json.load(open(os.path.join(ROOT, "far3d_amd", "data", "tuning_mi355x.json")))), "the two tables must cover the same layers"
     for key, tile in table.items():
         cout, cin, k, stride, npix = (int(v) for v in key.split(","))
         assert cout > 0 and cin > 0 and npix > 0 and k in (1, 3) and stride in (1, 2), key
-        generic = ids["igemm"] | ids["dma"]                      # any kernel size / stride (bf16, Cin % 32 == 0 for the DMA ring)
-        if k == 3 and stride == 1:
-            allowed = generic | ids["patch"] | {t for t in ids["pipe3"] if not 30 <= t <= 39}
-        elif k == 1 and stride == 1:
-            allowed = generic | ids["gemm"]
-        elif k == 3 and stride == 2:
-            allowed = generic | {t for t in ids["pipe3"] if 30 <= t <= 39}
-        else:
-            allowed = generic
-        assert tile in allowed, "tile %d is not dispatchable for layer %s" % (tile, key)
-        if tile in ids["dma"] | ids["patch"] | ids["pipe3"] | ids["gemm"]:
+        caps = ops.tile_caps(tile, ops.DT_BF16, ops.DT_BF16)
+        assert _takes(caps, k, stride) and not caps & ops.TILE_PERSISTENT, "tile %d is not dispatchable for layer %s" % (tile, key)
+        if caps & ops.TILE_LDS_DMA:
             assert cin % 32 == 0, "LDS-DMA tile %d needs Cin %% 32 == 0 (%s)" % (tile, key)
 
 
@@ -60,32 +44,25 @@ def test_tuned_tile_lookup_borrows_nearest_pixel_count():
 
 
 @pytest.mark.parametrize("name", ["tuning_mi355x_pair.json", "tuning_mi355x_pair_tput.json"])
-def test_pair_tuning_table_names_only_implemented_tiles(name):
-    """Same for the pair-storage (bf16x3) table: ids 150+ of igemm_pair.hip, 1..5 for the register-staged kernel."""
-    src = open(os.path.join(ROOT, "far3d_amd", "csrc", "igemm_pair.hip")).read()
-    ids = {"igemm": set(), "pipe3": set(), "gemm": set()}
-    for m in re.finditer(r"case (\d+): (?:rc = |return )?(launch_[a-z0-9_]+)<", src):
-        ids[{"launch_igemm": "igemm", "launch_conv3x3_pipe": "pipe3", "launch_gemm1x1_pipe": "gemm"}[m.group(2)]].add(int(m.group(1)))
-    ws_src = open(os.path.join(ROOT, "far3d_amd", "csrc", "conv_ws.hip")).read()
-    # launch_conv3x3_ws<WGM, WGN, WM, WN, NP, PAIR, ...>: the tiles whose sixth template argument says pair storage
-    ws_pair = {int(m.group(1)) for m in re.finditer(r"case (\d+): return launch_conv3x3_ws<([^>]*)>", ws_src) if m.group(2).split(",")[5].strip() == "true"}
-    ws_gemm = {int(m.group(1)) for m in re.finditer(r"case (\d+): return launch_gemm1x1_ws<", ws_src)}      # persistent 1x1 GEMM (pair storage only)
-    table = json.load(open(os.path.join(ROOT, "far3d_amd", "data", name)))
-    assert table and ids["pipe3"] and ids["gemm"] and ids["igemm"] == {1, 2, 3, 4, 5} and ws_pair and all(400 <= t < 460 for t in ws_pair)
-    assert ws_gemm and all(460 <= t < 478 for t in ws_gemm)
-    assert set(table) == set(json.load(open(os.path.join(ROOT, "far3d_amd", "data", "tuning_mi355x_pair.json"))))
+def test_pair_tuning_table_names_only_implemented_tiles(name, hip_lib):
+    """Same for the pair-storage (bf16x3) table: split-product tiles of the layer's geometry, 1..5 for the register-staged kernel."""
     from far3d_amd import ops
+    table = json.load(open(os.path.join(ROOT, "far3d_amd", "data", name)))
+    assert table
+    assert set(table) == set(json.load(open(os.path.join(ROOT, "far3d_amd", "data", "tuning_mi355x_pair.json"))))
+    pair_caps = lambda t: ops.tile_caps(t, ops.DT_BF16_PAIR, ops.DT_F32_BF16X3)      # noqa: E731
     for key, tile in table.items():
         cout, cin, k, stride, npix = (int(v) for v in key.split(","))
         assert cin % 32 == 0, key
-        allowed = ids["igemm"] | ({t for t in ids["pipe3"] if t < 300} if (k == 3 and stride == 1) else ids["gemm"] if (k == 1 and stride == 1) else
-                                  {t for t in ids["pipe3"] if t >= 330} if (k == 3 and stride == 2) else set())
         if isinstance(tile, list):
             # [wave-specialised tile (csrc/conv_ws.hip: 3x3 layers without residual / sums, 1x1 layers on pair maps), the general tile every other call of the layer shape takes]
             ws, tile = tile
-            assert stride == 1 and cout % 32 == 0 and ws in ops.WS_TILES and ((k == 3 and ws in ws_pair) or (k == 1 and ws in ws_gemm)), (key, ws)
+            assert stride == 1 and cout % 32 == 0 and ops.is_ws_tile(ws) and not ops.is_group_tile(ws) and k in (1, 3) and \
+                (pair_caps(ws) & 3) == GEOM[(k, 1)], (key, ws)          # a persistent pair 3x3 tile on a 3x3 layer, a persistent pair GEMM on a 1x1
             assert ops._tuned_tile(cout, cin, k, stride, npix, name, ws_ok=True) == ws and ops._tuned_tile(cout, cin, k, stride, npix, name) == tile
-        assert tile in allowed and not 200 <= tile < 300, "tile %d is not a split-product tile for layer %s" % (tile, key)
+        caps = pair_caps(tile)
+        assert _takes(caps, k, stride) and not caps & (ops.TILE_PERSISTENT | ops.TILE_HI_ONLY) and not 200 <= tile < 300, \
+            "tile %d is not a split-product tile for layer %s" % (tile, key)
 
 
 def test_persistent_tiles_are_not_borrowed_across_pixel_counts():
@@ -94,7 +71,7 @@ def test_persistent_tiles_are_not_borrowed_across_pixel_counts():
     from far3d_amd import ops
     name = "tuning_mi355x_pair.json"
     ws, gen = json.load(open(os.path.join(ROOT, "far3d_amd", "data", name)))["256,768,1,1,268800"]
-    assert ws in ops.WS_TILES and gen not in ops.WS_TILES
+    assert ops.is_ws_tile(ws) and not ops.is_ws_tile(gen)
     assert ops._tuned_tile(256, 768, 1, 1, 268800, name, ws_ok=True) == ws and ops._tuned_tile(256, 768, 1, 1, 268800, name) == gen
     assert ops._tuned_tile(256, 768, 1, 1, 230400, name, ws_ok=True) == ws          # 6 of 7 cameras: within a quarter
     for npix in (38400, 76800, 153600):                                             # 1, 2, 4 cameras per rank

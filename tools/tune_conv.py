@@ -129,7 +129,7 @@ def main():
         # SUMS=1: time the 1x1 layers WITH the channel sums of the eSE fusion in their epilogue (GEMM tiles only, Ho*Wo >= 512)
         sums = torch.zeros(N, Cout, dtype=torch.int64, device=dev) if (os.environ.get("SUMS") and k == 1 and Ho * Wo >= 512 and Cout % 8 == 0) else None
         if sums is not None:
-            tiles = tuple(tl for tl in tiles if tl in ops._GEMM_TILES)
+            tiles = tuple(tl for tl in tiles if ops.tile_takes_sums(tl, pair))
         ys = [torch.empty_like(y) for _ in range(conc)] if conc else None
         for tile in tiles:
             try:
@@ -147,10 +147,10 @@ def main():
             res[0] = float("nan")
         best = min((t, tl) for tl, t in res.items() if tl != 0)
         table[key] = best[1]
-        if best[1] in ops.WS_TILES:
+        if ops.is_ws_tile(best[1]):
             # the persistent wave-specialised kernel covers plain layers only: the entry carries the fastest general tile beside it, and the
             # ws tile is taken only where it wins by more than the run-to-run noise (3 %)
-            other = min((t, tl) for tl, t in res.items() if tl != 0 and tl not in ops.WS_TILES)
+            other = min((t, tl) for tl, t in res.items() if tl != 0 and not ops.is_ws_tile(tl))
             table[key] = [best[1], other[1]] if best[0] < 0.97 * other[0] else other[1]
         print("%-10s %-24s auto %7.1f us | " % (name, key, res[0] * 1e6) + " ".join("t%d %4.0f" % (tl, res[tl] * 1e6) for tl in tiles if tl) +
               " | best t%d %6.1f us %6.1f TF/s" % (best[1], best[0] * 1e6, fl / best[0] / 1e12), flush=True)
