@@ -43,7 +43,9 @@ def load_config(path):
 def default_model_cfg(num_cams=7, num_query=644, num_propagated=256, memory_len=1024, topk_proposals=256, backbone="V-99-eSE",
                       proposal_topk=None, proposal_capacity=None, multi_depth_config=None):
     """The Far3D VoV-99 Argoverse-2 model (values of the reference's only config), assembled programmatically.
-    multi_depth_config: overrides the head's dict(topk=1, range_min=30) (e.g. topk=2: multi-depth 2D proposals)."""
+    multi_depth_config: overrides the head's dict(topk=1, range_min=30) (e.g. topk=2: multi-depth 2D proposals).
+    backbone: a VoVNet spec name; the FPN's in_channels are that spec's stage widths."""
+    from .weights import VOV_SPECS
     depthnet = dict(type=0, hidden_dim=256, num_depth_bins=50, depth_min=0.1, depth_max=110, stride=8)
     strides = [8, 16, 32, 64]
     self_attn = dict(type="MultiheadAttention", embed_dims=256, num_heads=8, dropout=0.1)
@@ -67,5 +69,5 @@ def default_model_cfg(num_cams=7, num_query=644, num_propagated=256, memory_len=
                 img_backbone=dict(type="VoVNet", spec_name=backbone, norm_eval=True, frozen_stages=-1, input_ch=3,
                                   out_features=("stage2", "stage3", "stage4", "stage5")),
                 img_neck=dict(type="FPN", start_level=1, add_extra_convs="on_output", relu_before_extra_convs=True,
-                              in_channels=[256, 512, 768, 1024], out_channels=256, num_outs=4),
+                              in_channels=list(VOV_SPECS[backbone]["stage_out_ch"]), out_channels=256, num_outs=4),
                 img_roi_head=roi, pts_bbox_head=head, proposal_topk=proposal_topk, proposal_capacity=proposal_capacity)

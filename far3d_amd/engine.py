@@ -151,7 +151,14 @@ class Far3DEngine:
             if ck is not None:
                 self.sd[ck] = v.detach().float()
         self.spec = weights.VOV_SPECS[self.cfg["backbone"]]
-        self.convs = {}             # name -> PackedConv of every conv layer of the per-camera stages
+        if self.pair:
+            # pair storage keeps [32 hi | 32 lo] per 32-channel block: a map whose width is no multiple of 32 has no such layout
+            odd = [c for c in tuple(self.spec["stem"]) + tuple(self.spec["stage_conv_ch"]) + tuple(self.spec["stage_out_ch"]) if c % 32]
+            if odd:
+                raise ValueError("backbone %s has a channel width of %d, which is not a multiple of 32: the pair-stored precision %r cannot "
+                                 "hold it; the modes that run this spec are %s" %
+                                 (self.cfg["backbone"], odd[0], self.precision, ", ".join(k for k, v in PRECISIONS.items() if not v.get("pair"))))
+        self.convs = {}           # name -> PackedConv of every conv layer of the per-camera stages
         self._bufs = {}
         self._ins = {}              # static input buffers per buffer-set parity (graph replay reads them)
         self._graph = None
@@ -236,20 +243,36 @@ class Far3DEngine:
         bb = {}
         w, b, _, _ = self._conv_bn("img_backbone.stem.stem_1")
         bb["stem1"] = self._pack(F.pad(w.permute(0, 2, 3, 1).reshape(w.shape[0], 27), (0, 5)), b, name="stem1")   # 1x1 over the 32-ch im2col
-        bb["stem2"] = self._pack(*self._conv_bn("img_backbone.stem.stem_2"), name="stem2")
-        bb["stem3"] = self._pack(*self._conv_bn("img_backbone.stem.stem_3", stride=2), name="stem3")
+        dw = bool(self.spec.get("dw"))
+
+        def layer3(prefix, name, stride=1):
+            """A 3x3 layer: conv + BN + ReLU as one PackedConv, or -- depthwise specs (vovnet.py:100-121) -- the [9][C] depthwise weights
+            plus the pointwise 1x1 with `pw_norm` folded in (named '<name>.pw'; nothing nonlinear sits between the two)."""
+            if not dw:
+                return self._pack(*self._conv_bn(prefix, stride=stride), name=name)
+            return dict(dw=ops.pack_dw3x3(sd[prefix + "/dw_conv3x3.weight"], dev), stride=stride,
+                        pw=self._pack(*self._conv_bn(prefix, conv="/pw_conv1x1", norm="/pw_norm", pad=0), name=name + ".pw"))
+
+        bb["stem2"] = layer3("img_backbone.stem.stem_2", "stem2")
+        bb["stem3"] = layer3("img_backbone.stem.stem_3", "stem3", stride=2)
         stages = []
+        in_ch = self.spec["stem"][2]
         for si in range(4):
             k = si + 2
+            sc = self.spec["stage_conv_ch"][si]
             blocks = []
             for bi in range(self.spec["block_per_stage"][si]):
                 name = "OSA%d_%d" % (k, bi + 1)
                 p = "img_backbone.stage%d.%s" % (k, name)
-                convs = [self._pack(*self._conv_bn("%s.layers.%d.%s_%d" % (p, i, name, i)), name="s%d.b%d.c%d" % (k, bi, i))
+                convs = [layer3("%s.layers.%d.%s_%d" % (p, i, name, i), "s%d.b%d.c%d" % (k, bi, i))
                          for i in range(self.spec["layer_per_block"])]
                 cw, cb, _, _ = self._conv_bn("%s.concat.%s_concat" % (p, name), pad=0)
-                blocks.append(dict(convs=convs, concat=self._pack(cw, cb, name="s%d.b%d.cat" % (k, bi)), fcw=f32(sd[p + ".ese.fc.weight"].flatten(1)),
-                                   fcb=f32(sd[p + ".ese.fc.bias"])))
+                blk = dict(convs=convs, concat=self._pack(cw, cb, name="s%d.b%d.cat" % (k, bi)), fcw=f32(sd[p + ".ese.fc.weight"].flatten(1)),
+                           fcb=f32(sd[p + ".ese.fc.bias"]))
+                if dw and in_ch != sc:      # 1x1 + BN + ReLU in front of layer 0 only; the concat keeps the unreduced input (vovnet.py:200-204,220-230)
+                    blk["red"] = self._pack(*self._conv_bn("%s.conv_reduction.%s_reduction_0" % (p, name), pad=0), name="s%d.b%d.red" % (k, bi))
+                blocks.append(blk)
+                in_ch = self.spec["stage_out_ch"][si]
             stages.append(blocks)
         bb["stages"] = stages
         self.bb = bb
@@ -430,6 +453,19 @@ class Far3DEngine:
         return b
 
     # ------------------------------------------------------------------------------------------ a2: backbone
+    def _layer3(self, src, layer, out=None):
+        """One 3x3 layer of the backbone on the NHWC view `src` (+ BN + ReLU) into `out` (None: a fresh map).  A plain spec's layer is one
+        convolution; a depthwise spec's (a dict, _prepare_backbone) is far3d_dwconv3x3_nhwc into a scratch map of the layer's width and
+        the pointwise 1x1 GEMM from there, whose epilogue applies the folded BN and the ReLU."""
+        if not isinstance(layer, dict):
+            return ops.conv2d_nhwc(src, layer, out=out, act="relu")
+        N, H, W, Cs = src.shape
+        s = layer["stride"]
+        shape = (N, (H - 1) // s + 1, (W - 1) // s + 1, Cs)
+        # one scratch map per shape and buffer set: the launches of a stream are ordered, and a captured graph keeps its address
+        tmp = ops.dwconv3x3_nhwc(src, layer["dw"], s, out=self._buf(("dw_tmp",) + shape, shape, self.prec["act"]), pair=self.pair)
+        return ops.conv2d_nhwc(tmp, layer["pw"], out=out, act="relu")
+
     @_with_tile_tables
     def backbone(self, img, keep_stage2=True):
         """img (N,3,H,W) f32 NCHW on device -> [stage2..stage5] dense NHWC maps (pair mode: 2C stored bf16 channels each).
@@ -462,8 +498,8 @@ class Far3DEngine:
         else:
             x = ops.stem_im2col(img, act, pair=pair)
             x = ops.conv2d_nhwc(x, self.bb["stem1"], act="relu")
-        x = ops.conv2d_nhwc(x, self.bb["stem2"], act="relu")
-        H, W = self.bb["stem3"].out_hw(x.shape[1], x.shape[2])
+        x = self._layer3(x, self.bb["stem2"])
+        H, W = (x.shape[1] - 1) // 2 + 1, (x.shape[2] - 1) // 2 + 1       # stem3: 3x3 / stride 2 / pad 1
         in_ch = spec["stem"][2]
         outs = []
         stage_in = None   # dense input of the stage (stem3 output is written straight into the first concat buffer)
@@ -487,7 +523,7 @@ class Far3DEngine:
             else:
                 cat = self._buf(("cat", si, 0), want_shape, act)
             if si == 0:
-                ops.conv2d_nhwc(x, self.bb["stem3"], out=cat[..., :in_ch * cs], act="relu")
+                self._layer3(x, self.bb["stem3"], out=cat[..., :in_ch * cs])
             elif not pooled_by_ese:
                 assert stage_in is not None, "the previous stage's map was skipped (keep_stage2=False) but its eSE pass did not pool it"
                 ops.maxpool3x3s2_nhwc(stage_in, out=cat[..., :in_ch * cs], pair=pair)
@@ -496,9 +532,11 @@ class Far3DEngine:
             for bi, blk in enumerate(blocks):
                 last = bi == len(blocks) - 1
                 src = cat[..., :cur_in * cs]
+                if "red" in blk:       # depthwise block whose input width differs from the stage width: layer 0 reads the reduced map
+                    src = ops.conv2d_nhwc(src, blk["red"], out=self._buf(("red", si), (N, H, W, sc * cs), act), act="relu")
                 for i, pc in enumerate(blk["convs"]):
                     dst = cat[..., (cur_in + i * sc) * cs: (cur_in + (i + 1) * sc) * cs]
-                    ops.conv2d_nhwc(src, pc, out=dst, act="relu")
+                    self._layer3(src, pc, out=dst)
                     src = dst
                 fuse = esums is not None and ops.conv_can_fuse_sums(cat, blk["concat"])
                 xt = ops.conv2d_nhwc(cat, blk["concat"], out=self._buf(("xt", si), (N, H, W, oc * cs), act), act="relu",

@@ -978,6 +978,42 @@ def maxpool3x3s2_nhwc(x, out=None, pair=False):
     return out
 
 
+def pack_dw3x3(weight, device=None):
+    """Depthwise 3x3 weights (C,1,3,3) -> the kernel's [9][C] f32 layout, w9c[ky*3 + kx][c] = weight[c][0][ky][kx]."""
+    C = weight.shape[0]
+    if tuple(weight.shape) != (C, 1, 3, 3):
+        raise ValueError("pack_dw3x3: expected a (C,1,3,3) depthwise weight, got %s" % (tuple(weight.shape),))
+    w = weight.detach().float().reshape(C, 9).t().contiguous()
+    return w.to(device) if device is not None else w
+
+
+def dwconv3x3_nhwc(x, w9c, stride, out=None, pair=False):
+    """Depthwise 3x3 / pad 1 / stride 1|2 convolution without bias or activation (nn.Conv2d(C, C, 3, stride, 1, groups=C, bias=False)) on
+    an NHWC view x (f32 | bf16; pair: a pair-stored bf16 map of 2C stored channels).  w9c: (9, C) f32 (pack_dw3x3).  out: optional NHWC view
+    of x's storage (a channel slice of a wider buffer is fine).  Sizes, strides and alignment are checked by the library
+    (Far3dHipError, nothing launched)."""
+    lib = _lib.require_device()
+    N, H, W, Cs = x.shape
+    C = Cs // 2 if pair else Cs
+    if pair and x.dtype != torch.bfloat16:
+        raise TypeError("dwconv3x3_nhwc: pair storage is bf16")
+    _chk(w9c, "w9c", torch.float32, 2)
+    if tuple(w9c.shape) != (9, C):
+        raise ValueError("dwconv3x3_nhwc: weights %s != (9, %d)" % (tuple(w9c.shape), C))
+    ldx, xs = _nhwc_view(x, "x")
+    if out is None:
+        s = int(stride)
+        if s < 1:
+            raise ValueError("dwconv3x3_nhwc: stride %r" % (stride,))
+        out = torch.empty((N, (H - 1) // s + 1, (W - 1) // s + 1, Cs), dtype=x.dtype, device=x.device)
+    if out.dtype != x.dtype or out.shape[0] != N or out.shape[3] != Cs:
+        raise ValueError("dwconv3x3_nhwc: out %s %s does not match x %s %s" % (tuple(out.shape), out.dtype, tuple(x.shape), x.dtype))
+    ldy, ys = _nhwc_view(out, "out")
+    _lib.check(lib.far3d_dwconv3x3_nhwc(_ptr(x), DT_BF16_PAIR if pair else _dt(x), _ptr(w9c), _ptr(out), N, H, W, C, ldx, xs,
+                                        out.shape[1], out.shape[2], ldy, ys, int(stride), _stream(x)), "far3d_dwconv3x3_nhwc")
+    return out
+
+
 # --------------------------------------------------------------------------------------------------
 # front-end glue: stem im2col, 2D proposals, MLN apply
 # --------------------------------------------------------------------------------------------------

@@ -317,9 +317,11 @@ class NMSFreeCoder:
 
 
 # ------------------------------------------------------------------------------------------------ per-camera modules
-@BACKBONES.register_module()
+@BACKBONES.register_module(name=["VoVNet", "VoVNetCP"])
 class VoVNet(_SchemaModule):
-    """models/backbones/vovnet.py:276-384.  forward(x NCHW f32) -> list of NCHW stage maps, computed by the HIP engine."""
+    """models/backbones/vovnet.py:276-384.  forward(x NCHW f32) -> list of NCHW stage maps, computed by the HIP engine.
+    All seven specs of the reference's registry (vovnet.py:89-97), the depthwise and slim ones included.  Also registered as `VoVNetCP`
+    (models/backbones/vovnetcp.py): the same parameters and forward -- its activation checkpointing is a training-memory device."""
     prefix = "img_backbone."
 
     def __init__(self, spec_name, input_ch=3, out_features=None, frozen_stages=-1, norm_eval=True, pretrained=None, init_cfg=None):
@@ -341,6 +343,9 @@ class VoVNet(_SchemaModule):
         outs = self._eng.backbone(x.float().contiguous())
         names = ["stage2", "stage3", "stage4", "stage5"]
         return [self._eng.act_to_nchw(o) for n, o in zip(names, outs) if n in self._out_features]
+
+
+VoVNetCP = VoVNet
 
 
 @NECKS.register_module()

@@ -25,7 +25,21 @@ VOV_SPECS = {
     # build-owned miniature with the same topology, for plumbing-scale fixtures (BASELINE configs[0] scale)
     "V-tiny-eSE": dict(stem=(32, 32, 64), stage_conv_ch=(32, 32, 64, 64), stage_out_ch=(64, 128, 192, 256),
                        layer_per_block=2, block_per_stage=(1, 1, 2, 1)),
+    # the light specs of the reference's registry (models/backbones/vovnet.py:19-47).  dw: every 3x3 layer after stem_1 is a depthwise
+    # 3x3 followed by a pointwise 1x1 + BN + ReLU (vovnet.py:100-121), with a 1x1 reduction in front of a block whose input width differs
+    # from the stage width (vovnet.py:200-204)
+    "V-19-slim-dw-eSE": dict(stem=(64, 64, 64), stage_conv_ch=(64, 80, 96, 112), stage_out_ch=(112, 256, 384, 512),
+                             layer_per_block=3, block_per_stage=(1, 1, 1, 1), dw=True),
+    "V-19-dw-eSE": dict(stem=(64, 64, 64), stage_conv_ch=(128, 160, 192, 224), stage_out_ch=(256, 512, 768, 1024),
+                        layer_per_block=3, block_per_stage=(1, 1, 1, 1), dw=True),
+    "V-19-slim-eSE": dict(stem=(64, 64, 128), stage_conv_ch=(64, 80, 96, 112), stage_out_ch=(112, 256, 384, 512),
+                          layer_per_block=3, block_per_stage=(1, 1, 1, 1)),
 }
+
+
+def is_dw(spec_name):
+    """Whether the spec builds its 3x3 layers as depthwise 3x3 + pointwise 1x1 (the reference's "dw" flag)."""
+    return bool(VOV_SPECS[spec_name].get("dw"))
 
 
 def _bn(spec, name, c):
@@ -33,12 +47,25 @@ def _bn(spec, name, c):
         spec[name + "." + k] = (c,)
 
 
+def _dw_layer(spec, n, c):
+    """Keys of a dw_conv3x3 layer of width c (vovnet.py:100-121): depthwise 3x3, pointwise 1x1, BN."""
+    spec[n + "/dw_conv3x3.weight"] = (c, 1, 3, 3)
+    spec[n + "/pw_conv1x1.weight"] = (c, c, 1, 1)
+    _bn(spec, n + "/pw_norm", c)
+
+
 def backbone_spec(spec_name, input_ch=3):
     s = VOV_SPECS[spec_name]
+    dw = bool(s.get("dw"))
     spec = OrderedDict()
     chans = [input_ch] + list(s["stem"])
     for i in range(3):
         n = "img_backbone.stem.stem_%d" % (i + 1)
+        if dw and i > 0:
+            if chans[i] != chans[i + 1]:
+                raise ValueError("depthwise stem layers keep their width (%s: %d -> %d)" % (spec_name, chans[i], chans[i + 1]))
+            _dw_layer(spec, n, chans[i + 1])
+            continue
         spec[n + "/conv.weight"] = (chans[i + 1], chans[i], 3, 3)
         _bn(spec, n + "/norm", chans[i + 1])
     in_ch = s["stem"][2]
@@ -50,9 +77,15 @@ def backbone_spec(spec_name, input_ch=3):
             p = "img_backbone.stage%d.%s" % (k, name)
             c = in_ch
             for i in range(s["layer_per_block"]):
+                if dw:
+                    _dw_layer(spec, "%s.layers.%d.%s_%d" % (p, i, name, i), sc)
+                    continue
                 spec["%s.layers.%d.%s_%d/conv.weight" % (p, i, name, i)] = (sc, c, 3, 3)
                 _bn(spec, "%s.layers.%d.%s_%d/norm" % (p, i, name, i), sc)
                 c = sc
+            if dw and in_ch != sc:      # registered after `layers` in the reference module, so it follows them in a state dict
+                spec["%s.conv_reduction.%s_reduction_0/conv.weight" % (p, name)] = (sc, in_ch, 1, 1)
+                _bn(spec, "%s.conv_reduction.%s_reduction_0/norm" % (p, name), sc)
             spec["%s.concat.%s_concat/conv.weight" % (p, name)] = (oc, in_ch + s["layer_per_block"] * sc, 1, 1)
             _bn(spec, "%s.concat.%s_concat/norm" % (p, name), oc)
             spec[p + ".ese.fc.weight"] = (oc, oc, 1, 1)
@@ -193,7 +226,8 @@ def init_state_dict(spec, seed=0, pc_range=(-152.4, -152.4, -5.0, 152.4, 152.4, 
             fan_in = 1
             for d in shape[1:]:
                 fan_in *= d
-            gain = 1.0 if ("attn" in k or "weights_fc" in k or "learnable_fc" in k or "branches" in k) else math.sqrt(2.0)
+            # (a depthwise 3x3 has no ReLU behind it -- vovnet.py:100-121 -- so it gets the linear gain)
+            gain = 1.0 if ("attn" in k or "weights_fc" in k or "learnable_fc" in k or "branches" in k or "dw_conv3x3" in k) else math.sqrt(2.0)
             v = torch.randn(shape, generator=g) * (gain / math.sqrt(fan_in))
             if "learnable_fc" in k:
                 # the reference's own initialiser for the key-point offsets (detr3d_transformer.py:505,517-520): nn.Linear's

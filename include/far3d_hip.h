@@ -355,6 +355,18 @@ int far3d_groupnorm_nhwc(const void* x, int dt, const float* gamma, const float*
 int far3d_maxpool3x3s2_nhwc(const void* x, int dt, void* y, int N, int H, int W, int C, int Ho, int Wo, int ldy,
                             long y_img_stride, void* stream);
 
+/* Depthwise 3x3 convolution, pad 1, stride 1 or 2, no bias, no activation: nn.Conv2d(C, C, 3, stride, 1, groups=C, bias=False), the
+ * first half of the `dw_conv3x3` layers of VoVNet's depthwise specs (ref models/backbones/vovnet.py:100-121; the pointwise 1x1 + BN +
+ * ReLU that follows is a far3d_conv2d_nhwc call -- there is no nonlinearity between the two).
+ * x, y: NHWC maps of storage `dt` with dense rows, pixel strides ldx / ldy and image strides in stored elements, pointers pre-offset to
+ * the first channel (channel slices of wider buffers are fine).  dt: FAR3D_DT_F32 or FAR3D_DT_BF16 with C % 8 == 0, FAR3D_DT_BF16_PAIR
+ * with C % 32 == 0 (hi + lo read, the fp32 result stored split).  w: [9][C] f32, w[ky*3 + kx][c] = weight[c][0][ky][kx].
+ * Ho = (H-1)/stride + 1, Wo = (W-1)/stride + 1.  Every pointer and stride a multiple of 16 bytes.  x and y must not overlap.
+ * fp32 accumulation in the fixed tap order (0,0) ... (2,2) with pinned fmas: the bits of an output element depend on its own window
+ * and weights only, never on N or the launch's other pixels.  Bad arguments return FAR3D_ERR_ARG and launch nothing. */
+int far3d_dwconv3x3_nhwc(const void* x, int dt, const float* w, void* y, int N, int H, int W, int C, int ldx, long x_img_stride,
+                         int Ho, int Wo, int ldy, long y_img_stride, int stride, void* stream);
+
 /* NCHW fp32 image (N,3,H,W) -> NHWC (N,Ho,Wo,32) im2col of the stride-2 3x3 stem conv: channel = (ky*3+kx)*3 + c for the
  * 27 taps, 5 zero channels; Ho = (H-1)/2+1.  The first VoVNet conv (ref models/backbones/vovnet.py:306-311) then runs as
  * a K=32 far3d_conv2d_nhwc 1x1. */
