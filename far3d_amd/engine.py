@@ -9,6 +9,7 @@ Data layout (HBM): all feature maps are NHWC (channels-last) in the activation d
 writes its channel slice in place, so torch.cat never runs; FPN outputs are written twice by the same conv epilogue:
 raw (for the 2D head) and camera-modulated, token-major (N, S, 256), which IS `feat_flatten` of the reference.
 """
+import contextlib
 import fnmatch
 import functools
 import math
@@ -885,14 +886,18 @@ class Far3DEngine:
         mln_scale, mln_shift = self.sa["gamma"](hh), self.sa["beta"](hh)           # (n, E) each
         feats = self.backbone(img, keep_stage2=False)
         raw, tokens, hw, starts = self.fpn(feats, mln_scale, mln_shift)
-        st = dict(tokens=tokens, hw=hw, starts=starts, raw=raw, lidar2img=lidar2img)
+        st = dict(tokens=tokens, hw=hw, starts=starts, raw=raw, lidar2img=lidar2img, cams=(lo, hi))
         cls, reg, depth_logit = self.roi_head(raw)
         st.update(self.proposals(cls, reg, depth_logit, img2lidar, tokens, block_rows))
         return st
 
     def proposals(self, cls, reg, depth_logit, img2lidar, tokens, block_rows=None):
         """a5 + the adaptive-query part of a6: peak selection and 3D proposal construction for n cameras.
-        block_rows: fixed-capacity threshold mode on a camera shard -- rows of this rank's (compacted, zero-padded) record block."""
+        block_rows (None: the cameras are the frame, or a top-K shard whose rows are static): the cameras are a BLOCK of the frame and
+        the result goes into buffers of block_rows rows (camera_block_rows(n)).  Single depth, fixed-capacity threshold mode: the block's
+        proposals compacted and zero-padded, with its own count and flag (a rank's record block of the camera-sharded runner).  Multi-depth
+        (either static mode): the block's primaries and per-primary records only -- no extra rows, no count, no flag;
+        merge_camera_blocks packs the blocks and runs the extras."""
         cfg = self.cfg
         n = tokens.shape[0]
         E = cfg["embed_dims"]
@@ -911,10 +916,13 @@ class Far3DEngine:
         whole = n == cfg["num_cams"] and "head" in self.parts and block_rows is None
         prim = n * cap if capT is None else (capT if block_rows is None else block_rows)
         Kmd = self.md_k
-        if Kmd > 1 and block_rows is not None:
-            raise ValueError("multi-depth proposals (multi_depth topk=%d) are not supported on a camera shard" % Kmd)
-        # multi-depth: [primaries | extras | hole]; legacy threshold mode sizes the extras from the selection capacity (never overflows)
-        extra = 0 if Kmd <= 1 else (self.md_extra_rows(prim) if (K is not None or capT is not None) else (Kmd - 1) * prim)
+        block = block_rows is not None
+        if block and capT is None and (K is None or block_rows != prim):
+            raise ValueError("block_rows: a camera block has min(proposal_capacity, its share) rows in the fixed-capacity threshold mode "
+                             "and cameras * proposal_topk = %s rows in the top-K mode (got %d)" % (prim if K is not None else None, block_rows))
+        # multi-depth: [primaries | extras | hole]; legacy threshold mode sizes the extras from the selection capacity (never overflows).
+        # A camera block (block_rows) builds its primaries and records only: merge_camera_blocks packs the blocks and runs the extras
+        extra = 0 if (Kmd <= 1 or block) else (self.md_extra_rows(prim) if (K is not None or capT is not None) else (Kmd - 1) * prim)
         rows = prim + extra
         if (K is not None or capT is not None) and whole:
             # every camera is local and the row count is static: the reference points land directly in the adaptive-query rows
@@ -926,7 +934,7 @@ class Far3DEngine:
         out = (ref_out, self._buf(("ctx",), (rows, E + 1), torch.float32),
                self._buf(("box2d",), (rows, 4), torch.float32), self._buf(("score2d",), (rows,), torch.float32))
         m_dev = ovf = None
-        if capT is not None or Kmd > 1:
+        if (capT is not None or Kmd > 1) and not (block and Kmd > 1):      # a multi-depth block has no count or flag of its own
             m_dev = self._buf(("m_dev",), (1,), torch.int32)
             if capT is not None or K is not None:
                 ovf = self._buf(("ovf",), (1,), torch.int32)
@@ -1084,6 +1092,67 @@ class Far3DEngine:
         if md is not None:
             outs["md_records"] = md["records"]
         return outs
+
+    @contextlib.contextmanager
+    def buffers(self, key):
+        """Run what is inside with the engine's persistent buffers taken from the set `key` (any hashable): camera blocks of one frame
+        that must keep their results side by side, e.g. camera_stage(..., block_rows=...) per block before merge_camera_blocks."""
+        keep = self._par
+        self._par = key
+        try:
+            yield
+        finally:
+            self._par = keep
+
+    def camera_block_rows(self, ncam):
+        """Rows of the proposal buffers of a block of `ncam` cameras (camera_stage's block_rows) in the two static proposal modes."""
+        K, capT = self.cfg["proposal_topk"], self.cfg.get("proposal_capacity")
+        if K is not None:
+            return ncam * K
+        if capT is None:
+            raise ValueError("camera blocks need a static proposal mode (proposal_topk or proposal_capacity): the legacy threshold mode syncs on M")
+        return min(capT, ncam * self.cfg["proposal_cap"])
+
+    def merge_camera_blocks(self, blocks):
+        """blocks: the results of camera_stage(..., block_rows=self.camera_block_rows(n)) for contiguous camera blocks that together are the
+        frame, in ascending camera order, each run inside its own `buffers` set.  Packs their proposals into the frame's layout
+        (proposal_merge_blocks: primaries camera-major, records with the frame's camera indices, one count, one flag), straight into
+        the adaptive-query rows of the head's buffer, then runs proposal_extra_rows when multi_depth topk > 1.  Two launches (one for
+        a single depth) + a small copy per block (img2lidar), no sync.  -> the proposal part of a whole-frame camera_stage result
+        (ref2d, ctx, box2d, score2d, sel_cnt, m_dev, overflow, md, md_records, rows) for head_stage."""
+        cfg = self.cfg
+        N, E, nq, Kmd = cfg["num_cams"], cfg["embed_dims"], cfg["num_query"], self.md_k
+        K = cfg["proposal_topk"]
+        capT = cfg.get("proposal_capacity") if K is None else None
+        if K is None and capT is None:
+            raise ValueError("merge_camera_blocks needs a static proposal mode (proposal_topk or proposal_capacity)")
+        P = N * K if K is not None else capT
+        if [b["cams"][0] for b in blocks] + [N] != [0] + [b["cams"][1] for b in blocks]:
+            raise ValueError("merge_camera_blocks: the blocks must be the frame's cameras in ascending order, got %s" % [b["cams"] for b in blocks])
+        rows = P + self.md_extra_rows(P)
+        out = (self._buf(("rf",), (nq + rows + cfg["memory_len"], 3), torch.float32)[nq:nq + rows], self._buf(("ctx",), (rows, E + 1), torch.float32),
+               self._buf(("box2d",), (rows, 4), torch.float32), self._buf(("score2d",), (rows,), torch.float32))
+        sel_cnt = self._buf(("sel_cnt",), (N,), torch.int32)
+        m_dev = ovf = None
+        if capT is not None or Kmd > 1:
+            m_dev, ovf = self._buf(("m_dev",), (1,), torch.int32), self._buf(("ovf",), (1,), torch.int32)
+            self._overflow = ovf
+        rec = md = None
+        if Kmd > 1:
+            rec = (self._buf(("md_flags",), (P,), torch.int32), self._buf(("md_info",), (P, 2 * Kmd), torch.int32))
+            i2l = self._buf(("md_i2l",), (N, 4, 4), torch.float32)
+            for b in blocks:
+                i2l[b["cams"][0]:b["cams"][1]].copy_(b["md"]["img2lidar"])
+            md = dict(records=rec, img2lidar=i2l, primary_rows=P, sel_cap=blocks[0]["md"]["sel_cap"], rows=rows)
+        parts = [dict(rows=(b["ref2d"], b["ctx"], b["box2d"], b["score2d"]), sel_cnt=b["sel_cnt"], first_cam=b["cams"][0],
+                      records=b["md"]["records"] if Kmd > 1 else None, overflow=b["overflow"],
+                      count=(b["cams"][1] - b["cams"][0]) * K if K is not None else b["m_dev"]) for b in blocks]
+        ops.proposal_merge_blocks(parts, out, sel_cnt, P, records_out=rec, m_out=m_dev, overflow_out=ovf)
+        st = dict(ref2d=out[0], ctx=out[1], box2d=out[2], score2d=out[3], sel_cnt=sel_cnt, m_dev=m_dev, overflow=ovf, md=md, rows=rows,
+                  md_records=rec)
+        if md is not None:
+            self.proposal_extra_rows(st, True)
+        return st
 
     def proposal_extra_rows(self, st, fill_hole=True):
         """The multi-depth extra rows of a frame whose primaries proposals() built (st: its result): one launch, no sync."""

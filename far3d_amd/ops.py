@@ -1202,6 +1202,78 @@ def proposal_extra_rows(sel_cnt, sel_cap, primary_rows, topk, records, img2lidar
     return ref2d, ctx, box2d, score
 
 
+def proposal_merge_blocks(blocks, out, sel_cnt_out, primary_rows, records_out=None, m_out=None, overflow_out=None):
+    """The proposals of camera blocks -> the frame's layout (far3d_hip.h far3d_proposal_merge_blocks).  blocks: dicts in ascending
+    camera order with rows = (ref2d, ctx, box2d, score) of the block's own buffers, sel_cnt (cams,) int32, first_cam, and optionally
+    records = (flags, info) (multi-depth; all blocks or none), count (int32 device scalar, or a static int; absent: min(sum sel_cnt,
+    the buffers' rows)) and overflow (int32 device scalar).  out = the frame's (ref2d, ctx, box2d, score) (rows_total = their rows):
+    rows [0, Mp) receive the blocks' primaries back to back, Mp = min(sum counts, primary_rows).  records_out = the frame's (flags,
+    info): multi-depth, rows past Mp are left for proposal_extra_rows; None: single depth, rows [Mp, rows_total) are zero-filled.
+    sel_cnt_out (N,) int32; m_out / overflow_out: int32 device scalars for Mp and the OR of the flags | overflow.  One launch, no sync."""
+    lib = _lib.require_device()
+    nb = len(blocks)
+    ref2d, ctx, box2d, score = out
+    rows_total = ref2d.shape[0]
+    C = ctx.shape[1] - 1
+    _chk(sel_cnt_out, "sel_cnt_out", torch.int32, 1)
+    if ref2d.stride(0) != 3 or ctx.stride(0) != C + 1 or min(ctx.shape[0], box2d.shape[0], score.shape[0]) < rows_total:
+        raise ValueError("proposal_merge_blocks: ref2d / ctx / box2d / score must be dense rows, as many as ref2d's")
+    if not (box2d.is_contiguous() and score.is_contiguous()) or box2d.dim() != 2 or box2d.shape[1] != 4 or score.dim() != 1:
+        raise ValueError("proposal_merge_blocks: the frame's box2d (rows, 4) and score (rows,) must be contiguous")
+    md = records_out is not None
+    if any(("records" in b and b["records"] is not None) != md for b in blocks):
+        raise ValueError("proposal_merge_blocks: multi-depth records come from every block and go to records_out, or from none")
+    topk = 0
+    if md:
+        _chk(records_out[0], "md_flags", torch.int32, 1)
+        _chk(records_out[1], "md_info", torch.int32, 2)
+        topk = records_out[1].shape[1] // 2
+        if min(records_out[0].shape[0], records_out[1].shape[0]) < primary_rows:
+            raise ValueError("proposal_merge_blocks: records_out needs primary_rows=%d rows" % primary_rows)
+    for t in (m_out, overflow_out):
+        if t is not None:
+            _chk(t, "m_out / overflow_out", torch.int32)
+    rows_b, cams_b, cnt_host, cnt_dev, ovf = [], [], [], [], []
+    for b in blocks:
+        r, c, x, s = b["rows"]
+        n = min(r.shape[0], c.shape[0], x.shape[0], s.shape[0])
+        _chk(b["sel_cnt"], "block sel_cnt", torch.int32, 1)
+        if r.stride(0) != 3 or c.stride(0) != C + 1 or c.shape[1] != C + 1 or not (x.is_contiguous() and s.is_contiguous()):
+            raise ValueError("proposal_merge_blocks: a block's ref2d / ctx / box2d / score must be dense rows of the frame's widths")
+        if md:
+            f, i = b["records"]
+            _chk(f, "block md_flags", torch.int32, 1)
+            _chk(i, "block md_info", torch.int32, 2)
+            if i.shape[1] != 2 * topk:
+                raise ValueError("proposal_merge_blocks: a block's md_info has %d columns, the frame's %d" % (i.shape[1], 2 * topk))
+            n = min(n, f.shape[0], i.shape[0])
+        cnt = b.get("count")
+        if isinstance(cnt, torch.Tensor):
+            _chk(cnt, "block count", torch.int32)
+        if b.get("overflow") is not None:
+            _chk(b["overflow"], "block overflow", torch.int32)
+        rows_b.append(n)
+        cams_b.append(b["sel_cnt"].shape[0])
+        cnt_dev.append(cnt.data_ptr() if isinstance(cnt, torch.Tensor) else None)
+        cnt_host.append(-1 if cnt is None or isinstance(cnt, torch.Tensor) else int(cnt))
+        ovf.append(b["overflow"].data_ptr() if b.get("overflow") is not None else None)
+    pa = lambda vals: (ctypes.c_void_p * nb)(*vals)
+    arr = [_ptr_array([b["rows"][k] for b in blocks]) for k in range(4)]
+    rec = [_ptr_array([b["records"][k] for b in blocks]) if md else None for k in range(2)]
+    hk, hp = _host_i32(cnt_host)
+    fk, fp = _host_i32([int(b["first_cam"]) for b in blocks])
+    ck, cp = _host_i32(cams_b)
+    rk, rp = _host_i32(rows_b)
+    _lib.check(lib.far3d_proposal_merge_blocks(nb, arr[0], arr[1], arr[2], arr[3], rec[0], rec[1], _ptr_array([b["sel_cnt"] for b in blocks]),
+                                               pa(cnt_dev), hp, pa(ovf), fp, cp, rp, sel_cnt_out.shape[0], C, topk, int(primary_rows),
+                                               int(rows_total), _ptr(ref2d), _ptr(ctx), _ptr(box2d), _ptr(score),
+                                               _ptr(records_out[0]) if md else None, _ptr(records_out[1]) if md else None,
+                                               _ptr(sel_cnt_out), _ptr(m_out) if m_out is not None else None,
+                                               _ptr(overflow_out) if overflow_out is not None else None, _stream(ctx)),
+               "far3d_proposal_merge_blocks")
+    return ref2d, ctx, box2d, score
+
+
 def compact_rows(src, counts, dst, m_out, overflow_out):
     """src (nblocks, rows_per_block, D) f32 with counts[b] valid rows in block b -> dst (dst_rows, D): the valid rows in block order,
     the rest zero; m_out = min(sum counts, dst_rows); overflow_out |= (sum counts > dst_rows).  One launch, no sync."""

@@ -436,6 +436,31 @@ int far3d_proposal_extra_rows(const int* sel_cnt, int N, int sel_cap, int primar
                               const float* pc_range, int C, float* ref2d, float* ctx, float* box2d, float* score, int rows_total,
                               int fill_hole, int32_t* m_out, int32_t* overflow_out, void* stream);
 
+/* Proposals of camera BLOCKS -> the frame's layout (far3d_amd/csrc/md_blocks.hip).  nblocks (1 .. 16) blocks in ascending camera
+ * order, block b = cameras [first_cam[b], first_cam[b] + block_cams[b]) (contiguous, together all N), each processed on its own by
+ * far3d_proposal_gather / far3d_proposal_gather_md into its own buffers of block_rows[b] rows, whose rows [0, count_b) hold its
+ * primaries camera-major.  ref2d / ctx / box2d / score / md_flags / md_info / sel_cnt / count_dev / overflow are HOST arrays of
+ * nblocks DEVICE pointers; count_b = *count_dev[b] when that pointer is given, else count_host[b] when count_host is given and
+ * >= 0 (static top-K), else min(sum sel_cnt of the block, block_rows[b]) (what far3d_proposal_gather_md kept; a sum above
+ * block_rows[b] counts as that block's overflow flag); it is clamped to [0, block_rows[b]].  count_dev, count_host, overflow and their entries may be NULL.
+ * Writes, with Mp = min(sum count_b, primary_rows): rows [0, Mp) of the frame's o_ref2d (rows_total,3), o_ctx (rows_total,C+1),
+ * o_box2d (rows_total,4), o_score (rows_total) = the blocks' rows back to back; o_sel_cnt (N) = the blocks' sel_cnt;
+ * *m_out = Mp; *overflow_out = OR of the blocks' flags | (sum count_b > primary_rows) (both optional).
+ * Records given (md_flags, md_info, o_md_flags (primary_rows), o_md_info (primary_rows, 2 topk) all non-NULL; multi-depth): rows
+ * [0, Mp) of the records too, the camera field of md_info rebased by first_cam[b]; rows [Mp, rows_total) are NOT touched -- run
+ * far3d_proposal_extra_rows next, which writes the extra rows, M', the final flag and the hole.  Records NULL (single depth): rows
+ * [Mp, rows_total) are zero-filled, the result is that of far3d_proposal_gather(rows_total) on all cameras.
+ * Equal to the all-camera call bit for bit when block_rows[b] >= min(primary_rows, block_cams[b] * cap).  One launch whose grid
+ * depends on the static sizes only; no atomics, no order between workgroups, no host sync.  The frame's buffers must not overlap a
+ * block's. */
+int far3d_proposal_merge_blocks(int nblocks, const float* const* ref2d, const float* const* ctx, const float* const* box2d,
+                                const float* const* score, const int32_t* const* md_flags, const int32_t* const* md_info,
+                                const int32_t* const* sel_cnt, const int32_t* const* count_dev, const int32_t* count_host,
+                                const int32_t* const* overflow, const int32_t* first_cam, const int32_t* block_cams,
+                                const int32_t* block_rows, int N, int C, int topk, int primary_rows, int rows_total,
+                                float* o_ref2d, float* o_ctx, float* o_box2d, float* o_score, int32_t* o_md_flags,
+                                int32_t* o_md_info, int32_t* o_sel_cnt, int32_t* m_out, int32_t* overflow_out, void* stream);
+
 /* Blocks of rows -> one compact run (camera-sharded fixed-capacity mode): src (nblocks, rows_per_block, D) f32 of which the first
  * counts[b] rows of block b are valid; dst (dst_rows, D): rows [0, M) the valid rows in block order, the rest zero,
  * *m_out = M = min(sum counts, dst_rows); *overflow_out is OR-ed with (sum counts > dst_rows) (initialise it). */
