@@ -41,10 +41,12 @@ def load_config(path):
 
 
 def default_model_cfg(num_cams=7, num_query=644, num_propagated=256, memory_len=1024, topk_proposals=256, backbone="V-99-eSE",
-                      proposal_topk=None, proposal_capacity=None, multi_depth_config=None):
+                      proposal_topk=None, proposal_capacity=None, multi_depth_config=None, use_depthwise=False, reg_depth_level="p3"):
     """The Far3D VoV-99 Argoverse-2 model (values of the reference's only config), assembled programmatically.
     multi_depth_config: overrides the head's dict(topk=1, range_min=30) (e.g. topk=2: multi-depth 2D proposals).
-    backbone: a VoVNet spec name; the FPN's in_channels are that spec's stage widths."""
+    backbone: a VoVNet spec name; the FPN's in_channels are that spec's stage widths.
+    use_depthwise / reg_depth_level: the 2D head's light options (yolox_head.py:197-219, :300-301): depthwise-separable towers, and the
+    FPN level ('p3' | 'p4' | 'p5') the depth branch reads.  The reference's config sets neither (dense towers, 'p3')."""
     from .weights import VOV_SPECS
     depthnet = dict(type=0, hidden_dim=256, num_depth_bins=50, depth_min=0.1, depth_max=110, stride=8)
     strides = [8, 16, 32, 64]
@@ -63,7 +65,8 @@ def default_model_cfg(num_cams=7, num_query=644, num_propagated=256, memory_len=
                 bbox_coder=dict(type="NMSFreeCoder", post_center_range=POINT_CLOUD_RANGE, pc_range=POINT_CLOUD_RANGE, max_num=300,
                                 voxel_size=[0.2, 0.2, 8], num_classes=26))
     roi = dict(type="YOLOXHeadCustom", num_classes=26, in_channels=256, strides=strides, pred_with_depth=True,
-               depthnet_config=depthnet, reg_depth_level="p3", sample_with_score=True, threshold_score=0.1, topk_proposal=None,
+               depthnet_config=depthnet, reg_depth_level=reg_depth_level, use_depthwise=bool(use_depthwise), sample_with_score=True,
+               threshold_score=0.1, topk_proposal=None,
                return_context_feat=True)
     return dict(type="Far3D", use_grid_mask=True, stride=strides, position_level=[0, 1, 2, 3],
                 img_backbone=dict(type="VoVNet", spec_name=backbone, norm_eval=True, frozen_stages=-1, input_ch=3,

@@ -126,4 +126,9 @@ __device__ __forceinline__ void store4(pair_t* p, const float4& v) {
   *reinterpret_cast<uint2*>(p + 32) = l;
 }
 
+// Swish / SiLU on an fp32 value with full-precision expf and division -- the statement the conv epilogues write out for their fp32 / pair
+// outputs (igemm_kernels.hpp, conv_ws.hpp: v * (1.f / (1.f + expf(-v))); their bf16-output branches use the hardware exp2 / rcp instead).
+// far3d_dwconv3x3_act_nhwc takes it from here, so a depthwise tower layer rounds like a dense one.
+__device__ __forceinline__ float swish_f32(float v) { return v * (1.f / (1.f + expf(-v))); }
+
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }

@@ -72,6 +72,10 @@ def default_cfg(**over):
         # value drops extras past it in reference order, reported by check_proposal_overflow().  The legacy threshold mode sizes
         # them from its selection capacity and ignores this.
         multi_depth_capacity=None,
+        # the light 2D head (ref yolox_head.py:197-219, :300-301).  roi_depthwise: the towers are depthwise-separable (use_depthwise=True:
+        # depthwise 3x3 + BN + Swish, pointwise 1x1 + BN + Swish per layer).  depth_level: the FPN level the depth branch reads
+        # (reg_depth_level p3 / p4 / p5 = 0 / 1 / 2); the proposals take the depth map's stride from strides[depth_level]
+        roi_depthwise=False, depth_level=0,
     )
     cfg.update(over)
     return cfg
@@ -203,6 +207,15 @@ class Far3DEngine:
         self.mem = None
         self.prev_scene = None
         self.md_k = multi_depth_topk(self.cfg)
+        self.roi_dw = bool(self.cfg.get("roi_depthwise", False))
+        self.depth_level = int(self.cfg.get("depth_level", 0) or 0)
+        if not 0 <= self.depth_level < len(self.cfg["strides"]):
+            raise ValueError("depth_level %d is outside the %d levels of strides %s" % (self.depth_level, len(self.cfg["strides"]), self.cfg["strides"]))
+        self.depth_stride = self.cfg["strides"][self.depth_level]     # the reference derives it from the map's size (farhead.py:722)
+        self.roi_dw_merged = False  # light towers: True = both towers' first depthwise layers as ONE two-set launch (one read of the level map).
+                                    # Measured slower than two single-set launches (profiles/light_head/README.md: 142 vs 123 us in bf16, 155
+                                    # vs 147 us pair-stored on the 7x80x120x256 map -- two weight sets cost the kernel its second wave per
+                                    # SIMD), so the default issues two launches; bit-identical either way
         self.md_min_bin = (ops.depth_range_min_bin(self.cfg["depthnet"], (self.cfg.get("multi_depth") or {}).get("range_min", -1))
                            if self.md_k > 1 else None)
         self._prepare()
@@ -295,14 +308,28 @@ class Far3DEngine:
         self.roi = []
         for l in range(len(cfg["strides"])):
             lv = {}
-            for t in ("cls", "reg"):
-                lv[t] = [self._pack(*self._conv_bn(r + "multi_level_%s_convs.%d.%d" % (t, l, i), conv=".conv", norm=".bn", eps=1e-3),
-                                    name="roi%d.%s1" % (l, t) if i == 1 else None) for i in range(2)]
-            # the two towers' first convs read the same map: one 256 -> 512 conv (cls channels first), half the launches and
-            # twice the workgroups on the small levels
-            wc, bc, _, _ = self._conv_bn(r + "multi_level_cls_convs.%d.0" % l, conv=".conv", norm=".bn", eps=1e-3)
-            wr, br, _, _ = self._conv_bn(r + "multi_level_reg_convs.%d.0" % l, conv=".conv", norm=".bn", eps=1e-3)
-            lv["tower0"] = self._pack(torch.cat([wc, wr]), torch.cat([bc, br]), 1, 1, name="roi%d.tower0" % l)
+            if self.roi_dw:
+                # depthwise-separable towers: per layer the folded depthwise (9,C) weights + bias (ops.dwconv3x3_act_nhwc, Swish) and the
+                # pointwise 1x1 with its BN folded ('roi<l>.<tower><i>.pw', Swish in the GEMM's epilogue)
+                for t in ("cls", "reg"):
+                    lv[t] = []
+                    for i in range(2):
+                        p = r + "multi_level_%s_convs.%d.%d" % (t, l, i)
+                        w, b, _, _ = self._conv_bn(p, conv=".depthwise_conv.conv", norm=".depthwise_conv.bn", eps=1e-3)
+                        pw = self._pack(*self._conv_bn(p, conv=".pointwise_conv.conv", norm=".pointwise_conv.bn", eps=1e-3, pad=0),
+                                        name="roi%d.%s%d.pw" % (l, t, i))
+                        lv[t].append(dict(dw=ops.pack_dw3x3_sets([w], [b], dev), w=w, b=b, pw=pw))
+                # both towers' first depthwise layers read the same map: packed as one two-set operand (cls channels first) for roi_dw_merged
+                lv["dw0"] = ops.pack_dw3x3_sets([lv["cls"][0]["w"], lv["reg"][0]["w"]], [lv["cls"][0]["b"], lv["reg"][0]["b"]], dev)
+            else:
+                for t in ("cls", "reg"):
+                    lv[t] = [self._pack(*self._conv_bn(r + "multi_level_%s_convs.%d.%d" % (t, l, i), conv=".conv", norm=".bn", eps=1e-3),
+                                        name="roi%d.%s1" % (l, t) if i == 1 else None) for i in range(2)]
+                # the two towers' first convs read the same map: one 256 -> 512 conv (cls channels first), half the launches and
+                # twice the workgroups on the small levels
+                wc, bc, _, _ = self._conv_bn(r + "multi_level_cls_convs.%d.0" % l, conv=".conv", norm=".bn", eps=1e-3)
+                wr, br, _, _ = self._conv_bn(r + "multi_level_reg_convs.%d.0" % l, conv=".conv", norm=".bn", eps=1e-3)
+                lv["tower0"] = self._pack(torch.cat([wc, wr]), torch.cat([bc, br]), 1, 1, name="roi%d.tower0" % l)
             lv["cls_head"] = self._pack(sd[r + "multi_level_conv_cls.%d.weight" % l], sd[r + "multi_level_conv_cls.%d.bias" % l], name="roi%d.cls_head" % l)
             lv["reg_head"] = self._pack(torch.cat([sd[r + "multi_level_conv_reg.%d.weight" % l], sd[r + "multi_level_conv_obj.%d.weight" % l]]),
                                         torch.cat([sd[r + "multi_level_conv_reg.%d.bias" % l], sd[r + "multi_level_conv_obj.%d.bias" % l]]),
@@ -610,25 +637,46 @@ class Far3DEngine:
         npix = d.shape[0] * d.shape[1] * d.shape[2]
         gt0 = ops.group_tile("roi.tower0", npix) if self.pair else 0
         gt1 = ops.group_tile("roi.cls1reg1", npix) if self.pair else 0
-        if gt0 and gt1 and centers2d is None and self._roi_groupable(raw):
+        light = self.roi_dw or self.depth_level != 0      # the grouped launches cover the dense towers with the depth branch on p3 only
+        if gt0 and gt1 and centers2d is None and not light and self._roi_groupable(raw):
             return self._roi_head_grouped(raw, gt0, gt1)
         cls, reg = [], []
         for l, x in enumerate(raw):
             lv = self.roi[l]
-            t0 = ops.conv2d_nhwc(x, lv["tower0"], act="swish")                 # (N,h,w,512): cls | reg
-            half = t0.shape[-1] // 2
-            cf = ops.conv2d_nhwc(t0[..., :half], lv["cls"][1], act="swish")
+            if self.roi_dw:
+                cf, rf = self._light_towers(x, lv)
+            else:
+                t0 = ops.conv2d_nhwc(x, lv["tower0"], act="swish")                 # (N,h,w,512): cls | reg
+                half = t0.shape[-1] // 2
+                cf = ops.conv2d_nhwc(t0[..., :half], lv["cls"][1], act="swish")
+                rf = ops.conv2d_nhwc(t0[..., half:], lv["reg"][1], act="swish")
             cls.append(ops.conv2d_nhwc(cf, lv["cls_head"], out_dtype=torch.float32))
-            rf = ops.conv2d_nhwc(t0[..., half:], lv["reg"][1], act="swish")
             reg.append(ops.conv2d_nhwc(rf, lv["reg_head"], out_dtype=torch.float32))
             if centers2d is not None:
                 centers2d.append(ops.conv2d_nhwc(rf, lv["ctr_head"], out_dtype=torch.float32))
-        d = raw[0]
+        d = raw[self.depth_level]
         gscr = self._buf(("gn_scratch",), (ops.ese_scratch_floats(d.shape[0], d.shape[-1] // self.cs),), torch.float32)
         for i in range(2):
             d = ops.conv2d_nhwc(d, self.depth["convs"][i])
             d = ops.groupnorm_nhwc(d, *self.depth["gn"][i], groups=32, relu=True, scratch=gscr, pair=self.pair)
         return cls, reg, ops.conv2d_nhwc(d, self.depth["cls"], out_dtype=torch.float32)
+
+    def _light_towers(self, x, lv):
+        """The depthwise-separable cls and reg towers of one level (yolox_head.py:197-219) on the NHWC map x -> (cls feature, reg feature).
+        Per tower and layer: far3d_dwconv3x3_act_nhwc (folded BN bias + Swish), then the pointwise 1x1 + BN + Swish.  Layer 0 of both towers
+        reads x: with roi_dw_merged their depthwise halves are one two-set launch (cls channels first), otherwise two single-set launches."""
+        if self.roi_dw_merged:
+            t0 = ops.dwconv3x3_act_nhwc(x, lv["dw0"][0], 1, bias=lv["dw0"][1], act="swish", pair=self.pair)      # (N,h,w,2C): cls | reg
+            half = t0.shape[-1] // 2
+            t0 = (t0[..., :half], t0[..., half:])
+        else:
+            t0 = tuple(ops.dwconv3x3_act_nhwc(x, lv[t][0]["dw"][0], 1, bias=lv[t][0]["dw"][1], act="swish", pair=self.pair) for t in ("cls", "reg"))
+        out = []
+        for t, h in zip(("cls", "reg"), t0):
+            f = ops.conv2d_nhwc(h, lv[t][0]["pw"], act="swish")
+            f = ops.dwconv3x3_act_nhwc(f, lv[t][1]["dw"][0], 1, bias=lv[t][1]["dw"][1], act="swish", pair=self.pair)
+            out.append(ops.conv2d_nhwc(f, lv[t][1]["pw"], act="swish"))
+        return out
 
     def _roi_groupable(self, raw):
         if 2 * len(raw) + 1 > ops.GROUP_MAX:
@@ -945,7 +993,7 @@ class Far3DEngine:
             rec = (self._buf(("md_flags",), (prim,), torch.int32), self._buf(("md_info",), (prim, 2 * Kmd), torch.int32))
             i2l = self._buf(("md_i2l",), tuple(img2lidar.shape), torch.float32)
             i2l.copy_(img2lidar)
-            ops.proposal_gather_md(reg, cfg["strides"], sel_idx, sel_cnt, wgt, depth_logit, cfg["depthnet"]["stride"], cfg["depthnet"],
+            ops.proposal_gather_md(reg, cfg["strides"], sel_idx, sel_cnt, wgt, depth_logit, self.depth_stride, cfg["depthnet"],
                                    img2lidar, tokens, cfg["pc_range"], Kmd, self.md_min_bin, rec, out,
                                    primary_rows=prim if capT is not None else 0, score_thr=0.1)
             md = dict(records=rec, img2lidar=i2l, primary_rows=prim, sel_cap=cap if capT is not None else 0, rows=rows)
@@ -953,7 +1001,7 @@ class Far3DEngine:
                         peak_weight=wgt, m_dev=m_dev, overflow=ovf, md=md)
         # the log-odds threshold is the reference's hard-coded 0.1 (farhead.py:577), not cfg score_thr
         ref2d, ctx, box2d, score2d = ops.proposal_gather(reg, cfg["strides"], sel_idx, sel_cnt, wgt, depth_logit,
-                                                         cfg["depthnet"]["stride"], cfg["depthnet"], img2lidar, tokens,
+                                                         self.depth_stride, cfg["depthnet"], img2lidar, tokens,
                                                          cfg["pc_range"], score_thr=0.1, out=out, rows_total=rows if capT is not None else 0,
                                                          m_out=m_dev, overflow_out=ovf)
         return dict(ref2d=ref2d, ctx=ctx, box2d=box2d, score2d=score2d, sel_idx=sel_idx, sel_cnt=sel_cnt, depth_logit=depth_logit, peak_weight=wgt,

@@ -1014,6 +1014,61 @@ def dwconv3x3_nhwc(x, w9c, stride, out=None, pair=False):
     return out
 
 
+DW_ACTS = {None: 0, "none": 0, "relu": 1, "swish": 2}
+
+
+def pack_dw3x3_sets(weights, biases=None, device=None):
+    """One or two depthwise layers of the same width -> far3d_dwconv3x3_act_nhwc's operands: (reps, 9, C) f32 weights (pack_dw3x3 per
+    set) and the (reps, C) f32 biases (None: no bias).  weights: a list of (C,1,3,3) tensors; biases: a list of (C,) tensors."""
+    w = torch.stack([pack_dw3x3(wi) for wi in weights]).contiguous()
+    b = None if biases is None else torch.stack([bi.detach().float() for bi in biases]).contiguous()
+    if b is not None and tuple(b.shape) != (w.shape[0], w.shape[2]):
+        raise ValueError("pack_dw3x3_sets: biases %s do not match weights %s" % (tuple(b.shape), tuple(w.shape)))
+    if device is not None:
+        w, b = w.to(device), (None if b is None else b.to(device))
+    return w, b
+
+
+def dwconv3x3_act_nhwc(x, w, stride, bias=None, act=None, out=None, pair=False):
+    """dwconv3x3_nhwc with a bias, an activation and one or two weight sets per window: out[..., r*C + c] = act(dw(x[..., c]; w[r]) + bias[r][c]).
+    w: (reps, 9, C) f32 (a (9, C) tensor is one set), reps 1 or 2; bias: (reps, C) f32 or None; act: None | "relu" | "swish" (or the
+    library's code 0 / 1 / 2).  out: optional NHWC view of x's storage with reps*C logical channels.  With reps = 1, no bias and no
+    activation the result is dwconv3x3_nhwc's, bit for bit.  Sizes, strides, alignment, reps and act are checked by the library
+    (Far3dHipError, nothing launched)."""
+    lib = _lib.require_device()
+    N, H, W, Cs = x.shape
+    C = Cs // 2 if pair else Cs
+    if pair and x.dtype != torch.bfloat16:
+        raise TypeError("dwconv3x3_act_nhwc: pair storage is bf16")
+    if w.dim() == 2:
+        w = w[None]
+    _chk(w, "w", torch.float32, 3)
+    reps = w.shape[0]
+    if tuple(w.shape[1:]) != (9, C):
+        raise ValueError("dwconv3x3_act_nhwc: weights %s != (reps, 9, %d)" % (tuple(w.shape), C))
+    if bias is not None:
+        if bias.dim() == 1:
+            bias = bias[None]
+        _chk(bias, "bias", torch.float32, 2)
+        if tuple(bias.shape) != (reps, C):
+            raise ValueError("dwconv3x3_act_nhwc: bias %s != (%d, %d)" % (tuple(bias.shape), reps, C))
+    code = DW_ACTS[act] if (act is None or isinstance(act, str)) else int(act)
+    ldx, xs = _nhwc_view(x, "x")
+    if out is None:
+        s = int(stride)
+        if s < 1:
+            raise ValueError("dwconv3x3_act_nhwc: stride %r" % (stride,))
+        out = torch.empty((N, (H - 1) // s + 1, (W - 1) // s + 1, max(reps, 1) * Cs), dtype=x.dtype, device=x.device)
+    if out.dtype != x.dtype or out.shape[0] != N or out.shape[3] != reps * Cs:
+        raise ValueError("dwconv3x3_act_nhwc: out %s %s does not match x %s %s with %d weight sets" %
+                         (tuple(out.shape), out.dtype, tuple(x.shape), x.dtype, reps))
+    ldy, ys = _nhwc_view(out, "out")
+    _lib.check(lib.far3d_dwconv3x3_act_nhwc(_ptr(x), DT_BF16_PAIR if pair else _dt(x), _ptr(w), _ptr(bias) if bias is not None else None,
+                                            _ptr(out), N, H, W, C, ldx, xs, out.shape[1], out.shape[2], ldy, ys, int(stride), int(reps), code,
+                                            _stream(x)), "far3d_dwconv3x3_act_nhwc")
+    return out
+
+
 # --------------------------------------------------------------------------------------------------
 # front-end glue: stem im2col, 2D proposals, MLN apply
 # --------------------------------------------------------------------------------------------------

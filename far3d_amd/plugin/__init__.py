@@ -389,21 +389,41 @@ class YOLOXHeadCustom(_SchemaModule):
     """models/dense_heads/yolox_head.py:25-519 (inference members; parameter holder, computed inside Far3D)."""
     prefix = "img_roi_head."
 
-    def __init__(self, num_classes, in_channels, feat_channels=256, stacked_convs=2, strides=(8, 16, 32), pred_with_depth=False,
-                 depthnet_config=None, reg_depth_level="p4", sample_with_score=True, threshold_score=0.05, topk_proposal=None,
-                 return_context_feat=False, train_cfg=None, test_cfg=None, **kwargs):
+    def __init__(self, num_classes, in_channels, feat_channels=256, stacked_convs=2, strides=(8, 16, 32), use_depthwise=False,
+                 dcn_on_last_conv=False, pred_with_depth=False, depthnet_config=None, reg_depth_level="p4", pred_depth_var=False,
+                 embedding_cam=False, sample_with_score=True, threshold_score=0.05, topk_proposal=None, return_context_feat=False,
+                 train_cfg=None, test_cfg=None, **kwargs):
         super().__init__()
-        assert pred_with_depth and reg_depth_level == "p3" and stacked_convs == 2 and feat_channels == in_channels, \
+        assert pred_with_depth and stacked_convs == 2 and feat_channels == in_channels, \
             "only the reference's 2D-head configuration is implemented"
-        self.num_classes, self.strides, self.depthnet_config = num_classes, list(strides), dict(depthnet_config or {})
+        # options that change the arithmetic and are not built: refused by name (they used to vanish into **kwargs)
+        dn = dict(depthnet_config or {})
+        refused = [("embedding_cam", bool(embedding_cam)), ("pred_depth_var", bool(pred_depth_var)), ("dcn_on_last_conv", bool(dcn_on_last_conv)),
+                   ("depthnet_config.multi_level_pred", bool(dn.get("multi_level_pred", False))),
+                   ("depthnet_config.multi_level_fusion", bool(dn.get("multi_level_fusion", False))),
+                   ("depthnet_config.type", dn.get("type", 0) != 0),
+                   ("depthnet_config.conv_layer_num", dn.get("conv_layer_num", 2) != 2)]
+        for name, on in refused:
+            if on:
+                raise NotImplementedError("YOLOXHeadCustom: %s is not implemented by far3d_amd (it changes the head's arithmetic; "
+                                          "INTEGRATION.md section 3 lists the options that are)" % name)
+        levels = {"p3": 0, "p4": 1, "p5": 2}
+        if reg_depth_level not in levels:
+            raise ValueError("YOLOXHeadCustom: reg_depth_level %r (one of p3, p4, p5)" % (reg_depth_level,))
+        if levels[reg_depth_level] >= len(strides):
+            raise ValueError("YOLOXHeadCustom: reg_depth_level %r needs FPN level %d, but strides %s has %d levels" %
+                             (reg_depth_level, levels[reg_depth_level], list(strides), len(strides)))
+        self.use_depthwise, self.reg_depth_level, self.depth_level = bool(use_depthwise), reg_depth_level, levels[reg_depth_level]
+        self.num_classes, self.strides, self.depthnet_config = num_classes, list(strides), dn
         self.sample_with_score, self.threshold_score, self.topk_proposal = sample_with_score, threshold_score, topk_proposal
         full = weights.detector_spec(num_classes=num_classes, embed=in_channels, fpn_levels=len(strides),
-                                     depth_bins=self.depthnet_config.get("num_depth_bins", 50))
+                                     depth_bins=self.depthnet_config.get("num_depth_bins", 50), roi_depthwise=self.use_depthwise,
+                                     depth_level=self.depth_level)
         self._init_schema(full)
 
     def _engine_for(self, dev):
         cfg = _engine.default_cfg(num_classes=self.num_classes, strides=tuple(self.strides), score_thr=self.threshold_score,
-                                  proposal_topk=self.topk_proposal,
+                                  proposal_topk=self.topk_proposal, roi_depthwise=self.use_depthwise, depth_level=self.depth_level,
                                   depthnet=dict(num_depth_bins=self.depthnet_config.get("num_depth_bins", 50),
                                                 depth_min=self.depthnet_config.get("depth_min", 0.1),
                                                 depth_max=self.depthnet_config.get("depth_max", 110.0),
@@ -426,7 +446,7 @@ class YOLOXHeadCustom(_SchemaModule):
                    pred_centers2d_offset=[_to_nchw(c) for c in ctr], objectnesses=[_to_nchw(r[..., 4:5]) for r in reg],
                    topk_indexes=None, depth_logit=_to_nchw(depth_logit))
         out["pred_depth"] = out["depth_logit"].softmax(dim=1)
-        out["_far3d"] = dict(cls=cls, reg=reg, depth_logit=depth_logit)
+        out["_far3d"] = dict(cls=cls, reg=reg, depth_logit=depth_logit, depth_stride=eng.depth_stride)
         return out
 
     @torch.no_grad()
@@ -451,7 +471,7 @@ class YOLOXHeadCustom(_SchemaModule):
         # 2D boxes: the gather kernel decodes them (identity img2lidar / dummy tokens: only box2d and score are read here)
         eye = torch.eye(4, device=dev)[None].repeat(n, 1, 1).contiguous()
         tok = torch.zeros((n, S, cfg["embed_dims"]), device=dev)
-        _, _, box2d, score2d = ops.proposal_gather(st["reg"], cfg["strides"], sel_idx, sel_cnt, wgt, st["depth_logit"], cfg["depthnet"]["stride"],
+        _, _, box2d, score2d = ops.proposal_gather(st["reg"], cfg["strides"], sel_idx, sel_cnt, wgt, st["depth_logit"], eng.depth_stride,
                                                    cfg["depthnet"], eye, tok, cfg["pc_range"], score_thr=0.1)
         M = sum(cnt)
         off = [0]
@@ -547,6 +567,7 @@ class FarHead(_SchemaModule):
                 ops.row_affine_ln(x[n].view(-1, E), gamma[n:n + 1], beta[n:n + 1], do_ln=False,
                                   out=tokens[n, starts[l]:starts[l] + hw[l][0] * hw[l][1]])
         tokens = tokens.to(eng.prec["value"])
+        dstride = st.get("depth_stride", eng.depth_stride)     # the stride of the level the 2D head's depth branch read (farhead.py:722)
         if eng.md_k > 1:
             # multi-depth proposals (farhead.py:754-805): primaries + records, then the extra rows; one sync on M' like the reference's
             n, cap = st["sel_idx"].shape
@@ -556,7 +577,7 @@ class FarHead(_SchemaModule):
             rec = (torch.empty((n * cap,), dtype=torch.int32, device=dev), torch.empty((n * cap, 2 * K), dtype=torch.int32, device=dev))
             m_dev = torch.empty((1,), dtype=torch.int32, device=dev)
             ops.proposal_gather_md(st["reg"], eng.cfg["strides"], st["sel_idx"], st["sel_cnt"], st["peak_weight"], st["depth_logit"],
-                                   eng.cfg["depthnet"]["stride"], eng.cfg["depthnet"], img2lidar, tokens, eng.cfg["pc_range"], K,
+                                   dstride, eng.cfg["depthnet"], img2lidar, tokens, eng.cfg["pc_range"], K,
                                    eng.md_min_bin, rec, pr)
             ops.proposal_extra_rows(st["sel_cnt"], 0, n * cap, K, rec, img2lidar, eng.cfg["depthnet"], eng.cfg["pc_range"], pr,
                                     fill_hole=False, m_out=m_dev)
@@ -564,7 +585,7 @@ class FarHead(_SchemaModule):
         else:
             M = int(st["sel_cnt"].sum().item())
             pr = ops.proposal_gather(st["reg"], eng.cfg["strides"], st["sel_idx"], st["sel_cnt"], st["peak_weight"], st["depth_logit"],
-                                     eng.cfg["depthnet"]["stride"], eng.cfg["depthnet"], img2lidar, tokens, eng.cfg["pc_range"], score_thr=0.1)
+                                     dstride, eng.cfg["depthnet"], img2lidar, tokens, eng.cfg["pc_range"], score_thr=0.1)
         pad_hw = tuple(img_metas[0]["pad_shape"][0][:2])
         outs = eng.head_stage(tokens, pr[0], pr[1], M, dd, img_metas, hw, starts, pad_hw)
         self.last_outs = outs
@@ -634,7 +655,7 @@ class Far3D(nn.Module):
             depthnet=dict(num_depth_bins=r.depthnet_config.get("num_depth_bins", 50), depth_min=r.depthnet_config.get("depth_min", 0.1),
                           depth_max=r.depthnet_config.get("depth_max", 110.0), stride=r.depthnet_config.get("stride", 8)),
             score_thr=r.threshold_score, proposal_topk=self.proposal_topk, proposal_capacity=self.proposal_capacity,
-            multi_depth=dict(h.multi_depth_config))
+            multi_depth=dict(h.multi_depth_config), roi_depthwise=r.use_depthwise, depth_level=r.depth_level)
 
     def prepare(self, device="cuda:0", precision="bf16"):
         """Fold BN, pack weights for the kernels, upload.  Must be called again after loading new weights."""

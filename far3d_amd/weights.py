@@ -95,7 +95,14 @@ def backbone_spec(spec_name, input_ch=3):
 
 
 def detector_spec(backbone="V-99-eSE", num_query=644, num_propagated=256, num_classes=26, embed=256, num_layers=6,
-                  num_levels=4, num_pts=13, num_groups=8, ffn_dim=1024, code_size=8, depth_bins=50, fpn_levels=4):
+                  num_levels=4, num_pts=13, num_groups=8, ffn_dim=1024, code_size=8, depth_bins=50, fpn_levels=4, roi_depthwise=False,
+                  depth_level=0):
+    """roi_depthwise: the 2D head's towers as the reference builds them with use_depthwise=True (yolox_head.py:197-219): every tower
+    layer is mmcv 1.6.2's DepthwiseSeparableConvModule -- `depthwise_conv` (ConvModule: conv (C,1,3,3) without bias, bn, Swish) then
+    `pointwise_conv` (ConvModule: conv (C,C,1,1) without bias, bn, Swish).  (mmcv's source is not vendored: the structure is recalled,
+    see INTEGRATION.md §3.)  depth_level: the FPN level the depth branch reads (reg_depth_level p3 / p4 / p5 = 0 / 1 / 2); it changes no key."""
+    if not 0 <= int(depth_level) < fpn_levels:
+        raise ValueError("depth_level %s is outside the %d FPN levels" % (depth_level, fpn_levels))
     s = VOV_SPECS[backbone]
     spec = backbone_spec(backbone)
     fin = s["stage_out_ch"][1:]
@@ -169,6 +176,12 @@ def detector_spec(backbone="V-99-eSE", num_query=644, num_propagated=256, num_cl
         for t in ("cls", "reg"):
             for i in range(2):
                 p = r + "multi_level_%s_convs.%d.%d." % (t, l, i)
+                if roi_depthwise:
+                    spec[p + "depthwise_conv.conv.weight"] = (embed, 1, 3, 3)
+                    _bn(spec, p + "depthwise_conv.bn", embed)
+                    spec[p + "pointwise_conv.conv.weight"] = (embed, embed, 1, 1)
+                    _bn(spec, p + "pointwise_conv.bn", embed)
+                    continue
                 spec[p + "conv.weight"] = (embed, embed, 3, 3)
                 _bn(spec, p + "bn", embed)
         for n, o in (("cls", num_classes), ("reg", 4), ("obj", 1), ("centers2d", 2)):

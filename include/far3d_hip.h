@@ -367,6 +367,18 @@ int far3d_maxpool3x3s2_nhwc(const void* x, int dt, void* y, int N, int H, int W,
 int far3d_dwconv3x3_nhwc(const void* x, int dt, const float* w, void* y, int N, int H, int W, int C, int ldx, long x_img_stride,
                          int Ho, int Wo, int ldy, long y_img_stride, int stride, void* stream);
 
+/* far3d_dwconv3x3_nhwc with a bias, an activation and one or two weight sets per window: the depthwise half of mmcv's
+ * DepthwiseSeparableConvModule (conv + BN + activation, BN folded by the caller) as the light YOLOX towers use it
+ * (ref models/dense_heads/yolox_head.py:197-219).  y[..., r*C + c] = act(dw(x[..., c]; w[r]) + bias[r][c]) for r < reps: the output map
+ * has reps*C logical channels (ldy >= reps*C stored channels), and with reps = 2 both towers' first layers read their common FPN map once.
+ * Operand rules of far3d_dwconv3x3_nhwc (storage, C % 8 / C % 32, pad 1, stride 1 or 2, 16-byte alignment, no overlap).
+ * w: [reps][9][C] f32; bias: [reps][C] f32 or NULL; reps: 1 or 2; act: 0 none / 1 ReLU / 2 Swish (x * sigmoid(x), full-precision expf).
+ * Arithmetic: the nine pinned fmas of far3d_dwconv3x3_nhwc in its tap order, then one fp32 add of the bias (none when bias is NULL), then
+ * the activation -- the bits of an output element depend on its own window, weights and bias only, never on N, the launch's other pixels
+ * or reps; reps = 1, bias = NULL, act = 0 returns far3d_dwconv3x3_nhwc's bits.  Bad arguments return FAR3D_ERR_ARG and launch nothing. */
+int far3d_dwconv3x3_act_nhwc(const void* x, int dt, const float* w, const float* bias, void* y, int N, int H, int W, int C, int ldx,
+                             long x_img_stride, int Ho, int Wo, int ldy, long y_img_stride, int stride, int reps, int act, void* stream);
+
 /* NCHW fp32 image (N,3,H,W) -> NHWC (N,Ho,Wo,32) im2col of the stride-2 3x3 stem conv: channel = (ky*3+kx)*3 + c for the
  * 27 taps, 5 zero channels; Ho = (H-1)/2+1.  The first VoVNet conv (ref models/backbones/vovnet.py:306-311) then runs as
  * a K=32 far3d_conv2d_nhwc 1x1. */
