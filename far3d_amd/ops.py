@@ -1257,6 +1257,93 @@ def proposal_extra_rows(sel_cnt, sel_cap, primary_rows, topk, records, img2lidar
     return ref2d, ctx, box2d, score
 
 
+def mask_compact(valid, cap, overflow_out=None):
+    """Ordered compaction of a token mask (far3d_hip.h far3d_mask_compact).  valid (N,S) bool | uint8 on the device, non-zero =
+    selected.  Returns (sel_idx (N,cap) i32: the first min(count, cap) selected indices per camera, ascending; sel_cnt (N) i32);
+    overflow_out: optional int32 device scalar, 1 when a camera holds more than cap.  No sync."""
+    lib = _lib.require_device()
+    _chk(valid, "valid", ndim=2)
+    if valid.dtype not in (torch.bool, torch.uint8):
+        raise TypeError("valid must be torch.bool or torch.uint8 (got %s)" % valid.dtype)
+    N, S = valid.shape
+    cap = int(cap)
+    if N < 1 or S < 1 or cap < 1:
+        raise ValueError("mask_compact: need N >= 1, S >= 1 and cap >= 1 (got N=%d S=%d cap=%d)" % (N, S, cap))
+    if overflow_out is not None:
+        _chk(overflow_out, "overflow_out", torch.int32)
+    sel_idx = torch.empty((N, cap), dtype=torch.int32, device=valid.device)     # entries >= sel_cnt[n] are never read
+    sel_cnt = torch.empty((N,), dtype=torch.int32, device=valid.device)
+    _lib.check(lib.far3d_mask_compact(_ptr(valid), N, S, _ptr(sel_idx), _ptr(sel_cnt), cap,
+                                      _ptr(overflow_out) if overflow_out is not None else None, _stream(valid)), "far3d_mask_compact")
+    return sel_idx, sel_cnt
+
+
+def proposal_from_boxes(boxes, box_cnt, scores, sel_idx, sel_cnt, depth, depth_stride, depth_cfg, img2lidar, feat, pc_range,
+                        depth_is_prob=True, depth_layout="nhwc", score_thr=0.1, topk=1, range_min_bin=0, records=None, out=None,
+                        mismatch_out=None, rows=None):
+    """Adaptive-query rows from given boxes (far3d_hip.h far3d_proposal_from_boxes).  boxes (rows,4) f32 cxcywh camera-major with
+    box_cnt (N) i32 per camera, scores (rows,) f32; sel_idx (N,cap) / sel_cnt (N) from mask_compact; depth f32 (N,hd,wd,nd)
+    ("nhwc") or (N,nd,hd,wd) ("nchw"), logits or probabilities; feat (N,S,C) f32 | bf16.  Returns (ref2d (rows,3), ctx (rows,C+1))
+    -- `out` gives the buffers -- of which the rows of the given boxes are written.  topk > 1: records = (flags (rows,) i32, info
+    (rows,2*topk) i32) receive the multi-depth records; run proposal_extra_rows next with (ref2d, ctx, boxes, scores) as its `out`.
+    rows: the rows that may hold primaries (default: all of boxes'; fewer when the buffers also hold room for the extra rows).
+    mismatch_out: optional int32 device scalar, 1 when box_cnt != sel_cnt for a camera.  No sync."""
+    lib = _lib.require_device()
+    _chk(boxes, "boxes", torch.float32, 2)
+    _chk(scores, "scores", torch.float32, 1)
+    _chk(box_cnt, "box_cnt", torch.int32, 1)
+    _chk(sel_idx, "sel_idx", torch.int32, 2)
+    _chk(sel_cnt, "sel_cnt", torch.int32, 1)
+    _chk(depth, "depth", torch.float32, 4)
+    _chk(img2lidar, "img2lidar", torch.float32, 3)
+    _chk(feat, "feat", ndim=3)
+    if depth_layout not in ("nhwc", "nchw"):
+        raise ValueError("proposal_from_boxes: depth_layout %r (nhwc or nchw)" % (depth_layout,))
+    N, cap = sel_idx.shape
+    S, C = int(feat.shape[1]), int(feat.shape[2])
+    rows = int(boxes.shape[0]) if rows is None else int(rows)
+    if depth_layout == "nhwc":
+        _, hd, wd, nd = depth.shape
+    else:
+        _, nd, hd, wd = depth.shape
+    if boxes.shape[1] != 4 or rows < 1 or boxes.shape[0] < rows or scores.shape[0] < rows:
+        raise ValueError("proposal_from_boxes: boxes must be (>= rows >= 1, 4) and scores hold a value per row")
+    if not (box_cnt.shape[0] == sel_cnt.shape[0] == feat.shape[0] == depth.shape[0] == N) or img2lidar.shape[0] < N:
+        raise ValueError("proposal_from_boxes: box_cnt, sel_cnt, feat, depth and img2lidar need an entry per camera (%d)" % N)
+    dev = feat.device
+    if out is not None:
+        ref2d, ctx = out[0], out[1]
+    else:
+        ref2d = torch.empty((rows, 3), dtype=torch.float32, device=dev)
+        ctx = torch.empty((rows, C + 1), dtype=torch.float32, device=dev)
+    _chk(ref2d, "ref2d", torch.float32, 2)
+    _chk(ctx, "ctx", torch.float32, 2)
+    if ref2d.shape[1] != 3 or ctx.shape[1] != C + 1 or min(ref2d.shape[0], ctx.shape[0]) < rows:
+        raise ValueError("proposal_from_boxes: ref2d (>= %d, 3) and ctx (>= %d, %d) must be dense rows" % (rows, rows, C + 1))
+    topk = int(topk)
+    flags = info = None
+    if topk > 1:
+        if records is None:
+            raise ValueError("proposal_from_boxes: topk > 1 needs records = (flags, info)")
+        flags, info = records
+        _chk(flags, "md_flags", torch.int32, 1)
+        _chk(info, "md_info", torch.int32, 2)
+        if min(flags.shape[0], info.shape[0]) < rows or info.shape[1] != 2 * topk:
+            raise ValueError("proposal_from_boxes: the records need %d rows (info: %d columns)" % (rows, 2 * topk))
+    if mismatch_out is not None:
+        _chk(mismatch_out, "mismatch_out", torch.int32)
+    pk, pp = _host_f32(list(pc_range))
+    _lib.check(lib.far3d_proposal_from_boxes(_ptr(boxes), _ptr(box_cnt), _ptr(scores), rows, _ptr(sel_idx), _ptr(sel_cnt), cap, N, S,
+                                             _ptr(depth), 0 if depth_layout == "nhwc" else 1, 1 if depth_is_prob else 0, hd, wd, nd,
+                                             int(depth_stride), float(depth_cfg["depth_min"]), float(depth_cfg["depth_max"]),
+                                             int(depth_cfg["num_depth_bins"]), _ptr(img2lidar), _ptr(feat), _dt(feat), C, pp,
+                                             float(score_thr), _ptr(ref2d), _ptr(ctx), topk, int(range_min_bin),
+                                             _ptr(flags) if flags is not None else None, _ptr(info) if info is not None else None,
+                                             _ptr(mismatch_out) if mismatch_out is not None else None, _stream(feat)),
+               "far3d_proposal_from_boxes")
+    return ref2d, ctx
+
+
 def proposal_merge_blocks(blocks, out, sel_cnt_out, primary_rows, records_out=None, m_out=None, overflow_out=None):
     """The proposals of camera blocks -> the frame's layout (far3d_hip.h far3d_proposal_merge_blocks).  blocks: dicts in ascending
     camera order with rows = (ref2d, ctx, box2d, score) of the block's own buffers, sel_cnt (cams,) int32, first_cam, and optionally

@@ -532,19 +532,81 @@ class FarHead(_SchemaModule):
         if self._eng is not None:
             self._eng.reset_memory()
 
+    FOREIGN_KEYS = ("bbox_list", "valid_indices", "bbox2d_scores", "pred_depth")
+
+    def _foreign_proposals(self, eng, outs_roi, N, S, pad_hw, img2lidar, tokens):
+        """The adaptive-query rows from a reference-format 2D dict (farhead.py:571-610, 711-827): mask compaction, rows from the
+        given boxes, for topk > 1 the extra rows.  One host sync, reading M' and the flags.  -> ((ref2d, ctx, box2d, score), M)."""
+        dev, E, K = tokens.device, self.embed_dims, eng.md_k
+        nd = eng.cfg["depthnet"]["num_depth_bins"] + 1
+        boxes_in, valid, scores, depth = (outs_roi[k] for k in self.FOREIGN_KEYS)
+        if not isinstance(boxes_in, (list, tuple)) or len(boxes_in) != N or \
+                any(not isinstance(b, torch.Tensor) or b.dim() != 2 or b.shape[1] != 4 for b in boxes_in):
+            raise ValueError("FarHead.forward: bbox_list must be a list of %d tensors (M_i, 4), one per camera (got %s)" %
+                             (N, [tuple(b.shape) if isinstance(b, torch.Tensor) else type(b).__name__ for b in boxes_in]
+                              if isinstance(boxes_in, (list, tuple)) else type(boxes_in).__name__))
+        if not isinstance(valid, torch.Tensor) or tuple(valid.shape) not in ((N, S, 1), (N, S)):
+            raise ValueError("FarHead.forward: valid_indices must be (%d, %d, 1) or (%d, %d) -- cameras x the tokens of img_feats (got %s)" %
+                             (N, S, N, S, tuple(getattr(valid, "shape", ()))))
+        nums = [int(b.shape[0]) for b in boxes_in]
+        M = sum(nums)
+        if not isinstance(scores, torch.Tensor) or tuple(scores.shape) not in ((M, 1), (M,)):
+            raise ValueError("FarHead.forward: bbox2d_scores must be (%d, 1) or (%d,) -- one score per box of bbox_list (got %s)" %
+                             (M, M, tuple(getattr(scores, "shape", ()))))
+        if not isinstance(depth, torch.Tensor) or depth.dim() != 4 or depth.shape[0] != N or depth.shape[1] != nd:
+            raise ValueError("FarHead.forward: pred_depth must be (%d, %d, hd, wd) -- cameras x (num_depth_bins + 1) (got %s)" %
+                             (N, nd, tuple(getattr(depth, "shape", ()))))
+        dstride = int(pad_hw[0] / depth.shape[2])                 # farhead.py:722
+        if dstride < 1:
+            raise ValueError("FarHead.forward: pred_depth has %d rows, more than the padded image's %d" % (depth.shape[2], pad_hw[0]))
+        P = max(M, 1)                                             # primary rows; the buffers hold the K - 1 extra rows per primary too
+        box2d = torch.zeros((K * P, 4), dtype=torch.float32, device=dev)
+        score = torch.zeros((K * P,), dtype=torch.float32, device=dev)
+        if M > 0:
+            box2d[:M].copy_(torch.cat([b.to(dev).float() for b in boxes_in]))
+            score[:M].copy_(scores.to(dev).float().reshape(-1))
+        box_cnt = torch.tensor(nums, dtype=torch.int32).to(dev)
+        mask = valid.to(dev).reshape(N, S)
+        if mask.dtype not in (torch.bool, torch.uint8):
+            mask = mask != 0
+        flags = torch.zeros((3,), dtype=torch.int32, device=dev)  # M', box / mask mismatch, more selected tokens than boxes fit
+        sel_idx, sel_cnt = ops.mask_compact(mask.contiguous(), max(max(nums), 1), overflow_out=flags[2:3])
+        pr = (torch.empty((K * P, 3), device=dev), torch.empty((K * P, E + 1), device=dev), box2d, score)
+        rec = None
+        if K > 1:
+            # flags zeroed: on a count mismatch some primaries are not written, and an unset record must not be read as valid
+            rec = (torch.zeros((P,), dtype=torch.int32, device=dev), torch.empty((P, 2 * K), dtype=torch.int32, device=dev))
+        ops.proposal_from_boxes(box2d, box_cnt, score, sel_idx, sel_cnt, depth.to(dev).float().contiguous(), dstride, eng.cfg["depthnet"],
+                                img2lidar, tokens, eng.cfg["pc_range"], depth_is_prob=True, depth_layout="nchw", score_thr=0.1,
+                                topk=K, range_min_bin=eng.md_min_bin if K > 1 else 0, records=rec, out=pr, mismatch_out=flags[1:2], rows=P)
+        if K > 1:
+            ops.proposal_extra_rows(box_cnt, 0, P, K, rec, img2lidar, eng.cfg["depthnet"], eng.cfg["pc_range"], pr, fill_hole=False,
+                                    m_out=flags[0:1])
+        m_rows, mismatch, overflow = flags.tolist()               # the one host sync (the native path's read of M)
+        if mismatch or overflow:
+            raise ValueError("FarHead.forward: bbox_list and valid_indices disagree -- boxes per camera %s, selected tokens per camera %s "
+                             "(the j-th box of a camera pairs with its j-th selected token)" % (nums, mask.sum(dim=1).tolist()))
+        return pr, (m_rows if K > 1 else M)
+
     @torch.no_grad()
     def forward(self, img_metas, outs_roi=None, **data):
         """ref farhead.py:533-693 (inference branch): data['img_feats'] list of (1,N,C,h,w) FPN maps, intrinsics / extrinsics /
-        lidar2img (1,N,4,4), ego_pose / ego_pose_inv (1,4,4), timestamp (1,), prev_exists (1,); outs_roi = the dict built by this
-        package's YOLOXHeadCustom forward + get_bboxes.  Returns all_cls_scores (layers,1,A,classes), all_bbox_preds
-        (layers,1,A,code) and dn_mask_dict=None like the reference; the streaming memory lives in the module's engine."""
+        lidar2img (1,N,4,4), ego_pose / ego_pose_inv (1,4,4), timestamp (1,), prev_exists (1,).  outs_roi is either the dict built
+        by this package's YOLOXHeadCustom forward + get_bboxes (its device-side selection under '_far3d' is used), or the
+        reference's public entries from ANY 2D head (farhead.py:571-610, 711-827): bbox_list (N tensors (M_i,4) cxcywh in padded-image
+        pixels), valid_indices ((N,S,1) | (N,S) bool), bbox2d_scores ((M,1) | (M,)), pred_depth ((N,D,hd,wd) probabilities) -- on any
+        device, in any float dtype.  Returns all_cls_scores (layers,1,A,classes), all_bbox_preds (layers,1,A,code) and
+        dn_mask_dict=None like the reference; the streaming memory lives in the module's engine."""
         _lib.require_device()
         feats = data["img_feats"]
         dev = feats[0].device
-        if outs_roi is None or "_far3d" not in outs_roi or "sel_idx" not in outs_roi["_far3d"]:
-            raise NotImplementedError("FarHead.forward needs outs_roi from far3d_amd's YOLOXHeadCustom (forward + get_bboxes): the "
-                                      "adaptive queries are built by the HIP proposal kernels from its device-side selection")
-        st = outs_roi["_far3d"]
+        st = (outs_roi or {}).get("_far3d")
+        foreign = st is None or "sel_idx" not in st
+        if foreign:
+            missing = [k for k in self.FOREIGN_KEYS if outs_roi is None or k not in outs_roi]
+            if missing:
+                raise ValueError("FarHead.forward: outs_roi is neither the dict of far3d_amd's YOLOXHeadCustom (forward + get_bboxes) nor "
+                                 "a reference-format dict: it lacks %s" % ", ".join(missing))
         eng = self._part_engine(dev, ("head",), self.engine_cfg(strides=tuple(2 ** (3 + i) for i in range(len(feats)))))
         N = feats[0].shape[1]
         E = self.embed_dims
@@ -567,8 +629,11 @@ class FarHead(_SchemaModule):
                 ops.row_affine_ln(x[n].view(-1, E), gamma[n:n + 1], beta[n:n + 1], do_ln=False,
                                   out=tokens[n, starts[l]:starts[l] + hw[l][0] * hw[l][1]])
         tokens = tokens.to(eng.prec["value"])
-        dstride = st.get("depth_stride", eng.depth_stride)     # the stride of the level the 2D head's depth branch read (farhead.py:722)
-        if eng.md_k > 1:
+        pad_hw = tuple(img_metas[0]["pad_shape"][0][:2])
+        if foreign:
+            pr, M = self._foreign_proposals(eng, outs_roi, N, S, pad_hw, img2lidar, tokens)
+        elif eng.md_k > 1:
+            dstride = st.get("depth_stride", eng.depth_stride)     # the stride of the level the 2D head's depth branch read (farhead.py:722)
             # multi-depth proposals (farhead.py:754-805): primaries + records, then the extra rows; one sync on M' like the reference's
             n, cap = st["sel_idx"].shape
             K, rows = eng.md_k, eng.md_k * n * cap
@@ -583,10 +648,10 @@ class FarHead(_SchemaModule):
                                     fill_hole=False, m_out=m_dev)
             M = int(m_dev.item())
         else:
+            dstride = st.get("depth_stride", eng.depth_stride)
             M = int(st["sel_cnt"].sum().item())
             pr = ops.proposal_gather(st["reg"], eng.cfg["strides"], st["sel_idx"], st["sel_cnt"], st["peak_weight"], st["depth_logit"],
                                      dstride, eng.cfg["depthnet"], img2lidar, tokens, eng.cfg["pc_range"], score_thr=0.1)
-        pad_hw = tuple(img_metas[0]["pad_shape"][0][:2])
         outs = eng.head_stage(tokens, pr[0], pr[1], M, dd, img_metas, hw, starts, pad_hw)
         self.last_outs = outs
         return dict(all_cls_scores=outs["all_cls_scores"], all_bbox_preds=outs["all_bbox_preds"], dn_mask_dict=None,

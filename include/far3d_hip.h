@@ -448,6 +448,42 @@ int far3d_proposal_extra_rows(const int* sel_cnt, int N, int sel_cap, int primar
                               const float* pc_range, int C, float* ref2d, float* ctx, float* box2d, float* score, int rows_total,
                               int fill_hole, int32_t* m_out, int32_t* overflow_out, void* stream);
 
+/* Ordered stream compaction of a token mask (far3d_amd/csrc/foreign.hip): the selection of a FOREIGN 2D head -- the reference's
+ * `valid_indices` -- in the form the proposal kernels consume.  Replaces the boolean-mask indexing feat_flatten[valid_indices]
+ * (ref models/dense_heads/farhead.py:578-579; yolox_head.py:454,467).  valid (N,S): one byte per token, non-zero = selected
+ * (torch.bool storage as it is); any N >= 1, any S >= 1 (no alignment asked of S or of the pointer).
+ * sel_idx (N,cap) int32: the first min(count_n, cap) selected flat indices of camera n, ascending (entries past that are not
+ * written); sel_cnt (N) int32 = min(count_n, cap); *overflow_out (optional, DEVICE int32) = 1 when some count_n > cap, else 0: it is
+ * cleared by a 4-byte memset on `stream` in front of the launch, and the workgroups that overflow all store the same 1.
+ * One kernel launch of N workgroups (the grid depends on N only, the loop on S); no host sync; no atomics. */
+int far3d_mask_compact(const uint8_t* valid, int N, int S, int* sel_idx, int* sel_cnt, int cap, int32_t* overflow_out, void* stream);
+
+/* Adaptive-query rows from GIVEN 2D boxes (far3d_amd/csrc/foreign.hip; ref farhead.py:711-827): far3d_proposal_gather /
+ * far3d_proposal_gather_md without the box decode.  boxes (rows,4) f32 cx,cy,w,h in padded-image pixels, camera-major: camera n's
+ * boxes are rows [sum box_cnt[:n], + box_cnt[n]); box_cnt (N) int32 DEVICE; scores (rows) f32, row-aligned with boxes.  The j-th box
+ * of camera n pairs with token sel_idx[n,j] of far3d_mask_compact (sel_idx (N,cap), sel_cnt (N)); S = tokens per camera.
+ * depth: f32 map of nd = depth_bins + 1 values per cell, depth_layout 0 = (N,hd,wd,nd), 1 = (N,nd,hd,wd) (the reference's
+ * pred_depth as it is); depth_is_prob 0 = logits, 1 = probabilities (the bins are ranked on the values either way).  nd <= 256.
+ * Per row: the depth cell round(centre / depth_stride), half to even, clamped to the map (:736-742) -- the rule of
+ * far3d_proposal_gather; the best bin, lowest bin on ties; LID un-binning (:521-527); un-projection with img2lidar (N,4,4) and
+ * pc_range normalisation (:792-811) -> ref2d (rows,3); ctx (rows,C+1) = the token feat[n, sel_idx[n,j], :] (feat (N,S,C) f32|bf16)
+ * || log-odds(max(score,1e-6)) - log-odds(score_thr) (:773-784).  Output row = input row.
+ * topk = 1: md_flags / md_info are not touched (may be NULL).  topk = K in 2 ... 8: every written row also leaves its record in
+ * md_flags (rows) / md_info (rows,2K), the layout of far3d_proposal_gather_md: flag = best bin >= range_min_bin; camera, the K best
+ * bins, the K-1 ratios p_k / p_0 (float bits) -- for a probability map the quotient of the two map values, for logits
+ * (e_k / s) / (e_0 / s) of the fp32 softmax exactly as far3d_proposal_gather_md forms them.  Run far3d_proposal_extra_rows next with
+ * primary_rows = sum box_cnt and boxes / scores as its box2d / score (buffers of rows_total rows, the extra rows' copies are appended).
+ * Fed with far3d_proposal_gather(_md)'s own box2d, score, sel_idx, sel_cnt and its logits, ref2d / ctx / records are the same bit for bit.
+ * *mismatch_out (optional, DEVICE int32) = 1 when box_cnt[n] != sel_cnt[n] for some camera, else 0; rows are then still written for
+ * min(box_cnt[n], sel_cnt[n]) boxes per camera (never past `rows`), and the host refuses the frame.  Rows of boxes past the counts are
+ * not touched.  One launch whose grid depends on cap and N only; no host sync; no atomics. */
+int far3d_proposal_from_boxes(const float* boxes, const int* box_cnt, const float* scores, int rows, const int* sel_idx,
+                              const int* sel_cnt, int cap, int N, int S, const float* depth, int depth_layout, int depth_is_prob,
+                              int hd, int wd, int nd, int depth_stride, float depth_min, float depth_max, int depth_bins,
+                              const float* img2lidar, const void* feat, int feat_dt, int C, const float* pc_range, float score_thr,
+                              float* ref2d, float* ctx, int topk, int range_min_bin, int32_t* md_flags, int32_t* md_info,
+                              int32_t* mismatch_out, void* stream);
+
 /* Proposals of camera BLOCKS -> the frame's layout (far3d_amd/csrc/md_blocks.hip).  nblocks (1 .. 16) blocks in ascending camera
  * order, block b = cameras [first_cam[b], first_cam[b] + block_cams[b]) (contiguous, together all N), each processed on its own by
  * far3d_proposal_gather / far3d_proposal_gather_md into its own buffers of block_rows[b] rows, whose rows [0, count_b) hold its
