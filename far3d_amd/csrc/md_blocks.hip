@@ -5,6 +5,8 @@
 //                                the multi-depth records beside them (camera field rebased to the frame's camera index), the frame's
 //                                sel_cnt, ONE count and ONE overflow flag: exactly what far3d_proposal_gather(_md) on all cameras would
 //                                have left, so that far3d_proposal_extra_rows (multi-depth) or the head (single depth) runs unchanged.
+//   far3d_proposal_pack_block    one multi-depth block -> ONE record of words (header, sel_cnt, img2lidar, the six arrays) for a rank's
+//                                exchange; the merge then reads the gathered records in place (end of this file).
 // Because a block's rows stay contiguous, every array of a block is ONE run of words that moves to ONE run of the frame's array:
 // the kernel is a set of flat copies, 16 bytes per lane wherever source and destination share their alignment modulo 16 bytes
 // (always for box2d and the records of an even K; for the 257-word context rows whenever the block's row offset is a multiple of 4).
@@ -156,5 +158,86 @@ extern "C" int far3d_proposal_merge_blocks(int nblocks, const float* const* ref2
   const int G = (int)max(1l, min((words + 4 * MERGE_THREADS - 1) / (4 * MERGE_THREADS), 256l));
   hipLaunchKernelGGL(merge_blocks_kernel, dim3(G), dim3(MERGE_THREADS), 0, (hipStream_t)stream, g);
   FAR3D_CHECK_LAUNCH("far3d_proposal_merge_blocks");
+  return FAR3D_OK;
+}
+
+// far3d_proposal_pack_block: what a camera block's far3d_proposal_gather_md left -> ONE contiguous record of 4-byte words, the unit a
+// rank of the camera-sharded runner puts into the frame's exchange (far3d_amd/dist.py).  Sections, each starting on a 16-byte boundary:
+//   header (4 words: cameras, effective count, overflow flag, 0) | sel_cnt (per) | img2lidar (per*16) | ref2d (rows*3) |
+//   ctx (rows*(C+1)) | box2d (rows*4) | score (rows) | md_flags (rows) | md_info (rows*2K)
+// The first `count` rows of every array are copied, every other word of the record is zero-filled (padding camera slots, rows past the
+// count, alignment gaps): the record is a function of the valid rows alone, and far3d_proposal_merge_blocks reads its sections in place.
+#define PACK_SECTIONS 9
+
+struct PackParams {
+  const uint32_t* src[PACK_SECTIONS];                // [0] unused (header), [1] sel_cnt, [2] img2lidar, [3..8] the six row arrays
+  long off[PACK_SECTIONS + 1];                       // word offsets of the sections; off[PACK_SECTIONS] = the record's words
+  int width[PACK_SECTIONS];                          // words per row (sel_cnt: per camera 1, img2lidar: per camera 16)
+  uint32_t* dst;
+  const int* sel_cnt;
+  const int* overflow_in;                            // device int32 or null
+  int cams, rows_src, rows, host_count;              // host_count < 0: min(sum sel_cnt, rows_src)
+};
+
+// the section offsets of a record (words); shared by the launcher's check of the caller's record size
+static void pack_layout(int per, int rows, int C, int K, long* off, int* width) {
+  const int w[PACK_SECTIONS] = {4, 1, 16, 3, C + 1, 4, 1, 1, 2 * K};
+  long o = 0;
+  for (int s = 0; s < PACK_SECTIONS; ++s) {
+    const long n = s == 0 ? 4 : (long)(s <= 2 ? per : rows) * w[s];
+    width[s] = w[s];
+    off[s] = o;
+    o = (o + n + 3) & ~3l;
+  }
+  off[PACK_SECTIONS] = o;
+}
+
+__global__ __launch_bounds__(MERGE_THREADS) void pack_block_kernel(PackParams g) {
+  const long tid = (long)blockIdx.x * MERGE_THREADS + threadIdx.x, nth = (long)gridDim.x * MERGE_THREADS;
+  // the same count rule as merge_blocks_kernel; every workgroup walks the (few) camera counts itself
+  int c, flag = 0;
+  if (g.host_count >= 0) {
+    c = g.host_count;
+  } else {
+    c = 0;
+    for (int n = 0; n < g.cams; ++n) c += g.sel_cnt[n];
+    flag |= c > g.rows_src;
+  }
+  c = min(max(c, 0), min(g.rows_src, g.rows));
+  if (g.overflow_in) flag |= *g.overflow_in != 0;
+  if (tid == 0) *reinterpret_cast<uint4*>(g.dst) = make_uint4((unsigned)g.cams, (unsigned)c, (unsigned)flag, 0u);
+  for (int s = 1; s < PACK_SECTIONS; ++s) {
+    const long valid = (long)(s <= 2 ? g.cams : c) * g.width[s];
+    uint32_t* d = g.dst + g.off[s];
+    copy_words<false>(d, g.src[s], valid, tid, nth, 1, 0);
+    zero_words(d + valid, g.off[s + 1] - g.off[s] - valid, tid, nth);
+  }
+}
+
+extern "C" int far3d_proposal_pack_block(int cams, int per, int block_rows, int rows, int C, int topk, const int32_t* sel_cnt,
+                                         const float* img2lidar, const float* ref2d, const float* ctx, const float* box2d,
+                                         const float* score, const int32_t* md_flags, const int32_t* md_info, int count_host,
+                                         const int32_t* overflow_in, float* record, long record_words, void* stream) {
+  FAR3D_CHECK_ARG(record && per > 0 && rows > 0 && C > 0 && topk >= 2 && topk <= 8, "far3d_proposal_pack_block: bad sizes or null record");
+  FAR3D_CHECK_ARG(cams >= 0 && cams <= per && block_rows >= 0 && block_rows <= rows && count_host <= block_rows,
+                  "far3d_proposal_pack_block: 0 <= cams <= per, 0 <= block_rows <= rows, count <= block_rows");
+  FAR3D_CHECK_ARG(cams == 0 ? (block_rows == 0 && count_host <= 0)
+                            : (block_rows > 0 && sel_cnt && img2lidar && ref2d && ctx && box2d && score && md_flags && md_info),
+                  "far3d_proposal_pack_block: a block with cameras needs every array; the empty block has no rows");
+  FAR3D_CHECK_ARG((reinterpret_cast<uintptr_t>(record) & 15) == 0, "far3d_proposal_pack_block: the record must be 16-byte aligned");
+  PackParams g;
+  memset(&g, 0, sizeof(g));
+  pack_layout(per, rows, C, topk, g.off, g.width);
+  FAR3D_CHECK_ARG(record_words == g.off[PACK_SECTIONS], "far3d_proposal_pack_block: the record has %ld words, the layout %ld", record_words,
+                  g.off[PACK_SECTIONS]);
+  const void* src[PACK_SECTIONS] = {nullptr, sel_cnt, img2lidar, ref2d, ctx, box2d, score, md_flags, md_info};
+  for (int s = 0; s < PACK_SECTIONS; ++s) g.src[s] = reinterpret_cast<const uint32_t*>(src[s]);
+  g.dst = reinterpret_cast<uint32_t*>(record);
+  g.sel_cnt = sel_cnt; g.overflow_in = overflow_in;
+  g.cams = cams; g.rows_src = block_rows; g.rows = rows; g.host_count = count_host;
+  // static sizes only: a thread per 16 bytes of the record, at most 256 workgroups
+  const int G = (int)max(1l, min((g.off[PACK_SECTIONS] + 4 * MERGE_THREADS - 1) / (4 * MERGE_THREADS), 256l));
+  hipLaunchKernelGGL(pack_block_kernel, dim3(G), dim3(MERGE_THREADS), 0, (hipStream_t)stream, g);
+  FAR3D_CHECK_LAUNCH("far3d_proposal_pack_block");
   return FAR3D_OK;
 }

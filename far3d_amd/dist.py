@@ -8,7 +8,8 @@ sharded by camera because its softmax spans cameras (models/utils/detr3d_transfo
 
 What a frame costs on a rank (steady state, `use_graph`): one hipGraph for the per-camera stages, the exchange (the value
 maps, the records and -- fixed-capacity threshold mode -- the per-rank proposal counts travel as ONE coalesced RCCL group,
-issued eagerly: no collective is ever captured), one hipGraph for the replicated head.  With `pipeline` the two halves run on
+issued eagerly: no collective is ever captured; with multi-depth proposals the record is the rank's whole block packed by
+far3d_proposal_pack_block, still one record and no count pair), one hipGraph for the replicated head.  With `pipeline` the two halves run on
 two streams with two buffer sets, exactly like Far3DEngine.pipeline on one GPU: the camera graph and the exchange of frame i+1
 overlap the head of frame i, so the frame time tends to max(camera stages + exchange, head) instead of their sum.
 
@@ -169,6 +170,12 @@ class ShardedFrame:
     fixed-capacity threshold mode (cfg['proposal_capacity']; each rank compacts its cameras' proposals into a block, the blocks
     and their counts are gathered and packed into the reference's camera-major order on every rank by far3d_compact_rows).
 
+    multi_depth=True (needed, and only used, when the engine's multi_depth topk > 1; either static mode): the exchange stays value
+    maps + ONE record per rank.  A rank packs its block -- primaries, per-primary records, sel_cnt, img2lidar, count, flag -- into
+    one run of words with one launch (far3d_proposal_pack_block; an idle rank's record is all zeros), and every rank's head starts
+    with Far3DEngine.merge_camera_blocks on views into the gathered records (far3d_proposal_merge_blocks +
+    far3d_proposal_extra_rows).  Outputs gain bbox2d, bbox2d_scores, sel_cnt, md_records and proposal_overflow as on one GPU.
+
     use_graph: replay the steady-state frame as TWO hipGraphs per rank -- the per-camera stages and the replicated head --
     with the exchange issued eagerly between them (no collective is ever captured).  The graphs survive scene changes:
     the first frame of a scene runs eagerly and resets the engine's streaming memory in place.
@@ -179,11 +186,11 @@ class ShardedFrame:
     Results are bit-identical to the unpipelined runner; outputs are ready on `output_stream()` (call `wait_outputs()` before
     reading them on another stream)."""
 
-    def __init__(self, engine, group=None, use_graph=False, pipeline=False, decoder="replicated"):
-        if engine.md_k > 1:
-            # the extra rows need every camera's per-primary records, which the exchange does not carry
+    def __init__(self, engine, group=None, use_graph=False, pipeline=False, decoder="replicated", multi_depth=False):
+        if engine.md_k > 1 and not multi_depth:
+            # the extra rows need every camera's per-primary records, which the single-depth exchange does not carry
             raise ValueError("camera sharding supports single-depth proposals only (multi_depth topk=1); this engine has topk=%d "
-                             "-- run it on one GPU" % engine.md_k)
+                             "-- run it on one GPU, or pass multi_depth=True (each rank's record then carries its block's records)" % engine.md_k)
         if engine.static_adaptive_rows() is None:
             raise ValueError("camera sharding needs static shapes: proposal_topk=K, or the fixed-capacity threshold mode "
                              "(proposal_capacity=rows); the legacy threshold mode syncs on a data-dependent M")
@@ -205,6 +212,12 @@ class ShardedFrame:
         self.capacity = engine.cfg.get("proposal_capacity") if engine.cfg["proposal_topk"] is None else None
         # fixed-capacity mode: rows of one rank's record block (its cameras cannot hold more proposals than their selection capacity)
         self.block_rows = min(self.capacity, self.per * engine.cfg["proposal_cap"]) if self.capacity is not None else None
+        # multi-depth (opt-in): a rank's record is its block packed by far3d_proposal_pack_block -- primaries, per-primary records,
+        # sel_cnt, img2lidar, count and flag in ONE run of words -- and the head starts with Far3DEngine.merge_camera_blocks
+        self.md = bool(multi_depth) and engine.md_k > 1
+        if self.md:
+            from . import ops
+            self.layout = ops.md_block_layout(self.per, engine.camera_block_rows(self.per), engine.cfg["embed_dims"], engine.md_k)
         self._g_cam, self._g_head, self._st, self._head_out, self._sig = {}, {}, {}, {}, {}
         self._bufs = {}
         self._scene = None
@@ -241,7 +254,7 @@ class ShardedFrame:
             dev = tok.device
             b = dict(tok=torch.empty((self.world * self.per,) + tuple(tok.shape[1:]), dtype=tok.dtype, device=dev),
                      rec=torch.empty((self.world * rec.shape[0],) + tuple(rec.shape[1:]), dtype=rec.dtype, device=dev))
-            if self.capacity is not None:
+            if self.capacity is not None and not self.md:
                 E = self.eng.cfg["embed_dims"]
                 b.update(cnt=torch.zeros((self.world, 2), dtype=torch.int32, device=dev),       # per rank: (proposals, overflow flag)
                          rows=torch.empty((self.capacity, E + 4), dtype=torch.float32, device=dev),
@@ -260,8 +273,11 @@ class ShardedFrame:
         """Per-camera stages for this rank's cameras -> dict(tok (per,S,E) padded, rec, cnt | None, hw, starts).
         Top-K mode: rec (per,K,E+4), one row [context (E+1) | normalised reference point (3)] per proposal (context first: 16-byte
         aligned GEMM operand).  Fixed-capacity mode: rec (block_rows, E+4) = this rank's proposals compacted in camera order and
-        zero-padded, cnt (1,2) int32 = (their number, overflow flag)."""
+        zero-padded, cnt (1,2) int32 = (their number, overflow flag).  Multi-depth (either mode): rec (1, words) = the block's record
+        (ops.md_block_layout), one launch; no cnt -- the count and the flag travel in the record's header."""
         eng, cfg, dev = self.eng, self.eng.cfg, self.eng.dev
+        if self.md:
+            return self._camera_part_md(dd, pad_hw)
         K = cfg["proposal_topk"]
         E = cfg["embed_dims"]
         cnt = None
@@ -287,17 +303,56 @@ class ShardedFrame:
                 cnt = torch.zeros((1, 2), dtype=torch.int32, device=dev)
         return dict(tok=self._pad(tok), rec=rec, cnt=cnt, hw=hw, starts=starts)
 
+    def _camera_part_md(self, dd, pad_hw):
+        from . import ops
+        eng, cfg = self.eng, self.eng.cfg
+        K = cfg["proposal_topk"]
+        rec = eng._buf(("md_record",), (1, self.layout["words"]), torch.float32)
+        if self.cams:
+            img = dd["img"][self.cams[0]:self.cams[-1] + 1]
+            st = eng.camera_stage(img, dd, self.cams, pad_hw, block_rows=eng.camera_block_rows(len(self.cams)))
+            ops.proposal_pack_block(st, rec, self.layout, count=len(self.cams) * K if K is not None else None)
+            tok, hw, starts = st["tokens"], st["hw"], st["starts"]
+        else:           # idle rank: the empty block's record (all zeros) and padding
+            from .synth import level_shapes, level_starts
+            hw = level_shapes(pad_hw, cfg["strides"])
+            starts, S = level_starts(hw)
+            tok = torch.zeros((0, S, cfg["embed_dims"]), dtype=eng.prec["value"], device=eng.dev)
+            ops.proposal_pack_block(None, rec, self.layout)
+        return dict(tok=self._pad(tok), rec=rec, cnt=None, hw=hw, starts=starts)
+
+    def _head_md(self, p, dd, img_metas, hw, starts, pad_hw):
+        """Multi-depth head: the gathered records ARE the blocks (views, built once per buffer set) -> merge_camera_blocks
+        (far3d_proposal_merge_blocks + far3d_proposal_extra_rows) -> head_stage with the device-side M'."""
+        from . import ops
+        eng, cfg = self.eng, self.eng.cfg
+        b = self._bufs[p]
+        tok = b["tok"][:self.num_cams]
+        if "blocks" not in b:
+            sel_cap = min(cfg["proposal_cap"], tok.shape[1]) if self.capacity is not None else 0
+            _, shards = camera_shards(self.num_cams, self.world)
+            b["blocks"] = [ops.md_block_views(b["rec"][r], self.layout, len(cams), cams[0], sel_cap)
+                           for r, cams in enumerate([c for c in sl if c >= 0] for sl in shards) if cams]
+        st = eng.merge_camera_blocks(b["blocks"])
+        out = eng.head_stage(tok, st["ref2d"], st["ctx"], st["rows"], dd, img_metas, hw, starts, pad_hw, m_dev=st["m_dev"], qshard=self.qshard)
+        P = st["md"]["primary_rows"]
+        out.update(bbox2d=st["box2d"][:P], bbox2d_scores=st["score2d"][:P], sel_cnt=st["sel_cnt"], md_records=st["md_records"],
+                   proposal_overflow=st["overflow"])
+        return out
+
     def _exchange(self, p, st):
         """The ONE exchange of the frame: value maps + adaptive-query records (+ counts), never captured."""
         b = self._gather_bufs(p, st["tok"], st["rec"])
         pairs = [(st["tok"], b["tok"]), (st["rec"], b["rec"])]
-        if self.capacity is not None:
+        if self.capacity is not None and not self.md:
             pairs.append((st["cnt"], b["cnt"]))
         return gather_many(pairs, self.group)
 
     def _head(self, p, dd, img_metas, hw, starts, pad_hw):
         from . import ops
         eng = self.eng
+        if self.md:
+            return self._head_md(p, dd, img_metas, hw, starts, pad_hw)
         K, E = eng.cfg["proposal_topk"], eng.cfg["embed_dims"]
         b = self._bufs[p]
         tok = b["tok"][:self.num_cams]

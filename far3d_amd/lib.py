@@ -72,6 +72,7 @@ SIGNATURES = {
                                           c_float, c_float, c_int, _p, _p, c_int, c_int, _p, c_float, _p, _p, c_int, c_int, _p, _p,
                                           _p, _p]),
     "far3d_proposal_merge_blocks": (c_int, [c_int] + [_p] * 13 + [c_int] * 5 + [_p] * 10),
+    "far3d_proposal_pack_block": (c_int, [c_int] * 6 + [_p] * 8 + [c_int, _p, _p, c_long, _p]),
     "far3d_compact_rows": (c_int, [_p, _p, c_int, c_int, c_int, _p, c_int, _p, _p, _p]),
     "far3d_row_affine_ln": (c_int, [_p, _p, _p, _p, _p] + [c_int] * 6 + [c_float, c_int, _p]),
     "far3d_posemb3d": (c_int, [_p, _p, _p, c_int, _p]),

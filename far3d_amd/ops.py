@@ -1416,6 +1416,89 @@ def proposal_merge_blocks(blocks, out, sel_cnt_out, primary_rows, records_out=No
     return ref2d, ctx, box2d, score
 
 
+MD_BLOCK_SECTIONS = ("header", "sel_cnt", "img2lidar", "ref2d", "ctx", "box2d", "score", "md_flags", "md_info")
+
+
+def md_block_layout(per, rows, E, K):
+    """Word layout of the record one rank contributes to a multi-depth camera-sharded exchange (far3d_hip.h
+    far3d_proposal_pack_block): `per` camera slots, `rows` = the block rows of `per` cameras, context width E, multi_depth topk K.
+    -> dict(per, rows, E, K, <section>: first word ..., words: total); every section starts on a 16-byte boundary and the total is
+    a multiple of 4 words, so records stacked as (world, words) stay aligned.  Host arithmetic only; the same on every rank."""
+    per, rows, E, K = int(per), int(rows), int(E), int(K)
+    if per < 1 or rows < 1 or E < 1 or not 2 <= K <= 8:
+        raise ValueError("md_block_layout: per, rows, E >= 1 and 2 <= K <= 8 (got %s)" % ((per, rows, E, K),))
+    sizes = (4, per, per * 16, rows * 3, rows * (E + 1), rows * 4, rows, rows, rows * 2 * K)
+    lay = dict(per=per, rows=rows, E=E, K=K)
+    o = 0
+    for name, n in zip(MD_BLOCK_SECTIONS, sizes):
+        lay[name] = o
+        o = (o + n + 3) // 4 * 4
+    lay["words"] = o
+    return lay
+
+
+def proposal_pack_block(st, record, layout, count=None, overflow=None):
+    """Pack a multi-depth camera block into its record (far3d_hip.h far3d_proposal_pack_block).  st: the result of
+    camera_stage(..., block_rows=...) for the block (ref2d, ctx, box2d, score2d, sel_cnt, md.records, md.img2lidar), or None for the
+    empty block of a rank without cameras.  record: (words,) or (1, words) float32, layout = md_block_layout(...).  count: the static
+    number of valid rows (top-K mode: cameras * K) or None (fixed-capacity mode: min(sum sel_cnt, the block's rows), a larger sum
+    raises the record's overflow flag); overflow: optional int32 device scalar OR-ed into that flag.  One launch, no sync."""
+    lib = _lib.require_device()
+    _chk(record, "record", torch.float32)
+    L = layout
+    if record.numel() != L["words"]:
+        raise ValueError("proposal_pack_block: the record has %d words, the layout %d" % (record.numel(), L["words"]))
+    if overflow is not None:
+        _chk(overflow, "overflow", torch.int32)
+    ovf = _ptr(overflow) if overflow is not None else None
+    if st is None:
+        if count not in (None, 0):
+            raise ValueError("proposal_pack_block: the empty block has no rows (count=%s)" % (count,))
+        args = [0, L["per"], 0, L["rows"], L["E"], L["K"]] + [None] * 8 + [-1 if count is None else 0, ovf]
+    else:
+        flags, info = st["md"]["records"]
+        i2l = st["md"]["img2lidar"]
+        ref2d, ctx, box2d, score, sel_cnt = st["ref2d"], st["ctx"], st["box2d"], st["score2d"], st["sel_cnt"]
+        for t, name, dt in ((ref2d, "ref2d", torch.float32), (ctx, "ctx", torch.float32), (box2d, "box2d", torch.float32),
+                            (score, "score2d", torch.float32), (i2l, "img2lidar", torch.float32), (sel_cnt, "sel_cnt", torch.int32),
+                            (flags, "md_flags", torch.int32), (info, "md_info", torch.int32)):
+            _chk(t, name, dt)
+        cams = sel_cnt.numel()
+        if ref2d.shape[1:] != (3,) or ctx.shape[1:] != (L["E"] + 1,) or box2d.shape[1:] != (4,) or score.dim() != 1 or flags.dim() != 1 or \
+                info.shape[1:] != (2 * L["K"],) or i2l.numel() != cams * 16:
+            raise ValueError("proposal_pack_block: the block's arrays do not have the layout's widths (E=%d, K=%d)" % (L["E"], L["K"]))
+        n = min(t.shape[0] for t in (ref2d, ctx, box2d, score, flags, info))
+        if not 1 <= cams <= L["per"] or not 1 <= n <= L["rows"]:
+            raise ValueError("proposal_pack_block: %d cameras / %d rows do not fit the layout's %d / %d" % (cams, n, L["per"], L["rows"]))
+        if count is not None and not 0 <= int(count) <= n:
+            raise ValueError("proposal_pack_block: count=%s outside the block's %d rows" % (count, n))
+        args = [cams, L["per"], n, L["rows"], L["E"], L["K"], _ptr(sel_cnt), _ptr(i2l), _ptr(ref2d), _ptr(ctx), _ptr(box2d), _ptr(score),
+                _ptr(flags), _ptr(info), -1 if count is None else int(count), ovf]
+    _lib.check(lib.far3d_proposal_pack_block(*args, _ptr(record), L["words"], _stream(record)), "far3d_proposal_pack_block")
+    return record
+
+
+def md_block_views(record, layout, ncams, first_cam, sel_cap):
+    """One rank's record (words,) float32 (e.g. a row of the gathered (world, words) buffer) -> the block dict
+    Far3DEngine.merge_camera_blocks takes, made of VIEWS into the record: nothing is copied, so the views built once stay valid for
+    every later frame that lands in the same buffer.  ncams / first_cam: the rank's cameras (static, from dist.camera_shards);
+    sel_cap: the per-camera selection capacity of the fixed-capacity mode (0 in the top-K mode), as camera_stage's md.sel_cap.
+    m_dev and overflow are the header's count and flag."""
+    L = layout
+    if record.dim() != 1 or record.dtype != torch.float32 or record.numel() != L["words"] or not record.is_contiguous():
+        raise ValueError("md_block_views: the record must be a contiguous (%d,) float32 tensor" % L["words"])
+    if not 1 <= ncams <= L["per"]:
+        raise ValueError("md_block_views: %d cameras in a record of %d slots" % (ncams, L["per"]))
+    rows, E, K = L["rows"], L["E"], L["K"]
+    irec = record.view(torch.int32)
+    f = lambda name, n, w: record[L[name]:L[name] + n * w].view(n, w)
+    return dict(ref2d=f("ref2d", rows, 3), ctx=f("ctx", rows, E + 1), box2d=f("box2d", rows, 4), score2d=record[L["score"]:L["score"] + rows],
+                sel_cnt=irec[L["sel_cnt"]:L["sel_cnt"] + ncams], cams=(int(first_cam), int(first_cam) + int(ncams)),
+                m_dev=irec[L["header"] + 1:L["header"] + 2], overflow=irec[L["header"] + 2:L["header"] + 3],
+                md=dict(records=(irec[L["md_flags"]:L["md_flags"] + rows], irec[L["md_info"]:L["md_info"] + rows * 2 * K].view(rows, 2 * K)),
+                        img2lidar=record[L["img2lidar"]:L["img2lidar"] + ncams * 16].view(ncams, 4, 4), sel_cap=int(sel_cap)))
+
+
 def compact_rows(src, counts, dst, m_out, overflow_out):
     """src (nblocks, rows_per_block, D) f32 with counts[b] valid rows in block b -> dst (dst_rows, D): the valid rows in block order,
     the rest zero; m_out = min(sum counts, dst_rows); overflow_out |= (sum counts > dst_rows).  One launch, no sync."""

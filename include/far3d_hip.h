@@ -509,6 +509,25 @@ int far3d_proposal_merge_blocks(int nblocks, const float* const* ref2d, const fl
                                 float* o_ref2d, float* o_ctx, float* o_box2d, float* o_score, int32_t* o_md_flags,
                                 int32_t* o_md_info, int32_t* o_sel_cnt, int32_t* m_out, int32_t* overflow_out, void* stream);
 
+/* One multi-depth camera block -> ONE contiguous record of 4-byte words (far3d_amd/csrc/md_blocks.hip): what a rank of the
+ * camera-sharded runner puts into the frame's exchange, and what far3d_proposal_merge_blocks then reads in place on every rank.
+ * The block: `cams` cameras (0 .. per; 0 = the empty block of an idle rank, every source NULL and block_rows 0) processed by
+ * far3d_proposal_gather_md into buffers of block_rows rows (<= rows).  The record: `per` camera slots and `rows` rows, sections in
+ * this order, each starting on a 16-byte boundary (record_words must equal the end of the last one, rounded up to 4 words):
+ *   header[4] = (cams, count, overflow flag, 0) | sel_cnt[per] | img2lidar[per*16] | ref2d[rows*3] | ctx[rows*(C+1)] |
+ *   box2d[rows*4] | score[rows] | md_flags[rows] | md_info[rows*2*topk]
+ * count = count_host when >= 0 (static top-K: cams * K), else min(sum sel_cnt, block_rows), and then the flag is
+ * (sum sel_cnt > block_rows); *overflow_in (optional device int32) is OR-ed into the flag.  The same rule as
+ * far3d_proposal_merge_blocks.  Exactly `count` rows of every array and `cams` entries of sel_cnt / img2lidar are copied; every
+ * other word of the record -- padding slots, rows past the count, alignment gaps -- is zero: the record is a function of the valid
+ * rows alone (the empty block's is all zeros) and safe to replay from a graph.  md_info keeps the block's own camera indices (the
+ * merge rebases them).  One launch whose grid depends on the static sizes only; no host sync.  The record must be 16-byte aligned
+ * and must not overlap a source. */
+int far3d_proposal_pack_block(int cams, int per, int block_rows, int rows, int C, int topk, const int32_t* sel_cnt,
+                              const float* img2lidar, const float* ref2d, const float* ctx, const float* box2d, const float* score,
+                              const int32_t* md_flags, const int32_t* md_info, int count_host, const int32_t* overflow_in,
+                              float* record, long record_words, void* stream);
+
 /* Blocks of rows -> one compact run (camera-sharded fixed-capacity mode): src (nblocks, rows_per_block, D) f32 of which the first
  * counts[b] rows of block b are valid; dst (dst_rows, D): rows [0, M) the valid rows in block order, the rest zero,
  * *m_out = M = min(sum counts, dst_rows); *overflow_out is OR-ed with (sum counts > dst_rows) (initialise it). */
