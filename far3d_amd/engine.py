@@ -91,6 +91,33 @@ def multi_depth_topk(cfg):
     return k
 
 
+def dwsep_layers(cfg, precision):
+    """Names of the depthwise-separable layers an engine of this cfg and precision runs as ONE far3d_dwsep_conv_nhwc launch when its
+    `fused_dwsep` is set -- every such layer ops.dwsep_supported accepts; the others keep the two-launch form.  Backbone layers of a
+    depthwise spec: 'stem2', 'stem3', 's<stage>.b<block>.c<layer>'; light-head tower layers (cfg roi_depthwise): 'roi<level>.cls<i>' /
+    'roi<level>.reg<i>' (each name is one layer = a depthwise 3x3 and its pointwise 1x1; the pointwise PackedConv is convs[name + '.pw']).
+    A pure function of its arguments: no device, no library."""
+    prec = PRECISIONS[precision] if isinstance(precision, str) else precision
+    storage = "pair" if prec.get("pair") else ("bf16" if prec["act"] == torch.bfloat16 else "f32")
+    # a pointwise layer assigned a single bf16 product inside a pair-stored network (single_bf16) is not what the fused kernel computes
+    single = lambda name: storage == "pair" and any(fnmatch.fnmatchcase(name + ".pw", pat) for pat in prec.get("single_bf16", ()))
+    ok = lambda name, C, Cout, stride: ops.dwsep_supported(C, Cout, stride, storage) and not single(name)
+    names = []
+    spec = weights.VOV_SPECS[cfg["backbone"]]
+    if spec.get("dw"):
+        st = spec["stem"]
+        names += [n for n, C, Cout, s in (("stem2", st[0], st[1], 1), ("stem3", st[1], st[2], 2)) if ok(n, C, Cout, s)]
+        for si in range(4):
+            sc = spec["stage_conv_ch"][si]
+            for bi in range(spec["block_per_stage"][si]):
+                names += ["s%d.b%d.c%d" % (si + 2, bi, i) for i in range(spec["layer_per_block"]) if ok("s%d.b%d.c%d" % (si + 2, bi, i), sc, sc, 1)]
+    if cfg.get("roi_depthwise"):
+        E = cfg["embed_dims"]
+        for l in range(len(cfg["strides"])):
+            names += ["roi%d.%s%d" % (l, t, i) for t in ("cls", "reg") for i in range(2) if ok("roi%d.%s%d" % (l, t, i), E, E, 1)]
+    return names
+
+
 def pos2posemb(pos, num_pos_feats, temperature=10000):
     dim_t = torch.arange(num_pos_feats, dtype=torch.float32, device=pos.device)
     dim_t = temperature ** (2 * torch.div(dim_t, 2, rounding_mode="floor") / num_pos_feats)
@@ -216,6 +243,10 @@ class Far3DEngine:
                                     # Measured slower than two single-set launches (profiles/light_head/README.md: 142 vs 123 us in bf16, 155
                                     # vs 147 us pair-stored on the 7x80x120x256 map -- two weight sets cost the kernel its second wave per
                                     # SIMD), so the default issues two launches; bit-identical either way
+        self.fused_dwsep = False    # True: every depthwise-separable layer far3d_dwsep_conv_nhwc takes (dwsep_layers) is ONE launch -- the depthwise
+                                    # result goes to the pointwise MFMA in registers, no scratch map; the others keep the two launches.  Opt-in:
+                                    # the pointwise sums accumulate in another order, so outputs differ in the last bits (profiles/dwsep/README.md)
+        self._dwsep = frozenset(dwsep_layers(self.cfg, self.prec))
         self.md_min_bin = (ops.depth_range_min_bin(self.cfg["depthnet"], (self.cfg.get("multi_depth") or {}).get("range_min", -1))
                            if self.md_k > 1 else None)
         self._prepare()
@@ -264,7 +295,7 @@ class Far3DEngine:
             plus the pointwise 1x1 with `pw_norm` folded in (named '<name>.pw'; nothing nonlinear sits between the two)."""
             if not dw:
                 return self._pack(*self._conv_bn(prefix, stride=stride), name=name)
-            return dict(dw=ops.pack_dw3x3(sd[prefix + "/dw_conv3x3.weight"], dev), stride=stride,
+            return dict(dw=ops.pack_dw3x3(sd[prefix + "/dw_conv3x3.weight"], dev), stride=stride, name=name,
                         pw=self._pack(*self._conv_bn(prefix, conv="/pw_conv1x1", norm="/pw_norm", pad=0), name=name + ".pw"))
 
         bb["stem2"] = layer3("img_backbone.stem.stem_2", "stem2")
@@ -318,7 +349,7 @@ class Far3DEngine:
                         w, b, _, _ = self._conv_bn(p, conv=".depthwise_conv.conv", norm=".depthwise_conv.bn", eps=1e-3)
                         pw = self._pack(*self._conv_bn(p, conv=".pointwise_conv.conv", norm=".pointwise_conv.bn", eps=1e-3, pad=0),
                                         name="roi%d.%s%d.pw" % (l, t, i))
-                        lv[t].append(dict(dw=ops.pack_dw3x3_sets([w], [b], dev), w=w, b=b, pw=pw))
+                        lv[t].append(dict(dw=ops.pack_dw3x3_sets([w], [b], dev), w=w, b=b, pw=pw, name="roi%d.%s%d" % (l, t, i)))
                 # both towers' first depthwise layers read the same map: packed as one two-set operand (cls channels first) for roi_dw_merged
                 lv["dw0"] = ops.pack_dw3x3_sets([lv["cls"][0]["w"], lv["reg"][0]["w"]], [lv["cls"][0]["b"], lv["reg"][0]["b"]], dev)
             else:
@@ -489,6 +520,8 @@ class Far3DEngine:
             return ops.conv2d_nhwc(src, layer, out=out, act="relu")
         N, H, W, Cs = src.shape
         s = layer["stride"]
+        if self.fused_dwsep and layer["name"] in self._dwsep:     # one launch, no scratch map (nothing nonlinear between the halves)
+            return ops.dwsep_conv_nhwc(src, layer["dw"], layer["pw"], s, act2="relu", out=out, pair=self.pair)
         shape = (N, (H - 1) // s + 1, (W - 1) // s + 1, Cs)
         # one scratch map per shape and buffer set: the launches of a stream are ordered, and a captured graph keeps its address
         tmp = ops.dwconv3x3_nhwc(src, layer["dw"], s, out=self._buf(("dw_tmp",) + shape, shape, self.prec["act"]), pair=self.pair)
@@ -663,17 +696,24 @@ class Far3DEngine:
 
     def _light_towers(self, x, lv):
         """The depthwise-separable cls and reg towers of one level (yolox_head.py:197-219) on the NHWC map x -> (cls feature, reg feature).
-        Per tower and layer: far3d_dwconv3x3_act_nhwc (folded BN bias + Swish), then the pointwise 1x1 + BN + Swish.  Layer 0 of both towers
-        reads x: with roi_dw_merged their depthwise halves are one two-set launch (cls channels first), otherwise two single-set launches."""
-        if self.roi_dw_merged:
+        Per tower and layer: far3d_dwconv3x3_act_nhwc (folded BN bias + Swish), then the pointwise 1x1 + BN + Swish -- or, with fused_dwsep,
+        both as one far3d_dwsep_conv_nhwc launch for the layers it takes.  Layer 0 of both towers reads x: with roi_dw_merged the depthwise
+        halves of the unfused ones are one two-set launch (cls channels first), otherwise single-set launches."""
+        fused = lambda ly: self.fused_dwsep and ly["name"] in self._dwsep
+        sep = lambda f, ly: ops.dwsep_conv_nhwc(f, ly["dw"][0], ly["pw"], 1, bias1=ly["dw"][1], act1="swish", act2="swish", pair=self.pair)
+        if self.roi_dw_merged and not (fused(lv["cls"][0]) or fused(lv["reg"][0])):
             t0 = ops.dwconv3x3_act_nhwc(x, lv["dw0"][0], 1, bias=lv["dw0"][1], act="swish", pair=self.pair)      # (N,h,w,2C): cls | reg
             half = t0.shape[-1] // 2
             t0 = (t0[..., :half], t0[..., half:])
         else:
-            t0 = tuple(ops.dwconv3x3_act_nhwc(x, lv[t][0]["dw"][0], 1, bias=lv[t][0]["dw"][1], act="swish", pair=self.pair) for t in ("cls", "reg"))
+            t0 = tuple(None if fused(lv[t][0]) else
+                       ops.dwconv3x3_act_nhwc(x, lv[t][0]["dw"][0], 1, bias=lv[t][0]["dw"][1], act="swish", pair=self.pair) for t in ("cls", "reg"))
         out = []
         for t, h in zip(("cls", "reg"), t0):
-            f = ops.conv2d_nhwc(h, lv[t][0]["pw"], act="swish")
+            f = sep(x, lv[t][0]) if h is None else ops.conv2d_nhwc(h, lv[t][0]["pw"], act="swish")
+            if fused(lv[t][1]):
+                out.append(sep(f, lv[t][1]))
+                continue
             f = ops.dwconv3x3_act_nhwc(f, lv[t][1]["dw"][0], 1, bias=lv[t][1]["dw"][1], act="swish", pair=self.pair)
             out.append(ops.conv2d_nhwc(f, lv[t][1]["pw"], act="swish"))
         return out

@@ -57,6 +57,8 @@ SIGNATURES = {
     "far3d_dwconv3x3_nhwc": (c_int, [_p, c_int, _p, _p, c_int, c_int, c_int, c_int, c_int, c_long, c_int, c_int, c_int, c_long, c_int, _p]),
     "far3d_dwconv3x3_act_nhwc": (c_int, [_p, c_int, _p, _p, _p, c_int, c_int, c_int, c_int, c_int, c_long, c_int, c_int, c_int, c_long,
                                          c_int, c_int, c_int, _p]),
+    "far3d_dwsep_conv_nhwc": (c_int, [_p, c_int, _p, _p, c_int, _p, c_int, _p, c_int, _p, c_int, c_int, c_int, c_int, c_int, c_long,
+                                      c_int, c_int, c_int, c_int, c_long, c_int, _p]),
     "far3d_stem_im2col": (c_int, [_p, _p, c_int, c_int, c_int, c_int, _p]),
     "far3d_stem_conv": (c_int, [_p, _p, _p, _p, c_int, c_int, c_int, c_int, c_long, c_int, _p]),
     "far3d_proposal_select": (c_int, [_p, _p, c_int, c_int, c_int, c_int, _p, _p, _p, _p, _p, _p, c_int, c_float, c_int, _p]),

@@ -1069,6 +1069,64 @@ def dwconv3x3_act_nhwc(x, w, stride, bias=None, act=None, out=None, pair=False):
     return out
 
 
+DWSEP_MAX_COUT = 256
+
+
+def dwsep_supported(C, Cout, stride, storage):
+    """Does far3d_dwsep_conv_nhwc (dwsep_conv_nhwc) take a depthwise-separable layer of C -> Cout channels at this stride on maps of
+    this storage?  storage: "bf16" | "pair" | "f32" (or the DT_* code / torch dtype of the maps).  A host predicate: no device, no
+    library.  The rules are the library's: bf16 or pair storage, C and Cout multiples of 32, Cout <= 256, stride 1 or 2."""
+    storage = {DT_BF16: "bf16", DT_BF16_PAIR: "pair", DT_F32: "f32", torch.bfloat16: "bf16", torch.float32: "f32"}.get(storage, storage)
+    if storage not in ("bf16", "pair"):
+        return False
+    C, Cout = int(C), int(Cout)
+    return C > 0 and Cout > 0 and C % 32 == 0 and Cout % 32 == 0 and Cout <= DWSEP_MAX_COUT and stride in (1, 2)
+
+
+def dwsep_conv_nhwc(x, w9, pc, stride, bias1=None, act1=None, act2=None, out=None, pair=False):
+    """A depthwise-separable layer in one launch: act2(pc(act1(dw3x3(x; w9) + bias1))), the result of dwconv3x3_act_nhwc followed by
+    conv2d_nhwc(., pc, act=act2) without the map between them (the depthwise half bit for bit, the pointwise sums in another order).
+    x: NHWC view, bf16 (pair: a pair-stored map of 2C stored channels).  w9: (9, C) f32 (pack_dw3x3; a (1, 9, C) set of
+    pack_dw3x3_sets is taken too).  pc: the 1x1 PackedConv the two-launch path uses (bf16 weights for bf16 maps, split weights for
+    pair-stored ones).  bias1: (C,) f32 or None.  act1 / act2: None | "relu" | "swish".  out: optional NHWC view of x's storage with
+    pc.Cout logical channels.  What dwsep_supported refuses, a misaligned view or an overlap of x and out is an error of the library
+    (Far3dHipError, nothing launched) -- there is no two-launch fallback in here."""
+    lib = _lib.require_device()
+    N, H, W, Cs = x.shape
+    C = Cs // 2 if pair else Cs
+    if pair and x.dtype != torch.bfloat16:
+        raise TypeError("dwsep_conv_nhwc: pair storage is bf16")
+    if w9.dim() == 3 and w9.shape[0] == 1:
+        w9 = w9[0]
+    _chk(w9, "w9", torch.float32, 2)
+    if tuple(w9.shape) != (9, C):
+        raise ValueError("dwsep_conv_nhwc: depthwise weights %s != (9, %d)" % (tuple(w9.shape), C))
+    if bias1 is not None:
+        if bias1.dim() == 2 and bias1.shape[0] == 1:
+            bias1 = bias1[0]
+        _chk(bias1, "bias1", torch.float32, 1)
+        if bias1.shape[0] != C:
+            raise ValueError("dwsep_conv_nhwc: bias1 %s != (%d,)" % (tuple(bias1.shape), C))
+    if (pc.KH, pc.KW, pc.stride, pc.pad) != (1, 1, 1, 0) or pc.Cin != C or pc.terms != 3:
+        raise ValueError("dwsep_conv_nhwc: pc must be a 1x1 / stride 1 / pad 0 layer of %d input channels with full products" % C)
+    codes = [DW_ACTS[a] if (a is None or isinstance(a, str)) else int(a) for a in (act1, act2)]
+    ldx, xs = _nhwc_view(x, "x")
+    s = int(stride)
+    if out is None:
+        if s < 1:
+            raise ValueError("dwsep_conv_nhwc: stride %r" % (stride,))
+        out = torch.empty((N, (H - 1) // s + 1, (W - 1) // s + 1, pc.Cout * (2 if pair else 1)), dtype=x.dtype, device=x.device)
+    if out.dtype != x.dtype or out.shape[0] != N or out.shape[3] != pc.Cout * (2 if pair else 1):
+        raise ValueError("dwsep_conv_nhwc: out %s %s does not match x %s %s and %d output channels" %
+                         (tuple(out.shape), out.dtype, tuple(x.shape), x.dtype, pc.Cout))
+    ldy, ys = _nhwc_view(out, "out")
+    _lib.check(lib.far3d_dwsep_conv_nhwc(_ptr(x), DT_BF16_PAIR if pair else _dt(x), _ptr(w9), _ptr(bias1) if bias1 is not None else None,
+                                         codes[0], _ptr(pc.w), pc.w_code, _ptr(pc.bias) if pc.bias is not None else None, codes[1], _ptr(out),
+                                         N, H, W, C, ldx, xs, out.shape[1], out.shape[2], pc.Cout, ldy, ys, s, _stream(x)),
+               "far3d_dwsep_conv_nhwc")
+    return out
+
+
 # --------------------------------------------------------------------------------------------------
 # front-end glue: stem im2col, 2D proposals, MLN apply
 # --------------------------------------------------------------------------------------------------

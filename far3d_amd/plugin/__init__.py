@@ -722,9 +722,12 @@ class Far3D(nn.Module):
             score_thr=r.threshold_score, proposal_topk=self.proposal_topk, proposal_capacity=self.proposal_capacity,
             multi_depth=dict(h.multi_depth_config), roi_depthwise=r.use_depthwise, depth_level=r.depth_level)
 
-    def prepare(self, device="cuda:0", precision="bf16"):
-        """Fold BN, pack weights for the kernels, upload.  Must be called again after loading new weights."""
+    def prepare(self, device="cuda:0", precision="bf16", fused_dwsep=False):
+        """Fold BN, pack weights for the kernels, upload.  Must be called again after loading new weights.
+        fused_dwsep: the engine's opt-in of the same name -- the depthwise-separable layers of a light model (depthwise backbone specs,
+        use_depthwise towers) as one launch each where the fused kernel takes them (engine.dwsep_layers)."""
         self.engine = _engine.Far3DEngine(self.state_dict(), self.engine_cfg(), device=device, precision=precision)
+        self.engine.fused_dwsep = bool(fused_dwsep)
         return self
 
     # -- reference inference entry points -------------------------------------------------------------------------------

@@ -379,6 +379,23 @@ int far3d_dwconv3x3_nhwc(const void* x, int dt, const float* w, void* y, int N, 
 int far3d_dwconv3x3_act_nhwc(const void* x, int dt, const float* w, const float* bias, void* y, int N, int H, int W, int C, int ldx,
                              long x_img_stride, int Ho, int Wo, int ldy, long y_img_stride, int stride, int reps, int act, void* stream);
 
+/* A depthwise-separable layer as ONE launch: y = act2( W_pw . round_storage( act1( dw3x3(x; w9) + b1 ) ) + b2 ), i.e.
+ * far3d_dwconv3x3_act_nhwc (one weight set) followed by the pointwise 1x1 far3d_conv2d_nhwc, without the scratch map between them.
+ * x, y: NHWC views under the operand rules of far3d_dwconv3x3_act_nhwc (16-byte alignment, ldx / ldy / image strides in stored
+ * elements, channel slices of wider buffers, pad 1, stride 1 or 2, Ho = (H-1)/stride + 1, Wo = (W-1)/stride + 1); x and y must not
+ * overlap (disjoint channel slices of one buffer with a common pixel stride are fine).  dt: FAR3D_DT_BF16 with w_dt = FAR3D_DT_BF16
+ * (bf16 MFMA), or FAR3D_DT_BF16_PAIR with w_dt = FAR3D_DT_F32_BF16X3 (the split products hi.hi + hi.lo + lo.hi); y has x's storage.
+ * C % 32 == 0, Cout % 32 == 0, Cout <= 256.  w9: [9][C] f32; b1: [C] f32 or NULL; w_pw, b2: the packed weights (rows >= Cout + 256,
+ * Cin padded to 32; split weights as [32 hi | 32 lo] per 32-channel block) and padded bias (or NULL) of a 1x1 far3d_conv2d_nhwc layer;
+ * act1, act2: 0 none / 1 ReLU / 2 Swish (full-precision expf).
+ * Depthwise half: the nine pinned fmas of far3d_dwconv3x3_nhwc in its tap order, the bias add, the activation, then the rounding of
+ * that kernel's store (bf16 round-to-nearest-even; pair hi = bf16(v), lo = bf16(v - hi)) -- the MFMA operand holds bit for bit what
+ * the two-launch path writes to its scratch map; only the accumulation order of the pointwise sums differs from far3d_conv2d_nhwc.
+ * Anything else (f32 storage, other sizes, overlap, misalignment) returns FAR3D_ERR_ARG and launches nothing. */
+int far3d_dwsep_conv_nhwc(const void* x, int dt, const float* w9, const float* b1, int act1, const void* w_pw, int w_dt, const float* b2,
+                          int act2, void* y, int N, int H, int W, int C, int ldx, long x_img_stride, int Ho, int Wo, int Cout, int ldy,
+                          long y_img_stride, int stride, void* stream);
+
 /* NCHW fp32 image (N,3,H,W) -> NHWC (N,Ho,Wo,32) im2col of the stride-2 3x3 stem conv: channel = (ky*3+kx)*3 + c for the
  * 27 taps, 5 zero channels; Ho = (H-1)/2+1.  The first VoVNet conv (ref models/backbones/vovnet.py:306-311) then runs as
  * a K=32 far3d_conv2d_nhwc 1x1. */
