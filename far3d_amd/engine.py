@@ -14,6 +14,7 @@ import fnmatch
 import functools
 import math
 import os
+from types import SimpleNamespace
 
 import torch
 import torch.nn.functional as F
@@ -764,32 +765,46 @@ class Far3DEngine:
         self.prev_scene = None
 
     # ------------------------------------------------------------------------------------------ a7/a8: decoder
-    def decoder(self, X2, x0, qpos, tokens, ref, hw, starts, lidar2img, pad_hw, A, hole=None, qshard=None):
-        """X2 (A+Km, 2E) `dec` dtype: rows [:A] = [tgt+pos | tgt] of the queries, rows [A:] = [mem+mempos | mem] of the memory
-        keys; x0 (A,E) f32 = tgt; qpos (A,E) f32.  Returns the stacked post-LN outputs (layers, A, E) f32.
-        qshard: query-sharded execution over several ranks (far3d_amd.dist.QueryShard), see decoder_query_sharded."""
-        if qshard is not None:
-            return self.decoder_query_sharded(X2, x0, qpos, tokens, ref, hw, starts, lidar2img, pad_hw, A, hole, qshard)
+    def _row_chains(self, packed):
+        """Do the row-resident chains (csrc/rowchain.hip) run in place of the unfused kernels?  fused_rows is set, the decoder dtype is
+        bf16 and every operand set of `packed` (the layers' RowChainLayer, the heads' RowChainBranches) could be built."""
+        return self.fused_rows and self.prec["dec"] == torch.bfloat16 and all(p is not None for p in packed)
+
+    def _decoder_setup(self, X2, x0, qpos, tokens, ref, hw, starts, lidar2img, pad_hw, A, hole, rows=None):
+        """The decoder's per-frame working set (buffers, static operands, the aggregation's order and tables) as one object, and the
+        query-independent launches.  rows None: the replicated run over all A queries; rows (a0, a1): a rank's share of the
+        query-sharded run, which orders only its own rows and runs neither the sorted mode nor sibling workgroups."""
         cfg = self.cfg
         E = cfg["embed_dims"]
         nL = len(self.layers)
         Kt = X2.shape[0]                      # A + memory keys
         at = self.prec["dec"]
-        fast = at == torch.bfloat16
         nJ = cfg["num_groups"] * cfg["num_levels"] * cfg["num_pts"]
         nO = cfg["num_pts"] * 3
-        outs = self._buf(("outs_dec",), (nL, A, E), torch.float32)
-        QKV = self._buf(("qkv",), (Kt, nL * 3 * E), at)          # per layer a [q | k | v] column block
-        XW = self._buf(("xw",), (A, 2 * E), at)                   # [x+pos | x] operand of the cross-attention GEMM
-        UL = self._buf(("ul",), (A, -(-(nJ + nO) // 64) * 64), torch.float32)    # [U (nJ) | key-point offsets (nO)] per query
-        x1 = self._buf(("x1",), (A, E), torch.float32)
-        x2 = self._buf(("x2",), (A, E), torch.float32)
-        x2b = self._buf(("x2b",), (A, E), at) if fast else None
+        ws = SimpleNamespace(X2=X2, x0=x0, qpos=qpos, tokens=tokens, ref=ref, hw=hw, starts=starts, lidar2img=lidar2img, pad_hw=pad_hw, hole=hole,
+                             nJ=nJ, nO=nO, chains=self._row_chains(ly["rc"] for ly in self.layers), perm=None, inv=None, qbase=None, split=None)
+        ws.outs = self._buf(("outs_dec",), (nL, A, E), torch.float32)
+        ws.QKV = self._buf(("qkv",), (Kt, nL * 3 * E), at)          # per layer a [q | k | v] column block
+        ws.XW = self._buf(("xw",), (A, 2 * E), at)                   # [x+pos | x] operand of the cross-attention GEMM
+        ws.UL = self._buf(("ul",), (A, -(-(nJ + nO) // 64) * 64), torch.float32)    # [U (nJ) | key-point offsets (nO)] per query
+        ws.x1 = self._buf(("x1",), (A, E), torch.float32)
+        ws.x2 = self._buf(("x2",), (A, E), torch.float32)
+        ws.x2b = self._buf(("x2b",), (A, E), at) if at == torch.bfloat16 else None
+        ws.agg_out = self._buf(("agg_out",), (A, E), at)
+        ws.att_out = self._buf(("att_out",), (A, E), at)
         # query-independent work first: the memory rows' K/V of all layers (one GEMM) and the camera term of the
         # aggregation logits of all layers (one launch)
         if Kt > A:
-            ops.linear(X2[A:], self.memkv, out=QKV[A:], out_dtype=at)
-        vc_all = ops.cam_embed_chain(lidar2img, self.cam_chain)             # (layers, N, nJ), bias included
+            ops.linear(X2[A:], self.memkv, out=ws.QKV[A:], out_dtype=at)
+        ws.vc_all = ops.cam_embed_chain(lidar2img, self.cam_chain)             # (layers, N, nJ), bias included
+        tab = self._buf(("agg_tab",), (nL, 2 + ws.vc_all.shape[1], nJ), torch.float32)
+        if rows is not None:
+            # a rank's share: the order of its own rows (absolute row indices; nothing to order for a rank without rows) and the tables
+            if rows[1] > rows[0]:
+                ws.perm = ops.aggregation_order(ref, lidar2img, cfg["pc_range"], pad_hw, out=self._buf(("perm_qs",), (rows[1] - rows[0],), torch.int32),
+                                                hole=hole, rows=rows)
+            ws.tabs = ops.agg_tables(ws.vc_all, out=tab)
+            return ws
         # per-frame preparations of the aggregation in ONE launch: reference points are fixed across the layers -> one camera-sorted
         # workgroup order (scheduling only); the camera factors of the factored softmax for all layers (include/far3d_hip.h)
         sp = None
@@ -798,78 +813,83 @@ class Far3DEngine:
             sp = self._bufs.get(sk)
             if sp is None:
                 sp = self._bufs[sk] = ops.AggSplit(A, self.agg_split_extra, self.dev)
-        self.last_agg_split = sp
+        self.last_agg_split = ws.split = sp
         srt = None
-        if self.agg_sorted and sp is None and self.agg_variant in (0, 8) and A > 0 and vc_all.shape[1] <= 8 and cfg["num_pts"] * cfg["num_levels"] <= 52:
+        if self.agg_sorted and sp is None and self.agg_variant in (0, 8) and A > 0 and ws.vc_all.shape[1] <= 8 and cfg["num_pts"] * cfg["num_levels"] <= 52:
             srt = (self._buf(("agg_inv",), (A,), torch.int32), self._buf(("agg_qbase",), (A, 4), torch.float32))
+            ws.inv, ws.qbase = srt
         res = ops.aggregation_order(ref, lidar2img, cfg["pc_range"], pad_hw, out=self._buf(("perm",), (A + (sp.extra if sp else 0),), torch.int32),
-                                    hole=hole, Vc=vc_all, tables_out=self._buf(("agg_tab",), (nL, 2 + vc_all.shape[1], nJ), torch.float32), split=sp,
-                                    sorted_operands=srt)
-        perm, tabs = res[0], res[1]
-        inv, qbase = srt if srt is not None else (None, None)
-        x = x0
-        if self.fused_rows and fast and all(ly["rc"] is not None for ly in self.layers):
-            return self._decoder_fused(X2, x0, qpos, tokens, ref, hw, starts, lidar2img, pad_hw, A, hole, outs, QKV, UL, x1, vc_all, perm, tabs,
-                                       inv, qbase)
-        for li, ly in enumerate(self.layers):
-            c0 = li * 3 * E
-            # self-attention: q = x+pos, k = cat[x,mem]+cat[pos,mempos], v = cat[x,mem] (detr3d_transformer.py:378-396)
-            ops.linear(X2[:A], ly["qkv"], out=QKV[:A, c0:c0 + 3 * E], out_dtype=at)
-            att = ops.attention_forward(QKV[:A, c0:c0 + E], QKV[:, c0 + E:c0 + 2 * E], QKV[:, c0 + 2 * E:c0 + 3 * E],
-                                        num_heads=cfg["num_heads"], out_dtype=at, hole=hole)
-            y = ops.linear(att, ly["out"], res=x)
-            # (sorted mode: the GEMM-operand rows [x1 + pos | x1] go to the aggregation kernel's launch slots, so the GEMM below
-            # writes the logits / offsets in launch order)
-            ops.layernorm(y, *ly["norms"][0], out=x1, add=qpos, y2=XW[:, :E], yb=XW[:, E:], out_rows=inv)
-            # cross-attention: fused perspective-aware aggregation (detr3d_transformer.py:522-569)
-            ops.linear(XW, ly["wl"], out=UL[:, :nJ + nO])
-            agg = ops.aggregate_forward(tokens, ref, UL[:, nJ:nJ + nO], lidar2img, UL[:, :nJ], vc_all[li], hw, starts,
-                                        cfg["pc_range"], pad_hw, num_groups=cfg["num_groups"], perm=perm, out_dtype=at,
-                                        variant=self.agg_variant, tables=tabs[li], split=sp, qbase=qbase)
-            self.last_agg = (tokens, ref, UL[:, nJ:nJ + nO], lidar2img, UL[:, :nJ], vc_all[li], hw, starts, pad_hw, perm, tabs[li], qbase)
-            y = ops.linear(agg, ly["oproj"], res=x1)
-            if fast:
-                ops.layernorm(y, *ly["norms"][1], out=x2, yb=x2b)
-            else:
-                ops.layernorm(y, *ly["norms"][1], out=x2)
-            # FFN: x + W2 relu(W1 x), hidden 1024 (SURVEY.md finding 4)
-            hdn = ops.linear(x2b if fast else x2, ly["ffn1"], act="relu", out_dtype=at)
-            y = ops.linear(hdn, ly["ffn2"], res=x2)
-            ops.layernorm(y, *ly["norms"][2], out=outs[li], add=qpos, y2=X2[:A, :E], yb=X2[:A, E:])
-            x = outs[li]
-        return outs
+                                    hole=hole, Vc=ws.vc_all, tables_out=tab, split=sp, sorted_operands=srt)
+        ws.perm, ws.tabs = res[0], res[1]
+        return ws
 
-    def _decoder_fused(self, X2, x0, qpos, tokens, ref, hw, starts, lidar2img, pad_hw, A, hole, outs, QKV, UL, x1, vc_all, perm, tabs,
-                       inv=None, qbase=None):
-        """The decoder layers with their row-local parts as two row-resident chains (csrc/rowchain.hip): per layer the attention
-        core, far3d_rowchain_attn_out (out-projection + residual + LN0 + the aggregation's logit / offset linears), the
-        aggregation kernel, far3d_rowchain_ffn (output projection + residual + LN1 + FFN + LN2 + the NEXT layer's q / k / v) --
-        4 launches instead of 11; only layer 0's in-projection is a GEMM launch of its own.  Same operands and arithmetic as the
-        unfused loop in decoder() (bf16 operands, fp32 accumulation and LayerNorms), a different K order inside the GEMMs."""
-        cfg = self.cfg
-        E = cfg["embed_dims"]
-        at = self.prec["dec"]
-        nJ = cfg["num_groups"] * cfg["num_levels"] * cfg["num_pts"]
-        nO = cfg["num_pts"] * 3
-        nL = len(self.layers)
-        agg = self._buf(("agg_out",), (A, E), at)
-        att = self._buf(("att_out",), (A, E), at)
-        ops.linear(X2[:A], self.layers[0]["qkv"], out=QKV[:A, :3 * E], out_dtype=at)
-        x = x0
+    def _decoder_layer(self, ws, li, a0, a1, dst, feed_next):
+        """The row-local part of layer `li` for the query rows [a0, a1) against the keys / values of ALL rows (ws.QKV holds the
+        layer's q / k / v): attention, out-projection, aggregation, FFN, the three LayerNorms; the post-LN2 rows go to dst
+        ((a1 - a0, E) f32).  Every kernel here works row by row and gives a row the same bits whatever rows the launch covers, which
+        is what makes ONE body valid for the whole range (the replicated run) and for any rank's share of it.
+        Two forms.  Unfused: 10 launches (11 with the in-projection the caller issues).  Row chains (ws.chains, csrc/rowchain.hip):
+        the attention core, far3d_rowchain_attn_out (out-projection + residual + LN0 + the aggregation's logit / offset linears),
+        the aggregation kernel, far3d_rowchain_ffn (output projection + residual + LN1 + FFN + LN2) -- 4 launches; same operands
+        and arithmetic as the unfused form (bf16 operands, fp32 accumulation and LayerNorms), a different K order inside the GEMMs.
+        feed_next (the replicated run): the last launch also writes the next layer's operand for these rows -- unfused [x + pos | x]
+        into ws.X2, with the chains the NEXT layer's q / k / v into ws.QKV (nothing after the last layer).  Without it (a rank's
+        share, dst = its send buffer) nothing but dst is written: the next operand is built from the exchanged rows."""
+        cfg, ly = self.cfg, self.layers[li]
+        E, at = cfg["embed_dims"], self.prec["dec"]
+        nJ, nO = ws.nJ, ws.nO
+        c0 = li * 3 * E
+        r = slice(a0, a1)
+        x = (ws.x0 if li == 0 else ws.outs[li - 1])[r]
+        qpos, x1, att = ws.qpos[r], ws.x1[r], ws.att_out[r]
+        # self-attention: q = x+pos, k = cat[x,mem]+cat[pos,mempos], v = cat[x,mem] (detr3d_transformer.py:378-396)
+        ops.attention_forward(ws.QKV[r, c0:c0 + E], ws.QKV[:, c0 + E:c0 + 2 * E], ws.QKV[:, c0 + 2 * E:c0 + 3 * E],
+                              num_heads=cfg["num_heads"], out=att, hole=ws.hole)
+        # (sorted mode, ws.inv: the rows of the logits / offsets go to the aggregation kernel's launch slots -- the chain stores them
+        # there, the unfused form stores the GEMM-operand rows [x1 + pos | x1] there so that the GEMM writes in launch order)
+        if ws.chains:
+            ops.rowchain_attn_out(att, x, qpos, ly["rc"], x1, ws.UL[r], ul_rows=ws.inv)
+        else:
+            y = ops.linear(att, ly["out"], res=x)
+            ops.layernorm(y, *ly["norms"][0], out=x1, add=qpos, y2=ws.XW[r, :E], yb=ws.XW[r, E:], out_rows=ws.inv)
+            ops.linear(ws.XW[r], ly["wl"], out=ws.UL[r, :nJ + nO])
+        # cross-attention: fused perspective-aware aggregation (detr3d_transformer.py:522-569) of the rows ws.perm lists, on the
+        # full-size buffers
+        U, off = ws.UL[:, :nJ], ws.UL[:, nJ:nJ + nO]
+        ops.aggregate_forward(ws.tokens, ws.ref, off, ws.lidar2img, U, ws.vc_all[li], ws.hw, ws.starts, cfg["pc_range"], ws.pad_hw,
+                              num_groups=cfg["num_groups"], perm=ws.perm, out=ws.agg_out, variant=self.agg_variant, tables=ws.tabs[li],
+                              split=ws.split, qbase=ws.qbase)
+        self.last_agg = (ws.tokens, ws.ref, off, ws.lidar2img, U, ws.vc_all[li], ws.hw, ws.starts, ws.pad_hw, ws.perm, ws.tabs[li], ws.qbase)
+        agg = ws.agg_out[r]
+        if ws.chains:
+            feed = feed_next and li + 1 < len(self.layers)
+            ops.rowchain_ffn(agg, x1, qpos, ly["rc"], dst, nxt=self.layers[li + 1]["rc"] if feed else None,
+                             qkv=ws.QKV[r, c0 + 3 * E:c0 + 6 * E] if feed else None)
+        else:
+            x2, x2b = ws.x2[r], (ws.x2b[r] if ws.x2b is not None else None)          # x2b: the bf16 copy the bf16 FFN reads
+            y = ops.linear(agg, ly["oproj"], res=x1)
+            ops.layernorm(y, *ly["norms"][1], out=x2, yb=x2b)
+            # FFN: x + W2 relu(W1 x), hidden 1024 (SURVEY.md finding 4)
+            hdn = ops.linear(x2 if x2b is None else x2b, ly["ffn1"], act="relu", out_dtype=at)
+            y = ops.linear(hdn, ly["ffn2"], res=x2)
+            nxt = dict(add=qpos, y2=ws.X2[r, :E], yb=ws.X2[r, E:]) if feed_next else {}
+            ops.layernorm(y, *ly["norms"][2], out=dst, **nxt)
+
+    def decoder(self, X2, x0, qpos, tokens, ref, hw, starts, lidar2img, pad_hw, A, hole=None, qshard=None):
+        """X2 (A+Km, 2E) `dec` dtype: rows [:A] = [tgt+pos | tgt] of the queries, rows [A:] = [mem+mempos | mem] of the memory
+        keys; x0 (A,E) f32 = tgt; qpos (A,E) f32.  Returns the stacked post-LN outputs (layers, A, E) f32.
+        qshard: query-sharded execution over several ranks (far3d_amd.dist.QueryShard), see decoder_query_sharded."""
+        if qshard is not None:
+            return self.decoder_query_sharded(X2, x0, qpos, tokens, ref, hw, starts, lidar2img, pad_hw, A, hole, qshard)
+        ws = self._decoder_setup(X2, x0, qpos, tokens, ref, hw, starts, lidar2img, pad_hw, A, hole)
+        E = self.cfg["embed_dims"]
         for li, ly in enumerate(self.layers):
-            c0 = li * 3 * E
-            ops.attention_forward(QKV[:A, c0:c0 + E], QKV[:, c0 + E:c0 + 2 * E], QKV[:, c0 + 2 * E:c0 + 3 * E],
-                                  num_heads=cfg["num_heads"], out=att, hole=hole)
-            ops.rowchain_attn_out(att, x, qpos, ly["rc"], x1, UL, ul_rows=inv)
-            ops.aggregate_forward(tokens, ref, UL[:, nJ:nJ + nO], lidar2img, UL[:, :nJ], vc_all[li], hw, starts,
-                                  cfg["pc_range"], pad_hw, num_groups=cfg["num_groups"], perm=perm, out=agg,
-                                  variant=self.agg_variant, tables=tabs[li], split=self.last_agg_split, qbase=qbase)
-            self.last_agg = (tokens, ref, UL[:, nJ:nJ + nO], lidar2img, UL[:, :nJ], vc_all[li], hw, starts, pad_hw, perm, tabs[li], qbase)
-            last = li + 1 == nL
-            ops.rowchain_ffn(agg, x1, qpos, ly["rc"], outs[li], nxt=None if last else self.layers[li + 1]["rc"],
-                             qkv=None if last else QKV[:A, c0 + 3 * E:c0 + 6 * E])
-            x = outs[li]
-        return outs
+            # the in-projection is a GEMM launch of its own for layer 0 only with the row chains (the FFN chain of layer li - 1 wrote
+            # this layer's q / k / v), for every layer without them
+            if li == 0 or not ws.chains:
+                ops.linear(X2[:A], ly["qkv"], out=ws.QKV[:A, li * 3 * E:(li + 1) * 3 * E], out_dtype=self.prec["dec"])
+            self._decoder_layer(ws, li, 0, A, ws.outs[li], True)
+        return ws.outs
 
     def decoder_query_sharded(self, X2, x0, qpos, tokens, ref, hw, starts, lidar2img, pad_hw, A, hole, qs):
         """The decoder with its QUERIES sharded over the ranks of a camera-sharded frame (SURVEY.md 8(e) "alternatives"): every rank
@@ -878,83 +898,35 @@ class Far3DEngine:
         small all-gather per layer (A x E fp32 = 1.5 MB at the benchmark size) hands every rank the full layer output, from which
         the next layer's keys / values are recomputed locally (one GEMM over all rows: cheaper than gathering K and V).
         Row-wise kernels give every row the same bits whatever subset of rows a launch covers, so the result is BIT-IDENTICAL to
-        the replicated decoder (tests/test_dist_gpu.py).  Per layer the sharded part is ~11 of 12 launches; what stays replicated is
+        the replicated decoder (tests/test_dist_gpu.py, tests/test_decoder_gpu.py): both run _decoder_layer, here on a share of
+        the rows.  Per layer the sharded part is ~11 of 12 launches; what stays replicated is
         the qkv GEMM, the memory K/V GEMM, the camera term and the cls / reg heads."""
-        cfg = self.cfg
-        E = cfg["embed_dims"]
-        nL = len(self.layers)
-        Kt = X2.shape[0]
-        at = self.prec["dec"]
-        fast = at == torch.bfloat16
-        nJ = cfg["num_groups"] * cfg["num_levels"] * cfg["num_pts"]
-        nO = cfg["num_pts"] * 3
+        E, at = self.cfg["embed_dims"], self.prec["dec"]
         per = qs.rows_per_rank(A)
         a0, a1 = min(qs.rank * per, A), min((qs.rank + 1) * per, A)
         nr = a1 - a0
-        outs = self._buf(("outs_dec",), (nL, A, E), torch.float32)
-        QKV = self._buf(("qkv",), (Kt, nL * 3 * E), at)
-        XW = self._buf(("xw",), (A, 2 * E), at)
-        UL = self._buf(("ul",), (A, -(-(nJ + nO) // 64) * 64), torch.float32)
-        x1 = self._buf(("x1",), (A, E), torch.float32)
-        x2 = self._buf(("x2",), (A, E), torch.float32)
-        x2b = self._buf(("x2b",), (A, E), at) if fast else None
-        agg = self._buf(("agg_out",), (A, E), at)
+        ws = self._decoder_setup(X2, x0, qpos, tokens, ref, hw, starts, lidar2img, pad_hw, A, hole, rows=(a0, a1))
         gsrc = self._buf(("qs_src",), (per, E), torch.float32)           # this rank's rows of a layer output (zero padded)
         gdst = self._buf(("qs_dst",), (qs.world * per, E), torch.float32)
         if nr < per:
             gsrc[nr:].zero_()
-        perm = None
-        if nr > 0:
-            perm = ops.aggregation_order(ref, lidar2img, cfg["pc_range"], pad_hw, out=self._buf(("perm_qs",), (nr,), torch.int32), hole=hole,
-                                         rows=(a0, a1))
-        if Kt > A:
-            ops.linear(X2[A:], self.memkv, out=QKV[A:], out_dtype=at)
-        vc_all = ops.cam_embed_chain(lidar2img, self.cam_chain)
-        tabs = ops.agg_tables(vc_all, out=self._buf(("agg_tab",), (nL, 2 + vc_all.shape[1], nJ), torch.float32))
-        x = x0
-        # fused_rows: the same row-resident chains as the replicated decoder (_decoder_fused) on this rank's rows -- their results do
-        # not depend on the rows launched together -- with the in-projection of layers > 0 as far3d_rowchain_qkv over ALL rows
-        # after the exchange (bit-identical to the chain's tail): the replicated and the sharded decoder stay equal bit for bit
-        fused = self.fused_rows and fast and all(ly["rc"] is not None for ly in self.layers)
         for li, ly in enumerate(self.layers):
             c0 = li * 3 * E
-            if fused and li > 0:
-                ops.rowchain_qkv(outs[li - 1], qpos, ly["rc"], QKV[:A, c0:c0 + 3 * E])
+            # the in-projection over ALL rows (every rank needs every K / V).  With the row chains, layers > 0 take it as
+            # far3d_rowchain_qkv on the exchanged rows: bit-identical to the tail of the FFN chain that writes it in the replicated run
+            if ws.chains and li > 0:
+                ops.rowchain_qkv(ws.outs[li - 1], qpos, ly["rc"], ws.QKV[:A, c0:c0 + 3 * E])
             else:
-                ops.linear(X2[:A], ly["qkv"], out=QKV[:A, c0:c0 + 3 * E], out_dtype=at)      # all rows: every rank needs every K / V
-            if nr > 0 and fused:
-                att = ops.attention_forward(QKV[a0:a1, c0:c0 + E], QKV[:, c0 + E:c0 + 2 * E], QKV[:, c0 + 2 * E:c0 + 3 * E],
-                                            num_heads=cfg["num_heads"], out_dtype=at, hole=hole)
-                ops.rowchain_attn_out(att, x[a0:a1], qpos[a0:a1], ly["rc"], x1[a0:a1], UL[a0:a1])
-                ops.aggregate_forward(tokens, ref, UL[:, nJ:nJ + nO], lidar2img, UL[:, :nJ], vc_all[li], hw, starts,
-                                      cfg["pc_range"], pad_hw, num_groups=cfg["num_groups"], perm=perm, out=agg, variant=self.agg_variant,
-                                      tables=tabs[li])
-                ops.rowchain_ffn(agg[a0:a1], x1[a0:a1], qpos[a0:a1], ly["rc"], gsrc[:nr])
-            elif nr > 0:
-                att = ops.attention_forward(QKV[a0:a1, c0:c0 + E], QKV[:, c0 + E:c0 + 2 * E], QKV[:, c0 + 2 * E:c0 + 3 * E],
-                                            num_heads=cfg["num_heads"], out_dtype=at, hole=hole)
-                y = ops.linear(att, ly["out"], res=x[a0:a1])
-                ops.layernorm(y, *ly["norms"][0], out=x1[a0:a1], add=qpos[a0:a1], y2=XW[a0:a1, :E], yb=XW[a0:a1, E:])
-                ops.linear(XW[a0:a1], ly["wl"], out=UL[a0:a1, :nJ + nO])
-                ops.aggregate_forward(tokens, ref, UL[:, nJ:nJ + nO], lidar2img, UL[:, :nJ], vc_all[li], hw, starts,
-                                      cfg["pc_range"], pad_hw, num_groups=cfg["num_groups"], perm=perm, out=agg, variant=self.agg_variant,
-                                      tables=tabs[li])
-                y = ops.linear(agg[a0:a1], ly["oproj"], res=x1[a0:a1])
-                if fast:
-                    ops.layernorm(y, *ly["norms"][1], out=x2[a0:a1], yb=x2b[a0:a1])
-                else:
-                    ops.layernorm(y, *ly["norms"][1], out=x2[a0:a1])
-                hdn = ops.linear((x2b if fast else x2)[a0:a1], ly["ffn1"], act="relu", out_dtype=at)
-                y = ops.linear(hdn, ly["ffn2"], res=x2[a0:a1])
-                ops.layernorm(y, *ly["norms"][2], out=gsrc[:nr])
+                ops.linear(X2[:A], ly["qkv"], out=ws.QKV[:A, c0:c0 + 3 * E], out_dtype=at)
+            if nr > 0:
+                self._decoder_layer(ws, li, a0, a1, gsrc[:nr], False)
             qs.gather(gsrc, gdst)                                       # the layer's ONE exchange (never captured into a graph)
-            outs[li].copy_(gdst[:A])       # rank r owns rows [r * per, (r + 1) * per): the blocks are already in row order, padding last
+            ws.outs[li].copy_(gdst[:A])    # rank r owns rows [r * per, (r + 1) * per): the blocks are already in row order, padding last
             # next layer's operand [x + pos | x] for ALL rows (what the fused LayerNorm epilogue writes in the replicated decoder;
             # the row chains build it inside far3d_rowchain_qkv)
-            if not fused:
-                ops.add_cast(outs[li], qpos, at, out_sum=X2[:A, :E], out_a=X2[:A, E:])
-            x = outs[li]
-        return outs
+            if not ws.chains:
+                ops.add_cast(ws.outs[li], qpos, at, out_sum=X2[:A, :E], out_a=X2[:A, E:])
+        return ws.outs
 
     # ------------------------------------------------------------------------------------------ one frame
     @_with_tile_tables
@@ -1069,12 +1041,7 @@ class Far3DEngine:
         # query-major state buffers: rows [0,nq) learned queries (constant), [nq,nq+M) adaptive queries, then the Lm memory
         # slots, whose first P_ are the propagated queries and whose rest are the extra self-attention keys
         # (farhead.py:305-311) -- so tgt = TQ[:A], memory = TQ[A:], with no concatenation copies
-        old = self._bufs.get((self._par, "tq"))
-        TQ = self._buf(("tq",), (Kt, E), torch.float32)
-        QP = self._buf(("qp",), (Kt, E), torch.float32)
-        RF = self._buf(("rf",), (Kt, 3), torch.float32)
-        if TQ is not old:      # (re)allocated (M changed in threshold mode): write the constant learned-query rows once
-            TQ[:nq].copy_(self.tgt_fixed); QP[:nq].copy_(self.qpos_fixed); RF[:nq].copy_(self.ref_fixed)
+        TQ, QP, RF = self._query_buffers(M)
         # ---- a6: memory pre-update + temporal codes (one kernel)
         m, _, mem_code, tpos = ops.memory_prepare(self.mem, dd["ego_pose_inv"], dd["timestamp"], self.pseudo_ref, self.dim_t256,
                                                   0.0 if fresh else 1.0, fresh, cfg["pc_range"], P_, temp_ref_out=RF[nq + M:])
@@ -1105,7 +1072,7 @@ class Far3DEngine:
         flatb = ops.nan_to_num_(flat, bf16_copy=fast)
         hin = flatb if fast else flat
         nl = cfg["num_layers"]
-        if self.fused_rows and fast and self.branch_rc is not None:      # both branches in one row-resident launch (csrc/rowchain.hip)
+        if self._row_chains([self.branch_rc]):      # both branches in one row-resident launch (csrc/rowchain.hip)
             cls_flat = self._buf(("cls_flat",), (nl * A, cfg["num_classes"]), torch.float32)
             rr = self._buf(("reg_flat",), (nl * A, cfg["code_size"]), torch.float32)
             ops.rowchain_branches(hin, self.branch_rc, cls_flat, rr)
@@ -1321,14 +1288,25 @@ class Far3DEngine:
         if self._ready is not None:
             torch.cuda.current_stream(self.dev).wait_event(self._ready)
 
-    def _alloc_query_buffers(self, ncam):
+    def _query_buffers(self, M):
+        """The head's query-major state buffers tq / qp (Kt, E) and rf (Kt, 3) for M adaptive-query rows, Kt = num_query + M +
+        memory_len.  The constant learned-query rows are written when the buffers are (re)allocated (a new buffer set, or M changed
+        in the legacy threshold mode), not per frame."""
         cfg = self.cfg
         E, nq = cfg["embed_dims"], cfg["num_query"]
-        Kt = nq + self.static_adaptive_rows(ncam) + cfg["memory_len"]
+        Kt = nq + M + cfg["memory_len"]
+        old = self._bufs.get((self._par, "tq"))
         TQ = self._buf(("tq",), (Kt, E), torch.float32)
         QP = self._buf(("qp",), (Kt, E), torch.float32)
         RF = self._buf(("rf",), (Kt, 3), torch.float32)
-        TQ[:nq].copy_(self.tgt_fixed); QP[:nq].copy_(self.qpos_fixed); RF[:nq].copy_(self.ref_fixed)
+        if TQ is not old:
+            TQ[:nq].copy_(self.tgt_fixed); QP[:nq].copy_(self.qpos_fixed); RF[:nq].copy_(self.ref_fixed)
+        return TQ, QP, RF
+
+    def _alloc_query_buffers(self, ncam):
+        """Before a capture: make the query buffers and their constant rows exist, so that the captured head neither allocates them
+        nor rewrites the constants on every replay."""
+        self._query_buffers(self.static_adaptive_rows(ncam))
 
     @torch.no_grad()
     @_with_tile_tables

@@ -9,6 +9,7 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from far3d_amd import dist as fdist  # noqa: E402
 from far3d_amd import engine, synth, weights  # noqa: E402
 
 K_PROP = 92
@@ -31,15 +32,12 @@ def timeit(fn, iters=5, reps=3):
     return e0.elapsed_time(e1) / (iters * reps)
 
 
-class _FakeShard:
-    """QueryShard stand-in: rank 0 of `world`, the exchange replaced by a device copy of the same size (its cost on xGMI is modelled
-    separately in DESIGN.md)."""
+class _FakeShard(fdist.QueryShard):
+    """QueryShard without a process group: rank 0 of `world` (its row partition is the real one), the exchange replaced by a device
+    copy of the same size (its cost on xGMI is modelled separately in DESIGN.md)."""
 
     def __init__(self, world):
         self.rank, self.world = 0, world
-
-    def rows_per_rank(self, A):
-        return -(-(-(-A // self.world)) // 4) * 4
 
     def gather(self, src, dst):
         dst[:src.shape[0]].copy_(src)
