@@ -232,6 +232,115 @@ def aggregate_forward(feat, ref, offsets, lidar2img, U, Vc, level_hw, level_star
     return out
 
 
+# The shape family of far3d_aggregate_forward (include/far3d_hip.h: "Requires C=256, G=8, L<=4, N<=16, N*P<=256, N*P*L<=384").
+AGG_FUSED_C, AGG_FUSED_G, AGG_FUSED_MAX_L, AGG_FUSED_MAX_N, AGG_FUSED_MAX_NP, AGG_FUSED_MAX_NLP = 256, 8, 4, 16, 256, 384
+
+
+def aggregate_fused_supported(C, G, L, N, P):
+    """Does far3d_aggregate_forward (aggregate_forward) take embed width C, G groups, L levels, N cameras and P points?  A host
+    predicate: no device, no library.  The rules are the library's size checks, one for one."""
+    C, G, L, N, P = int(C), int(G), int(L), int(N), int(P)
+    return (C == AGG_FUSED_C and G == AGG_FUSED_G and 1 <= L <= AGG_FUSED_MAX_L and 1 <= N <= AGG_FUSED_MAX_N and P >= 1 and
+            N * P <= AGG_FUSED_MAX_NP and N * P * L <= AGG_FUSED_MAX_NLP)
+
+
+def _batch_rows(t, B, A, name, who):
+    """(B,A,K) f32 device tensor -> its rows b*A + a as ONE (B*A,K) view with unit inner stride and any row stride, so that a column
+    block of a merged-GEMM output stays a view; a tensor whose rows do not lie at one stride is copied."""
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 3 and tuple(t.shape[:2]) == (B, A)):
+        raise ValueError("%s: %s must be a (B,A,.) f32 device tensor" % (who, name))
+    K = t.shape[2]
+    if B * A == 0:
+        return t.new_empty((0, K))
+    if t.stride(2) != 1 or (B > 1 and t.stride(0) != A * t.stride(1)):
+        t = t.contiguous()
+    return t.as_strided((B * A, K), (t.stride(1), 1))      # keeps the view's storage offset
+
+
+def _agg_batched(ref, offsets, lidar2img, U, Vc, who):
+    """The operands of aggregate_forward with or without a batch dimension -> (B, A, N, ref (B,A,3), offsets (B*A,3P) row-strided,
+    lidar2img (B,N,4,4), U (B*A,J) row-strided, Vc (B,N,J))."""
+    _chk(ref, "ref", torch.float32)
+    if ref.dim() == 2:
+        ref, offsets, lidar2img, U, Vc = ref[None], offsets[None], lidar2img[None], U[None], Vc[None]
+    if ref.dim() != 3 or ref.shape[2] != 3:
+        raise ValueError("%s: ref must be (A,3) or (B,A,3), got %s" % (who, tuple(ref.shape)))
+    B, A = ref.shape[:2]
+    _chk(lidar2img, "lidar2img", torch.float32, 4)
+    _chk(Vc, "Vc", torch.float32, 3)
+    N = lidar2img.shape[1]
+    if tuple(lidar2img.shape) != (B, N, 4, 4) or tuple(Vc.shape[:2]) != (B, N):
+        raise ValueError("%s: inconsistent shapes ref%s l2i%s Vc%s" % (who, tuple(ref.shape), tuple(lidar2img.shape), tuple(Vc.shape)))
+    if offsets.dim() == 4:
+        offsets = offsets.reshape(B, A, -1)
+    return B, A, N, ref, _batch_rows(offsets, B, A, "offsets", who), lidar2img, _batch_rows(U, B, A, "U", who), Vc
+
+
+def agg_operands(ref, offsets, lidar2img, U, Vc, num_levels, num_groups, pc_range, pad_hw, expand=True, key_points=False):
+    """The two MSDA operands of the aggregation in the reference's layout (far3d_agg_operands; reference detr3d_transformer.py:535-555).
+
+    ref (B,A,3) f32 normalised reference points; offsets (B,A,P,3) or (B,A,P*3) f32; lidar2img (B,N,4,4) f32; U (B,A,L*P*G) f32;
+    Vc (B,N,L*P*G) f32 -- or the one-sample tensors of aggregate_forward (no B).  U / offsets may be row-strided views.
+    Returns (loc, weights): loc (B*N,A,G,L,P,2) f32 -- expand=False: the compact (B*N,A,P,2) -- and weights (B*N,A,G,L*P) f32, what
+    msda_forward takes with bs = B*N.  key_points=True: also the key points in metres (B,A,P,3), as a third result."""
+    lib = _lib.require_device()
+    B, A, N, ref, offs, l2i, U2, Vc = _agg_batched(ref, offsets, lidar2img, U, Vc, "agg_operands")
+    L, G = int(num_levels), int(num_groups)
+    P = offs.shape[1] // 3
+    J = L * P * G
+    if offs.shape[1] != P * 3 or U2.shape[1] != J or Vc.shape[2] != J:
+        raise ValueError("agg_operands: inconsistent shapes offsets%s U%s Vc%s (L=%d P=%d G=%d)" %
+                         (tuple(offs.shape), tuple(U2.shape), tuple(Vc.shape), L, P, G))
+    dev = ref.device
+    loc = torch.empty((B * N, A, G, L, P, 2) if expand else (B * N, A, P, 2), dtype=torch.float32, device=dev)
+    w = torch.empty((B * N, A, G, L * P), dtype=torch.float32, device=dev)
+    kp = torch.empty((B, A, P, 3), dtype=torch.float32, device=dev) if key_points else None
+    pc_keep, pc_p = _host_f32(list(pc_range))
+    _lib.check(lib.far3d_agg_operands(_ptr(ref), _ptr(offs), _ptr(l2i), _ptr(U2), _ptr(Vc), _ptr(loc), _ptr(w),
+                                      _ptr(kp) if kp is not None else None, B, A, N, G, P, L, pc_p, float(pad_hw[0]), float(pad_hw[1]),
+                                      U2.stride(0), offs.stride(0), 1 if expand else 0,
+                                      _stream(ref)), "far3d_agg_operands")
+    return (loc, w, kp) if key_points else (loc, w)
+
+
+def camera_sum(x, num_cams):
+    """x (B*N, A, C) f32 -> (B, A, C) f32, the cameras of a sample added in ascending order (far3d_camera_sum)."""
+    lib = _lib.require_device()
+    _chk(x, "x", torch.float32, 3)
+    N = int(num_cams)
+    BN, A, C = x.shape
+    if N < 1 or BN % N:
+        raise ValueError("camera_sum: %d maps are not a multiple of %d cameras" % (BN, N))
+    out = torch.empty((BN // N, A, C), dtype=torch.float32, device=x.device)
+    _lib.check(lib.far3d_camera_sum(_ptr(x), _ptr(out), BN // N, N, A, C, _stream(x)), "far3d_camera_sum")
+    return out
+
+
+def _level_tensor(v, device):
+    if isinstance(v, torch.Tensor):
+        return v.to(device=device, dtype=torch.int64).contiguous()
+    return torch.tensor([list(r) if isinstance(r, (tuple, list)) else int(r) for r in v], dtype=torch.int64, device=device)
+
+
+def aggregate_general(feat, ref, offsets, lidar2img, U, Vc, level_hw, level_start, pc_range, pad_hw, num_groups):
+    """The aggregation for any shape and batch, as the reference runs it: agg_operands -> msda_forward on feat.view(B*N, S, G, C/G) ->
+    camera_sum.  feat (B*N,S,C) f32|bf16 with (C/G) % 4 == 0; the other operands as agg_operands takes them (batched or one sample);
+    level_hw [(H,W)]*L and level_start [L], as lists or as the (L,2) / (L,) integer tensors of the reference.  Returns (B,A,C) f32.
+    Three launches and the operands through memory: the path for what aggregate_fused_supported refuses, and the independent statement
+    the fused kernel is tested against -- aggregate_forward stays the path of the family."""
+    _chk(feat, "feat", ndim=3)
+    BN, S, C = feat.shape
+    G = int(num_groups)
+    if G < 1 or C % G or (C // G) % 4:
+        raise ValueError("aggregate_general: C=%d must split into G=%d groups of a multiple of 4 channels" % (C, G))
+    shapes, starts = _level_tensor(level_hw, feat.device), _level_tensor(level_start, feat.device)
+    loc, w = agg_operands(ref, offsets, lidar2img, U, Vc, shapes.shape[0], G, pc_range, pad_hw)
+    if loc.shape[0] != BN:
+        raise ValueError("aggregate_general: feat holds %d maps, the operands describe %d (B*N)" % (BN, loc.shape[0]))
+    per_cam = msda_forward(feat.view(BN, S, G, C // G), shapes, starts, loc, w, im2col_step=max(BN, 1))
+    return camera_sum(per_cam, lidar2img.shape[-3])
+
+
 # --------------------------------------------------------------------------------------------------
 # implicit-GEMM convolution / linear
 # --------------------------------------------------------------------------------------------------

@@ -129,7 +129,13 @@ class MultiScaleDeformableAttnFunction:
 # ------------------------------------------------------------------------------------------------ attention modules
 @ATTENTION.register_module(name=["DeformableFeatureAggregationCuda", "SpatialDeformableAttention", "PerspectiveAwareAggregation"])
 class DeformableFeatureAggregationCuda(nn.Module):
-    """Reference: models/utils/detr3d_transformer.py:483-569 (same kwargs, same parameter names, same forward args)."""
+    """Reference: models/utils/detr3d_transformer.py:483-569 (same kwargs, same parameter names, same forward args).
+
+    One sample at the fused kernel's shape family (ops.aggregate_fused_supported: the reference configuration) runs 3 small GEMMs + ONE
+    far3d_aggregate_forward launch + the output projection.  Any other embed_dims / num_groups with (C / G) % 4 == 0, num_levels,
+    num_pts, camera count (the limits of far3d_agg_operands, include/far3d_hip.h) and any batch size runs the reference's own sequence
+    on the device, ops.aggregate_general: far3d_agg_operands -> far3d_msda_forward -> far3d_camera_sum.  sampling_operands(...) returns
+    the two tensors the reference hands to its MSDA operator, and the key points."""
 
     def __init__(self, embed_dims=256, num_groups=8, num_levels=4, num_cams=6, dropout=0.1, num_pts=13, im2col_step=64,
                  batch_first=True, bias=1.0):
@@ -162,13 +168,59 @@ class DeformableFeatureAggregationCuda(nn.Module):
                                 ce_ln=(self.cam_embed[4].weight.data.float().to(dev), self.cam_embed[4].bias.data.float().to(dev)))
         return self._packed
 
+    def _batched_operands(self, instance_feature, query_pos, reference_points, lidar2img_mat):
+        """The module's own layers on every sample at once (rows b*A + a / b*N + n), on the ops the one-sample path uses:
+        -> (x (bs*A,C), ref (bs,A,3), offsets (bs,A,P*3), lidar2img (bs,N,4,4), U (bs,A,J), Vc (bs,N,J)), all f32."""
+        bs, A = reference_points.shape[:2]
+        C = self.embed_dims
+        P = self._pack(instance_feature.device)
+        x = instance_feature.float().reshape(bs * A, C).contiguous()
+        xq = (instance_feature + query_pos).float().reshape(bs * A, C).contiguous()
+        l2i = lidar2img_mat.float().contiguous()
+        N = l2i.shape[1]
+        ce = ops.linear(ops.linear(l2i[:, :, :3, :].reshape(bs * N, 12).contiguous(), P["ce0"], act="relu"), P["ce2"], act="relu")
+        ce = ops.layernorm(ce, *P["ce_ln"])
+        Vc, U, offs = ops.linear(ce, P["wfc_full"]), ops.linear(xq, P["wfc"]), ops.linear(x, P["lfc"])
+        return (x, reference_points.float().contiguous(), offs.view(bs, A, -1), l2i, U.view(bs, A, -1), Vc.view(bs, N, -1))
+
+    @torch.no_grad()
+    def sampling_operands(self, instance_feature, query_pos, feat_flatten, reference_points, spatial_flatten, level_start_index,
+                          pc_range, lidar2img_mat, img_metas):
+        """What the reference module hands to its MSDA operator for these inputs (forward's arguments, any batch size):
+        dict(sampling_locations (bs*N, A, G, L, P, 2)  -- `points_2d`, detr3d_transformer.py:547-555,
+             attention_weights (bs*N, A, G, L*P)       -- `weights`, :535-542,
+             key_points (bs, A, P, 3)                  -- metres, :524-525), f32 device tensors from ops.agg_operands."""
+        _lib.require_device()
+        _, ref, offs, l2i, U, Vc = self._batched_operands(instance_feature, query_pos, reference_points, lidar2img_mat)
+        pad = img_metas[0]["pad_shape"][0]
+        loc, w, kp = ops.agg_operands(ref, offs, l2i, U, Vc, self.num_levels, self.num_groups, [float(v) for v in pc_range.tolist()],
+                                      (pad[0], pad[1]), key_points=True)
+        return dict(sampling_locations=loc, attention_weights=w, key_points=kp)
+
+    def _forward_general(self, instance_feature, query_pos, feat_flatten, reference_points, spatial_flatten, level_start_index,
+                         pc_range, lidar2img_mat, img_metas):
+        """Any shape, any batch: the reference's own sequence (operands -> MSDA -> camera sum, ops.aggregate_general) between the
+        module's layers.  Needs (embed_dims / num_groups) % 4 == 0 and the sizes far3d_agg_operands takes; anything else raises."""
+        bs, A = reference_points.shape[:2]
+        x, ref, offs, l2i, U, Vc = self._batched_operands(instance_feature, query_pos, reference_points, lidar2img_mat)
+        pad = img_metas[0]["pad_shape"][0]
+        feat = feat_flatten
+        if feat.dtype not in (torch.float32, torch.bfloat16):
+            feat = feat.float()
+        agg = ops.aggregate_general(feat.contiguous(), ref, offs, l2i, U, Vc, spatial_flatten, level_start_index,
+                                    [float(v) for v in pc_range.tolist()], (pad[0], pad[1]), self.num_groups)
+        out = ops.linear(agg.view(bs * A, self.embed_dims), self._pack(x.device)["oproj"], res=x)
+        return out.view(bs, A, self.embed_dims)   # dropout is identity at inference
+
     @torch.no_grad()
     def forward(self, instance_feature, query_pos, feat_flatten, reference_points, spatial_flatten, level_start_index,
                 pc_range, lidar2img_mat, img_metas):
         _lib.require_device()
         bs, A = reference_points.shape[:2]
-        if bs != 1:
-            raise NotImplementedError("far3d_amd aggregation runs one sample per call (the reference tests with B=1)")
+        if bs != 1 or not ops.aggregate_fused_supported(self.embed_dims, self.num_groups, int(spatial_flatten.shape[0]),
+                                                        lidar2img_mat.shape[1], self.num_pts):
+            return self._forward_general(instance_feature, query_pos, feat_flatten, reference_points, spatial_flatten, level_start_index,
+                                         pc_range, lidar2img_mat, img_metas)
         dev = instance_feature.device
         P = self._pack(dev)
         x = instance_feature[0].float().contiguous()

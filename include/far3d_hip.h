@@ -82,7 +82,7 @@ int far3d_msda_forward(const void* value, int value_dtype, const int64_t* spatia
  * changes results (row a of `out` is always query a); an entry ~a (negative) means "row a holds no query": a zero row is
  * written and nothing else is done (far3d_agg_order produces such entries).  With perm, A counts the ENTRIES of perm (workgroups);
  * the rows they name may lie anywhere in ref / offsets / U / out (a subset of a larger query set).  Requires C=256, G=8, L<=4, N<=16,
- * N*P<=256, N*P*L<=384.
+ * N*P<=256, N*P*L<=384; every other shape, and a batch, runs as far3d_agg_operands -> far3d_msda_forward -> far3d_camera_sum (below).
  * cam_tables: the per-layer softmax factors of Vc from far3d_agg_tables / far3d_agg_order ((2+N)*L*P*G floats), or NULL.
  * variant: 0 = default: kernel 8 when cam_tables is given and N<=8, P<=16, value maps < 4 GiB, else kernel 7; 9 = kernel 8 with sibling
  * workgroups for heavy queries (below).
@@ -126,6 +126,32 @@ int far3d_aggregate_forward(const void* feat, int feat_dtype, const float* ref, 
  * detr3d_transformer.py:539-540) = exp(U[a][j] + mV[j] - m_a) * eV[n][j] / sum_j exp(U[a][j] + mV[j] - m_a) EV[j]: the camera
  * factors depend on the layer and the frame only, the per-query part shrinks to 8 exp per lane. */
 int far3d_agg_tables(const float* Vc, float* tables, int layers, int N, int J, void* stream);
+
+/* The aggregation's two MSDA operands, in the reference's own layout, for any shape and batch (csrc/agg_operands.hip).
+ * DeformableFeatureAggregationCuda builds `points_2d` (ref: models/utils/detr3d_transformer.py:547-555) and `weights` (:535-542) and hands
+ * them to the MSDA operator; far3d_aggregate_forward never materialises them and takes one shape family, one sample.  This entry point
+ * writes both, so that  far3d_agg_operands -> far3d_msda_forward(bs = B*N) -> far3d_camera_sum  is the whole module for every shape the
+ * reference class accepts, and an independent statement to hold the fused kernel against.  A fallback and an inspection path: the
+ * operands (about 3 * B*N*A*L*P*G floats) go through HBM; never the default for the fused family.
+ * Inputs = far3d_aggregate_forward's, with a batch dimension: ref (B,A,3) f32 normalised; offsets (B,A,P*3) f32, row stride ldOffs;
+ * lidar2img (B,N,4,4) f32; U (B,A,J) f32, row stride ldU (rows b*A + a of ONE 2-D buffer; 0 = dense); Vc (B,N,J) f32; J = L*P*G indexed
+ * (l*P + p)*G + g; pc_range 6 floats HOST; pad_h / pad_w as above.
+ * Outputs: loc (B*N, A, G, L, P, 2) f32 -- with expand = 0 the compact (B*N, A, P, 2) (the reference repeats the P points over groups
+ * and levels, :555); weights (B*N, A, G, L*P) f32; key_points (B, A, P, 3) f32 in metres (:524-525), or NULL.
+ * fp32 throughout, as the reference states it: ref_m = ref*(hi-lo)+lo; key = ref_m + offset; (x,y,z) = rows 0..2 of lidar2img . [key,1];
+ * zc = fmaxf(z, 1e-5f); u = (x / zc) / pad_w, v = (y / zc) / pad_h (true divisions); weights = softmax over the N*L*P entries of
+ * U[a] + Vc[n] per (a, g): max subtracted, expf, a fixed summation order, a division by the sum.  One launch (workgroup per (b, a)), no
+ * workspace, no atomics; the result does not depend on B or expand and is bit-identical from run to run.
+ * Sizes: 1 <= N <= 32, 1 <= L <= 8, 1 <= P <= 64, 1 <= G <= 64, N*L*P <= 8192; anything else is FAR3D_ERR_ARG and nothing is launched.
+ * 16-byte accesses are used where J % 4 == 0 (U rows: also ldU % 4 == 0) and the buffers are 16-byte aligned; up to J = 16384 a camera's
+ * weights leave as one contiguous run. */
+int far3d_agg_operands(const float* ref, const float* offsets, const float* lidar2img, const float* U, const float* Vc,
+                       float* loc, float* weights, float* key_points, int B, int A, int N, int G, int P, int L,
+                       const float* pc_range, float pad_h, float pad_w, int ldU, int ldOffs, int expand, void* stream);
+
+/* Cross-camera sum behind the MSDA operator (ref: models/utils/detr3d_transformer.py:565-569): x (B*N, A, C) f32 -> out (B, A, C) f32,
+ * cameras added in ascending order (((x0 + x1) + x2) + ...).  One streaming launch, 16-byte accesses where A*C % 4 == 0. */
+int far3d_camera_sum(const float* x, float* out, int B, int N, int A, int C, void* stream);
 
 /* Implicit-GEMM convolution / linear layer on the matrix cores (bf16 MFMA, or exact-fp32 MFMA when w_dt = F32).
  * Replaces the torch/cuDNN convolutions and nn.Linear GEMMs of the path:
