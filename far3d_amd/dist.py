@@ -10,14 +10,17 @@ What a frame costs on a rank (steady state, `use_graph`): one hipGraph for the p
 maps, the records and -- fixed-capacity threshold mode -- the per-rank proposal counts travel as ONE coalesced RCCL group,
 issued eagerly: no collective is ever captured; with multi-depth proposals the record is the rank's whole block packed by
 far3d_proposal_pack_block, still one record and no count pair), one hipGraph for the replicated head.  With `pipeline` the two halves run on
-two streams with two buffer sets, exactly like Far3DEngine.pipeline on one GPU: the camera graph and the exchange of frame i+1
-overlap the head of frame i, so the frame time tends to max(camera stages + exchange, head) instead of their sum.
+the streams and buffer sets of frame_pipeline.FramePipeline, the mechanism behind Far3DEngine.pipeline on one GPU, with the exchange as
+its "after camera" step: the camera graph and the exchange of frame i+1 overlap the head of frame i, so the frame time tends to
+max(camera stages + exchange, head) instead of their sum.
 
 Host logic here is device-agnostic so the shard / gather / un-pad arithmetic is covered by 2-process gloo tests on CPU;
 the compute itself has no CPU path.
 """
 import torch
 import torch.distributed as dist
+
+from .frame_pipeline import FramePipeline
 
 
 def camera_shards(num_cams, world):
@@ -179,7 +182,7 @@ class ShardedFrame:
     use_graph: replay the steady-state frame as TWO hipGraphs per rank -- the per-camera stages and the replicated head --
     with the exchange issued eagerly between them (no collective is ever captured).  The graphs survive scene changes:
     the first frame of a scene runs eagerly and resets the engine's streaming memory in place.
-    pipeline (with use_graph): frames of one stream are software-pipelined like on one GPU (engine.pipeline_sets buffer sets,
+    pipeline (with use_graph): frames of one stream are software-pipelined by the one-GPU mechanism, FramePipeline (engine.pipeline_sets buffer sets,
     engine.cam_streams high-priority camera streams): the camera graph + exchange of the next frames run side by side -- a rank
     with one or two cameras is launch-bound, three frames at once cost 1.08 ms per frame where one costs 2.33 (1 camera;
     profiles/r4/stage_times_bf16.txt) -- under the head of an earlier frame.  Exchanges are issued in frame order on every rank.
@@ -218,11 +221,11 @@ class ShardedFrame:
         if self.md:
             from . import ops
             self.layout = ops.md_block_layout(self.per, engine.camera_block_rows(self.per), engine.cfg["embed_dims"], engine.md_k)
-        self._g_cam, self._g_head, self._st, self._head_out, self._sig = {}, {}, {}, {}, {}
+        # the per-buffer-set graphs of both graph modes (a slot's `keep` is its camera part's result) and the pipeline's streams
+        self._pipe = FramePipeline(engine)
         self._bufs = {}
         self._scene = None
         self._fidx = 0
-        self._pipe = None
         # record_stage_times (unpipelined frames only; bench.py --gpus N): device events around the three parts of a rank's frame --
         # per-camera stages, exchange, replicated head -- so that a scaling line can be read against DESIGN.md section 7's table
         self.record_stage_times = False
@@ -260,7 +263,7 @@ class ShardedFrame:
                          rows=torch.empty((self.capacity, E + 4), dtype=torch.float32, device=dev),
                          m=torch.zeros((1,), dtype=torch.int32, device=dev), ovf=torch.zeros((1,), dtype=torch.int32, device=dev))
             self._bufs[p] = b
-            self._g_head.pop(p, None)
+            self._pipe.drop(p)          # graphs captured on the old buffers (none while this set is being captured: its slot is empty)
         return b
 
     def _pad(self, t):
@@ -369,16 +372,6 @@ class ShardedFrame:
         out["proposal_overflow"] = b["ovf"]
         return out
 
-    def _drop_stale_graphs(self, p, dd):
-        """Graphs bake the addresses of the staged inputs: a re-allocation (new resolution / camera count) invalidates them."""
-        sig = (dd["img"].data_ptr(), tuple(dd["img"].shape))
-        if self._sig.get(p) != sig:
-            if p in self._g_cam or p in self._g_head:
-                torch.cuda.synchronize(self.eng.dev)
-            for d in (self._g_cam, self._g_head, self._st, self._head_out):
-                d.pop(p, None)
-            self._sig[p] = sig
-
     def _capture(self, fn):
         g = torch.cuda.CUDAGraph()
         # thread_local: the RCCL watchdog thread of the process group keeps polling its events while we capture
@@ -426,116 +419,59 @@ class ShardedFrame:
     # ------------------------------------------------------------------------------------------ frames
     def output_stream(self):
         """The stream the latest forward_frame's outputs are produced on."""
-        return self._pipe["s_head"] if (self._pipe is not None and self.eng._ready is not None) else torch.cuda.current_stream(self.eng.dev)
+        return self._pipe.output_stream()
 
     def wait_outputs(self):
         self.eng.wait_outputs()
+
+    _g_head = property(lambda self: self._pipe["g_head"])      # {buffer set: its captured head (_Replay)}, both graph modes
+
+    def _capture_frame(self, dd, img_metas, pad_hw):
+        """FramePipeline's capture: the camera graph (an idle rank -- no cameras -- has none: it only pads the exchange and runs the head,
+        and is never the slowest rank), ONE eager exchange (a collective: every rank captures on the same frame), the head graph(s)."""
+        p = self.eng._par
+        if self.cams:
+            g_cam, st = self._capture(lambda: self._camera_part(dd, pad_hw))
+            g_cam.replay()
+        else:
+            g_cam, st = None, self._camera_part(dd, pad_hw)
+        for w in self._exchange(p, st):
+            w.wait()
+        g_head, outs = self._capture_head(lambda: self._head(p, dd, img_metas, st["hw"], st["starts"], pad_hw))
+        return g_cam, g_head, outs, st
 
     @torch.no_grad()
     def forward_frame(self, data, img_metas):
         eng = self.eng
         pad_hw = tuple(img_metas[0]["pad_shape"][0][:2])
         scene = img_metas[0]["scene_token"]
-        # an idle rank (no cameras) has no camera graph: it only pads the exchange and runs the head, and is never the slowest rank
         steady = self.use_graph and scene == self._scene and eng._mem_valid
         self._scene = scene
         p = eng._par = (self._fidx % max(2, int(eng.pipeline_sets))) if self.pipeline else 0
         self._fidx += 1
         if self.pipeline and steady:
-            return self._pipelined_frame(data, img_metas, pad_hw)
-        if self._pipe is not None:      # scene start in pipeline mode: eager on the caller's stream, after everything in flight
-            cur = torch.cuda.current_stream(eng.dev)
-            for sc in self._pipe["s_cams"]:
-                cur.wait_stream(sc)
-            cur.wait_stream(self._pipe["s_head"])
-        eng._ready = None
-        dd = eng._stage_inputs(data)      # every rank keeps the (small) calibration inputs; images are sliced per rank
-        self._drop_stale_graphs(p, dd)
-        evs = [] if (self.record_stage_times and steady and p in self._g_head) else None      # replayed frames only (a capture is not a frame)
-        self._mark(evs)
-        # ---- per-camera stages: eager, or one hipGraph per rank in steady state
-        if steady and self.cams:
-            if p not in self._g_cam:
-                self._g_cam[p], self._st[p] = self._capture(lambda: self._camera_part(dd, pad_hw))
-            self._g_cam[p].replay()
-            st = self._st[p]
-        else:
+            return self._pipe.frame(self._capture_frame, data, img_metas, pad_hw, after_camera=self._exchange)
+        self._pipe.drain()              # scene start in pipeline mode: eager on the caller's stream, after everything in flight
+        if not steady:                  # first frame of a scene (memory reset) or graphs off: eager
+            dd = eng._stage_inputs(data)      # every rank keeps the (small) calibration inputs; images are sliced per rank
             st = self._camera_part(dd, pad_hw)
+            for w in self._exchange(p, st):
+                w.wait()
+            return self._head(p, dd, img_metas, st["hw"], st["starts"], pad_hw)
+        # ---- steady state, unpipelined: the slot's camera graph, the exchange, its head graph, on the caller's stream
+        slot, first = self._pipe.slot(self._capture_frame, data, img_metas, pad_hw)
+        eng._stage_inputs(data)
+        evs = [] if (self.record_stage_times and not first) else None      # replayed frames only (a capture is not a frame)
         self._mark(evs)
-        for w in self._exchange(p, st):
+        if slot["cam"] is not None:
+            slot["cam"].replay()
+        self._mark(evs)
+        for w in self._exchange(p, slot["keep"]):
             w.wait()
         self._mark(evs)
-        # ---- replicated head on the gathered buffers: eager on the first frame of a scene (memory reset), else a hipGraph
-        if not steady:
-            return self._head(p, dd, img_metas, st["hw"], st["starts"], pad_hw)
-        if p not in self._g_head:
-            self._g_head[p], self._head_out[p] = self._capture_head(lambda: self._head(p, dd, img_metas, st["hw"], st["starts"], pad_hw))
-        self._g_head[p].replay()
+        slot["head"].replay()
         self._mark(evs)
         if evs is not None:
             self.stage_times.append(evs)
-        eng._overflow = self._head_out[p].get("proposal_overflow")
-        return self._head_out[p]
-
-    def _pipelined_frame(self, data, img_metas, pad_hw):
-        """One steady-state frame in pipeline mode.  Stream s_cam: [wait until the head that last used this buffer set is done] ->
-        input staging -> camera graph -> exchange.  Stream s_head: [wait for the exchange] -> head graph."""
-        eng = self.eng
-        if self._pipe is None:
-            ncs = max(1, min(int(eng.pipeline_sets) - 1, int(eng.cam_streams)))
-            self._pipe = dict(s_cams=[torch.cuda.Stream(eng.dev, priority=eng.cam_priority) for _ in range(ncs)], s_head=torch.cuda.Stream(eng.dev),
-                              cam_done={}, head_done={}, n_issued=0)
-        P = self._pipe
-        p = eng._par
-        cur = torch.cuda.current_stream(eng.dev)
-        here = torch.cuda.Event()
-        here.record(cur)
-        img = data["img"][0] if data["img"].dim() == 5 else data["img"]
-        cached = eng._ins.get(p)
-        if cached is None or tuple(cached["img"].shape) != tuple(img.shape) or p not in self._g_head:
-            # first steady frame on this buffer set (or a new input shape): capture its graphs with the device quiet.  The eager
-            # exchange inside is a collective: every rank takes this branch on the same frame (same frame sequence on every rank)
-            torch.cuda.synchronize(eng.dev)
-            dd = eng._stage_inputs(data)
-            self._drop_stale_graphs(p, dd)
-            if (p, "tq") not in eng._bufs:
-                eng._alloc_query_buffers(self.num_cams)
-            if self.cams:
-                self._g_cam[p], self._st[p] = self._capture(lambda: self._camera_part(dd, pad_hw))
-                self._g_cam[p].replay()
-            else:
-                self._st[p] = self._camera_part(dd, pad_hw)
-            st = self._st[p]
-            for w in self._exchange(p, st):
-                w.wait()
-            self._g_head[p], self._head_out[p] = self._capture_head(lambda: self._head(p, dd, img_metas, st["hw"], st["starts"], pad_hw))
-            P["cam_done"][p], P["head_done"][p] = torch.cuda.Event(), torch.cuda.Event()
-            torch.cuda.synchronize(eng.dev)
-            first = True
-        else:
-            first = False
-        st = self._st[p]
-        s_cam = P["s_cams"][P["n_issued"] % len(P["s_cams"])]      # consecutive frames alternate between the camera streams
-        P["n_issued"] += 1
-        s_cam.wait_event(here)
-        for v in data.values():
-            if isinstance(v, torch.Tensor) and v.is_cuda:
-                v.record_stream(s_cam)
-        with torch.cuda.stream(s_cam):
-            if not first:
-                s_cam.wait_event(P["head_done"][p])      # the head that last read this buffer set (inputs and exchange buffers included)
-            eng._stage_inputs(data)
-            if self.cams:
-                self._g_cam[p].replay()
-            works = self._exchange(p, st)
-            P["cam_done"][p].record(s_cam)
-        with torch.cuda.stream(P["s_head"]):
-            P["s_head"].wait_event(here)
-            P["s_head"].wait_event(P["cam_done"][p])
-            for w in works:
-                w.wait()                                         # stream-ordered on the RCCL backend: s_head waits, the host does not
-            self._g_head[p].replay()
-            P["head_done"][p].record(P["s_head"])
-        eng._ready = P["head_done"][p]
-        eng._overflow = self._head_out[p].get("proposal_overflow")      # this frame's flag (its buffer set), not the last captured one
-        return self._head_out[p]
+        eng._overflow = slot["outs"].get("proposal_overflow")      # this frame's flag (its buffer set), not the last captured one
+        return slot["outs"]

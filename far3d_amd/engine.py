@@ -21,6 +21,7 @@ import torch.nn.functional as F
 
 from . import lib as _lib
 from . import ops, weights
+from .frame_pipeline import FramePipeline
 from .synth import level_starts
 
 PRECISIONS = {
@@ -200,7 +201,8 @@ class Far3DEngine:
                                     # fixed-capacity threshold proposals, static_adaptive_rows() is not None)
         # pipeline (with use_graph): consecutive frames of a stream are software-pipelined -- the per-camera stages of frame
         # i+1 (which do not depend on the streaming memory) run on their own HIP stream while the head of frame i is still in
-        # flight.  Two complete buffer sets (parity = frame index & 1) and two graphs per parity (camera stages, head); the
+        # flight (frame_pipeline.FramePipeline: streams, events, staleness of the graphs, the steady frame).  pipeline_sets
+        # complete buffer sets (frame index modulo) and two graphs per set (camera stages, head: _capture_frame); the
         # head graphs are ordered on one stream, so the memory updates stay sequential and the results are bit-identical to
         # the unpipelined engine.  Throughput only: the latency of a single frame does not change.  In this mode the outputs of
         # forward_frame are ready on `output_stream()`; a caller that reads them on its own stream calls `wait_outputs()` first
@@ -221,7 +223,7 @@ class Far3DEngine:
                                     # head's small launches interleave with the camera stages and the gain is lost (167.0 at 3 sets)
         self._par = 0               # buffer set currently in use (always 0 without pipelining)
         self._fidx = 0
-        self._pipe = None
+        self._pipe = FramePipeline(self)      # the pipeline's streams and per-buffer-set graphs (falsy until used)
         self.agg_variant = 0        # far3d_aggregate_forward kernel variant (0 = default; tools/ use 3 for A/B timing)
         self.agg_sorted = True      # the aggregation kernel's SORTED mode (round 6): far3d_agg_order also emits the launch slot of every
                                     # row and the reference points in launch order; the producers of the per-layer logits / offsets store in launch
@@ -1104,8 +1106,8 @@ class Far3DEngine:
         cur = self._ins.get(self._par)
         if cur is None or tuple(cur["img"].shape) != tuple(img.shape):
             # (re)allocation: graphs captured on the old buffers of THIS parity are stale.  The single-graph mode drops its graph
-            # here; the pipeline's per-parity graphs are dropped by _pipelined_frame BEFORE it decides to replay (it checks the
-            # shape itself), and its streams / events are never dropped, so a scene start can always wait for heads in flight.
+            # here; the pipeline's per-parity graphs are dropped by FramePipeline.slot BEFORE it decides to replay (this dict is no
+            # longer the one they were captured on), and its streams are never dropped, so a scene start can always wait for heads in flight.
             cur = dict(img=torch.empty(tuple(img.shape), dtype=torch.float32, device=dev))
             for k in keys:
                 cur[k] = torch.empty(tuple(data[k].shape), dtype=torch.float64 if k == "timestamp" else torch.float32, device=dev)
@@ -1216,72 +1218,18 @@ class Far3DEngine:
                                 self.cfg["depthnet"], self.cfg["pc_range"], (st["ref2d"], st["ctx"], st["box2d"], st["score2d"]),
                                 fill_hole=fill_hole, m_out=st["m_dev"], overflow_out=st["overflow"])
 
-    def _pipelined_frame(self, data, img_metas, pad_hw):
-        """One steady-state frame in pipeline mode (see __init__).  Stream s_cam: [wait until the head that last used this
-        buffer set is done] -> input staging -> camera-stage graph.  Stream s_head: [wait for the camera stages] -> head graph."""
-        if self._pipe is None:
-            # the camera stages are the throughput-critical half: their stream gets the higher priority so that the head of the
-            # previous frame (latency-bound, few CUs) does not delay their workgroups (self.cam_priority, A/B in bench.py)
-            # pipeline_sets >= 3: two camera-stage streams.  A frame's per-camera stages are ~215 dependent launches, many of them one
-            # or two rounds of workgroups (stages 4-5, FPN, 2D head); the stages of the NEXT frame on a second stream fill their tails:
-            # two camera graphs take 4.66 ms per frame side by side against 5.62 ms back to back (profiles/r4/cam_overlap.txt)
-            ncs = max(1, min(int(self.pipeline_sets) - 1, int(self.cam_streams)))
-            self._pipe = dict(s_cams=[torch.cuda.Stream(self.dev, priority=self.cam_priority) for _ in range(ncs)], s_head=torch.cuda.Stream(self.dev), g_cam={}, g_head={}, outs={},
-                              cam_done={}, head_done={}, n_issued=0)
-        P = self._pipe
-        p = self._par
-        cur = torch.cuda.current_stream(self.dev)
-        here = torch.cuda.Event()
-        here.record(cur)                                  # the caller's stream up to this call: inputs, eager scene starts
-        img = data["img"][0] if data["img"].dim() == 5 else data["img"]
-        if p in P["g_cam"] and tuple(self._ins[p]["img"].shape) != tuple(img.shape):
-            # input shape changed: this parity's graphs replay on buffers that are about to be replaced
-            torch.cuda.synchronize(self.dev)
-            for k in ("g_cam", "g_head", "outs", "cam_done", "head_done"):
-                P[k].pop(p, None)
-        if p not in P["g_cam"]:
-            # first steady frame on this buffer set: capture its two graphs with the device quiet
-            torch.cuda.synchronize(self.dev)
-            dd = self._stage_inputs(data)
-            if (p, "tq") not in self._bufs:      # the query-major buffers and their constant rows exist before the capture
-                self._alloc_query_buffers(dd["img"].shape[0])
-            gc, gh = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
-            with torch.cuda.graph(gc):
-                st = self._camera_part(dd, pad_hw)
-            with torch.cuda.graph(gh):
-                outs = self._head_part(st, dd, img_metas, pad_hw)
-            P["g_cam"][p], P["g_head"][p], P["outs"][p] = gc, gh, outs
-            P["cam_done"][p], P["head_done"][p] = torch.cuda.Event(), torch.cuda.Event()
-            torch.cuda.synchronize(self.dev)
-            first = True
-        else:
-            first = False
-        s_cam = P["s_cams"][P["n_issued"] % len(P["s_cams"])]      # consecutive frames alternate between the camera streams
-        P["n_issued"] += 1
-        s_cam.wait_event(here)
-        for v in data.values():                           # the caller may free its input tensors right after this call
-            if isinstance(v, torch.Tensor) and v.is_cuda:
-                v.record_stream(s_cam)
-        with torch.cuda.stream(s_cam):
-            if not first:
-                s_cam.wait_event(P["head_done"][p])       # the head of the frame that last used this buffer set (inputs included)
-            self._stage_inputs(data)
-            P["g_cam"][p].replay()
-            P["cam_done"][p].record(s_cam)
-        with torch.cuda.stream(P["s_head"]):
-            P["s_head"].wait_event(here)
-            P["s_head"].wait_event(P["cam_done"][p])
-            P["g_head"][p].replay()
-            P["head_done"][p].record(P["s_head"])
-        self._ready = P["head_done"][p]
-        # the overflow flag this frame writes lives in ITS buffer set: bind it per frame (the replayed graph never runs the Python
-        # line that recorded it at capture time; ADVICE r3)
-        self._overflow = P["outs"][p].get("proposal_overflow")
-        return P["outs"][p]
+    def _capture_frame(self, dd, img_metas, pad_hw):
+        """FramePipeline's capture: the camera stages and the head of the current buffer set as two hipGraphs."""
+        gc, gh = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
+        with torch.cuda.graph(gc):
+            st = self._camera_part(dd, pad_hw)
+        with torch.cuda.graph(gh):
+            outs = self._head_part(st, dd, img_metas, pad_hw)
+        return gc, gh, outs, None
 
     def output_stream(self):
         """The stream the latest forward_frame's outputs are produced on."""
-        return self._pipe["s_head"] if (self.pipeline and self._pipe is not None and self._ready is not None) else torch.cuda.current_stream(self.dev)
+        return self._pipe.output_stream() if self.pipeline else torch.cuda.current_stream(self.dev)
 
     def wait_outputs(self):
         """Order the caller's current stream after the latest frame's outputs (a no-op outside pipeline mode)."""
@@ -1322,13 +1270,8 @@ class Far3DEngine:
             self._par = self._fidx % max(2, int(self.pipeline_sets))
             self._fidx += 1
             if steady:
-                return self._pipelined_frame(data, img_metas, pad_hw)
-            if self._pipe is not None:       # scene start: runs eagerly on the caller's stream, after everything in flight
-                cur = torch.cuda.current_stream(self.dev)
-                for sc in self._pipe["s_cams"]:
-                    cur.wait_stream(sc)
-                cur.wait_stream(self._pipe["s_head"])
-            self._ready = None
+                return self._pipe.frame(self._capture_frame, data, img_metas, pad_hw)
+            self._pipe.drain()               # scene start: runs eagerly on the caller's stream, after everything in flight
             outs = self._frame_body(self._stage_inputs(data), img_metas, pad_hw)
             self._overflow = outs.get("proposal_overflow")
             return outs

@@ -7,7 +7,7 @@ the reference's own benchmark protocol syncs around every frame (tools/analysis_
 `protocol.sync_per_frame`).  Measured basis (profiles/r4/stage_times_bf16.txt): 7 cameras in one batch 6.09 ms; two independent
 4-camera jobs side by side 3.15 ms per job, i.e. 0.79 ms per camera against 0.87.
 
-Mechanics (the engine's frame pipeline turned sideways): every camera group has its own buffer namespace (`engine._par = ("camgroup",
+Mechanics (the engine's frame pipeline, frame_pipeline.py, turned sideways): every camera group has its own buffer namespace (`engine._par = ("camgroup",
 g)`) and, in steady state, its own hipGraph replayed on its own high-priority stream; the groups write their value maps and
 adaptive-query records into ONE pair of persistent head-input buffers (camera-major, exactly what camera_stage of all cameras would
 have produced), and the head -- eager on the first frame of a scene, a hipGraph afterwards -- runs on the caller's stream after all
