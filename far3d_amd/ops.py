@@ -933,6 +933,72 @@ def attention_forward(q, k, v, num_heads=8, out=None, out_dtype=torch.float32, h
     return out
 
 
+def attention_batched(q, k, v, num_heads=8, attn_mask=None, key_padding_mask=None, out=None, out_dtype=torch.float32):
+    """Per sample and head softmax(q k^T / sqrt(d) + attn_mask + key padding) v in one launch (far3d_attention_batched).
+    q (B,Aq,E), k/v (B,Nk,E) f32|bf16 with unit inner stride (views of one (B,rows,3E) buffer are read in place); out (B,Aq,E).
+    attn_mask (Aq,Nk) or (B*num_heads,Aq,Nk): torch.bool / uint8 -> nonzero EXCLUDES the key; a float mask is added to the scores (may
+    hold -inf; a dtype other than float32 is cast on the host).  key_padding_mask (B,Nk) bool / uint8: nonzero excludes the key.
+    A query without any key left gets NaN in its whole row, as torch does."""
+    lib = _lib.require_device()
+    for t, n in ((q, "q"), (k, "k"), (v, "v")):
+        if not isinstance(t, torch.Tensor) or t.dim() != 3 or t.stride(2) != 1 or not t.is_cuda:
+            raise ValueError("attention_batched: %s must be a 3-D device tensor (B, rows, E) with unit inner stride" % n)
+    if not (q.dtype == k.dtype == v.dtype):
+        raise TypeError("attention_batched: q/k/v dtypes differ")
+    B, Aq, E = q.shape
+    Nk = k.shape[1]
+    if k.shape != (B, Nk, E) or v.shape != (B, Nk, E):
+        raise ValueError("attention_batched: k/v must be (%d, Nk, %d), got %s / %s" % (B, E, tuple(k.shape), tuple(v.shape)))
+    if E % num_heads:
+        raise ValueError("attention_batched: embed dim %d is not a multiple of num_heads %d" % (E, num_heads))
+    hd = E // num_heads
+    kind, mptr, ldm, mbs = 0, None, 0, 0
+    if attn_mask is not None:
+        if not isinstance(attn_mask, torch.Tensor) or not attn_mask.is_cuda:
+            raise ValueError("attention_batched: attn_mask must be a device tensor")
+        if attn_mask.dim() == 2:
+            want = (Aq, Nk)
+        elif attn_mask.dim() == 3:
+            want = (B * num_heads, Aq, Nk)
+        else:
+            want = None
+        if want is None or tuple(attn_mask.shape) != want:
+            raise ValueError("attention_batched: attn_mask must be (%d, %d) or (%d, %d, %d), got %s" %
+                             (Aq, Nk, B * num_heads, Aq, Nk, tuple(attn_mask.shape)))
+        if attn_mask.dtype in (torch.bool, torch.uint8):
+            kind = 1
+            attn_mask = attn_mask.view(torch.uint8) if attn_mask.dtype == torch.bool else attn_mask
+        elif attn_mask.is_floating_point():
+            kind = 2
+            attn_mask = attn_mask.float()
+        else:
+            raise TypeError("attention_batched: attn_mask dtype %s (bool, uint8 or a float type)" % attn_mask.dtype)
+        if attn_mask.stride(-1) != 1 or (attn_mask.dim() == 3 and attn_mask.stride(0) < 0):
+            attn_mask = attn_mask.contiguous()
+        mptr, ldm = _ptr(attn_mask), attn_mask.stride(-2)
+        mbs = attn_mask.stride(0) if attn_mask.dim() == 3 else 0
+    pptr = None
+    if key_padding_mask is not None:
+        if not isinstance(key_padding_mask, torch.Tensor) or not key_padding_mask.is_cuda:
+            raise ValueError("attention_batched: key_padding_mask must be a device tensor")
+        if tuple(key_padding_mask.shape) != (B, Nk):
+            raise ValueError("attention_batched: key_padding_mask must be (%d, %d), got %s" % (B, Nk, tuple(key_padding_mask.shape)))
+        if key_padding_mask.dtype not in (torch.bool, torch.uint8):
+            raise TypeError("attention_batched: key_padding_mask dtype %s (bool or uint8)" % key_padding_mask.dtype)
+        key_padding_mask = key_padding_mask.contiguous()
+        key_padding_mask = key_padding_mask.view(torch.uint8) if key_padding_mask.dtype == torch.bool else key_padding_mask
+        pptr = _ptr(key_padding_mask)
+    if out is None:
+        out = torch.empty((B, Aq, E), dtype=out_dtype, device=q.device)
+    elif tuple(out.shape) != (B, Aq, E) or out.stride(2) != 1 or not out.is_cuda:
+        raise ValueError("attention_batched: out must be a (%d, %d, %d) device tensor with unit inner stride" % (B, Aq, E))
+    _lib.check(lib.far3d_attention_batched(_ptr(q), _ptr(k), _ptr(v), _dt(q), _ptr(out), _dt(out), B, Aq, Nk, num_heads, hd,
+                                           q.stride(1), k.stride(1), v.stride(1), out.stride(1),
+                                           q.stride(0), k.stride(0), v.stride(0), out.stride(0), float(hd) ** -0.5,
+                                           mptr, kind, ldm, mbs, pptr, _stream(q)), "far3d_attention_batched")
+    return out
+
+
 def layernorm(x, gamma, beta, eps=1e-5, act=None, add=None, out=None, add_dtype=torch.float32, bf16_copy=False, y2=None, yb=None,
               out_rows=None):
     """Returns LN(x); with `add`: (LN(x), LN(x)+add [add_dtype]); with bf16_copy also a bf16 copy of LN(x) (last).

@@ -260,35 +260,71 @@ class MultiheadAttention(nn.Module):
                 key_padding_mask=None, **kwargs):
         """mmcv semantics (in-tree statement models/utils/petr_transformer.py:286-326): key/value default to query, identity to
         query, key_pos to query_pos when shapes agree; positions are added to q and k only; out = identity + out_proj(attn).
-        One sample (the reference tests with B=1), no masks (inference)."""
-        _lib.require_device()
-        if attn_mask is not None or key_padding_mask is not None:
-            raise NotImplementedError("far3d_amd MultiheadAttention: masks are a training-time (denoising) feature")
+        Any batch size; attn_mask (Aq, Nk) or (bs * num_heads, Aq, Nk), bool (True = the key is excluded) or float (added to the
+        scores), and key_padding_mask (bs, Nk) bool with torch.nn.MultiheadAttention's semantics.  One sample without masks runs the
+        one-sample kernel (far3d_attention_forward), everything else ONE far3d_attention_batched launch; the projections run on all
+        bs * rows at once."""
         key = query if key is None else key
         value = key if value is None else value
         identity = query if identity is None else identity
         if key_pos is None and query_pos is not None and query_pos.shape == key.shape:
             key_pos = query_pos
+        bdim = 0 if self.batch_first else 1
+        bs, Aq, Nk = query.shape[bdim], query.shape[1 - bdim], key.shape[1 - bdim]
+        if query.dim() != 3 or key.dim() != 3 or key.shape[bdim] != bs or value.shape != key.shape:
+            raise ValueError("MultiheadAttention: query / key / value must be 3-D with one batch size and key.shape == value.shape, got "
+                             "%s / %s / %s" % (tuple(query.shape), tuple(key.shape), tuple(value.shape)))
+        if attn_mask is not None and tuple(attn_mask.shape) not in ((Aq, Nk), (bs * self.num_heads, Aq, Nk)):
+            raise ValueError("MultiheadAttention: attn_mask must be (%d, %d) or (%d, %d, %d), got %s" %
+                             (Aq, Nk, bs * self.num_heads, Aq, Nk, tuple(attn_mask.shape)))
+        if key_padding_mask is not None and tuple(key_padding_mask.shape) != (bs, Nk):
+            raise ValueError("MultiheadAttention: key_padding_mask must be (%d, %d), got %s" % (bs, Nk, tuple(key_padding_mask.shape)))
+        _lib.require_device()
+        if bs != 1 or attn_mask is not None or key_padding_mask is not None:
+            return self._forward_batched(query, key, value, identity, query_pos, key_pos, attn_mask, key_padding_mask)
         sq = (lambda t: t[0] if self.batch_first else t[:, 0])
-        if (query.shape[0] if self.batch_first else query.shape[1]) != 1:
-            raise NotImplementedError("far3d_amd MultiheadAttention runs one sample per call")
         q = sq(query) + (sq(query_pos) if query_pos is not None else 0)
         k = sq(key) + (sq(key_pos) if key_pos is not None else 0)
         v, idn = sq(value), sq(identity).float().contiguous()
-        dev, E = q.device, self.embed_dims
-        dw = _engine.PRECISIONS[self.precision]["dec"]
+        dw, pq, pkk, pv, po = self._pack(q.device)
+        cast = lambda t: t.to(dw).contiguous()
+        Q, K_, V = ops.linear(cast(q), pq, out_dtype=dw), ops.linear(cast(k), pkk, out_dtype=dw), ops.linear(cast(v), pv, out_dtype=dw)
+        att = ops.attention_forward(Q, K_, V, num_heads=self.num_heads, out_dtype=dw)
+        out = ops.linear(att, po, res=idn)
+        return out[None] if self.batch_first else out[:, None]
+
+    def _pack(self, dev):
+        E, dw = self.embed_dims, _engine.PRECISIONS[self.precision]["dec"]
         ver = (int(self.attn.in_proj_weight._version), str(dev), self.precision)
         if self._packed is None or self._packed[0] != ver:
             w, b = self.attn.in_proj_weight.data, self.attn.in_proj_bias.data
             pk = lambda ww, bb: ops.PackedConv(ww, bb, dtype=dw, device=dev)
             self._packed = (ver, pk(w[:E], b[:E]), pk(w[E:2 * E], b[E:2 * E]), pk(w[2 * E:], b[2 * E:]),
                             pk(self.attn.out_proj.weight.data, self.attn.out_proj.bias.data))
-        _, pq, pkk, pv, po = self._packed
-        cast = lambda t: t.to(dw).contiguous()
-        Q, K_, V = ops.linear(cast(q), pq, out_dtype=dw), ops.linear(cast(k), pkk, out_dtype=dw), ops.linear(cast(v), pv, out_dtype=dw)
-        att = ops.attention_forward(Q, K_, V, num_heads=self.num_heads, out_dtype=dw)
-        out = ops.linear(att, po, res=idn)
-        return out[None] if self.batch_first else out[:, None]
+        return (dw,) + self._packed[1:]
+
+    def _forward_batched(self, query, key, value, identity, query_pos, key_pos, attn_mask, key_padding_mask):
+        """Any batch, with masks: projections over all bs * rows, one far3d_attention_batched launch on (bs, rows, E) views."""
+        bf = (lambda t: t if self.batch_first else t.transpose(0, 1))
+        q = bf(query) + (bf(query_pos) if query_pos is not None else 0)
+        k = bf(key) + (bf(key_pos) if key_pos is not None else 0)
+        v, idn = bf(value), bf(identity).float().contiguous()
+        bs, Aq, E = q.shape
+        Nk = k.shape[1]
+        dw, pq, pkk, pv, po = self._pack(q.device)
+        cast = lambda t: t.to(dw).reshape(-1, E).contiguous()
+        Q = ops.linear(cast(q), pq, out_dtype=dw).view(bs, Aq, E)
+        K_ = ops.linear(cast(k), pkk, out_dtype=dw).view(bs, Nk, E)
+        V = ops.linear(cast(v), pv, out_dtype=dw).view(bs, Nk, E)
+        if attn_mask is not None:
+            attn_mask = attn_mask.to(q.device)
+        if key_padding_mask is not None:
+            key_padding_mask = key_padding_mask.to(q.device)
+            if key_padding_mask.dtype not in (torch.bool, torch.uint8):
+                raise TypeError("MultiheadAttention: key_padding_mask dtype %s (bool or uint8)" % key_padding_mask.dtype)
+        att = ops.attention_batched(Q, K_, V, num_heads=self.num_heads, attn_mask=attn_mask, key_padding_mask=key_padding_mask, out_dtype=dw)
+        out = ops.linear(att.view(bs * Aq, E), po, res=idn.view(bs * Aq, E)).view(bs, Aq, E)
+        return out if self.batch_first else out.transpose(0, 1).contiguous()
 
 
 # ------------------------------------------------------------------------------------------------ transformer containers
@@ -316,8 +352,58 @@ class Detr3DTemporalDecoderLayer(nn.Module):
                                    nn.Linear(self.ffn_dim, self.embed_dims), nn.Dropout(0.0))
         self.ffns = nn.ModuleList([ffn])
         self.norms = nn.ModuleList([nn.LayerNorm(self.embed_dims) for _ in range(3)])
+        self.precision = "bf16"
+        self._packed = None
         for p in self.parameters():
             p.requires_grad_(False)
+
+    def _pack(self, dev):
+        l0, l1 = self.ffns[0].layers[0][0], self.ffns[0].layers[1]
+        ver = (int(l0.weight._version) + int(l1.weight._version) + sum(int(n.weight._version) for n in self.norms), str(dev), self.precision)
+        if self._packed is None or self._packed[0] != ver:
+            dw = _engine.PRECISIONS[self.precision]["dec"]
+            pk = lambda lin: ops.PackedConv(lin.weight.data, lin.bias.data, dtype=dw, device=dev)
+            self._packed = (ver, dw, pk(l0), pk(l1), [(n.weight.data.float().to(dev), n.bias.data.float().to(dev), n.eps) for n in self.norms])
+        return self._packed[1:]
+
+    @torch.no_grad()
+    def forward(self, query, query_pos, mlvl_feats, temp_memory, temp_pos, reference_points, spatial_flatten, level_start_index,
+                pc_range, lidar2img, img_metas, attn_masks=None, query_key_padding_mask=None, key_padding_mask=None):
+        """models/utils/detr3d_transformer.py:311-422 for the post-norm order with batch_first=True: self-attention over the keys
+        [query | temp_memory] with positions [query_pos | temp_pos] (temp_memory None: over the queries), LayerNorm, aggregation,
+        LayerNorm, FFN (ReLU, residual), LayerNorm -> (bs, A, C) f32.  attn_masks: None, one tensor or a list of two; like the
+        reference, only the self-attention reads its entry (and query_key_padding_mask as its key padding; key_padding_mask is unused
+        there too).  Composed from the two attention modules' own forwards, ops.layernorm and ops.linear; any batch size."""
+        if not self.batch_first:
+            raise NotImplementedError("Detr3DTemporalDecoderLayer.forward: batch_first=False is not implemented (the reference config "
+                                      "sets batch_first=True)")
+        if attn_masks is None:
+            attn_masks = [None] * len(self.attentions)
+        elif isinstance(attn_masks, torch.Tensor):
+            attn_masks = [attn_masks] * len(self.attentions)
+        elif len(attn_masks) != len(self.attentions):
+            raise ValueError("Detr3DTemporalDecoderLayer.forward: %d attn_masks for %d attention modules" %
+                             (len(attn_masks), len(self.attentions)))
+        _lib.require_device()
+        for a in self.attentions:
+            a.precision = self.precision
+        bs, A, C = query.shape
+        dw, p0, p1, norms = self._pack(query.device)
+        ln = lambda x, i: ops.layernorm(x.reshape(bs * A, C), norms[i][0], norms[i][1], eps=norms[i][2]).view(bs, A, C)
+        if temp_memory is not None:
+            temp_key = torch.cat([query, temp_memory], dim=1)
+            temp_pos = torch.cat([query_pos, temp_pos], dim=1)
+        else:
+            temp_key, temp_pos = query, query_pos
+        x = self.attentions[0](query, temp_key, temp_key, None, query_pos=query_pos, key_pos=temp_pos, attn_mask=attn_masks[0],
+                               key_padding_mask=query_key_padding_mask)
+        x = ln(x.float().contiguous(), 0)
+        x = self.attentions[1](x, query_pos, mlvl_feats, reference_points, spatial_flatten, level_start_index, pc_range, lidar2img, img_metas)
+        x = ln(x.float().contiguous(), 1)
+        rows = x.view(bs * A, C)
+        hid = ops.linear(rows.to(dw).contiguous(), p0, act="relu", out_dtype=dw)
+        x = ops.linear(hid, p1, res=rows).view(bs, A, C)
+        return ln(x, 2)
 
 
 @TRANSFORMER_LAYER_SEQUENCE.register_module()
@@ -326,6 +412,19 @@ class Detr3DTransformerDecoder(nn.Module):
         super().__init__()
         self.embed_dims, self.num_layers = embed_dims, num_layers
         self.layers = nn.ModuleList([TRANSFORMER_LAYER.build(copy.deepcopy(transformerlayers)) for _ in range(num_layers)])
+        self.precision = "bf16"
+
+    @torch.no_grad()
+    def forward(self, query, query_pos, mlvl_feats, temp_memory, temp_pos, reference_points, spatial_flatten, level_start_index,
+                pc_range, lidar2img, img_metas, attn_masks):
+        """models/utils/detr3d_transformer.py:138-190: the layers in sequence -> stacked (num_layers, bs, A, C) f32 states."""
+        intermediate = []
+        for layer in self.layers:
+            layer.precision = self.precision
+            query = layer(query, query_pos, mlvl_feats, temp_memory, temp_pos, reference_points, spatial_flatten, level_start_index,
+                          pc_range, lidar2img, img_metas, attn_masks)
+            intermediate.append(query)
+        return torch.stack(intermediate)
 
 
 @TRANSFORMER.register_module()
@@ -333,11 +432,22 @@ class Detr3DTransformer(nn.Module):
     def __init__(self, decoder=None, **kwargs):
         super().__init__()
         self.decoder = TRANSFORMER_LAYER_SEQUENCE.build(decoder)
+        self.precision = "bf16"
 
     def init_weights(self):
         for m in self.modules():
             if hasattr(m, "init_weight"):
                 m.init_weight()
+
+    @torch.no_grad()
+    def forward(self, query, query_pos, feat_flatten, spatial_flatten, level_start_index, temp_memory, temp_pos, attn_masks,
+                reference_points, pc_range, data, img_metas):
+        """models/utils/detr3d_transformer.py:58-124, the call of the reference's FarHead (models/dense_heads/farhead.py:643):
+        -> (num_layers, bs, A, C) f32 decoder states.  No nan_to_num here: the caller's head applies it, as in the reference."""
+        self.decoder.precision = self.precision
+        return self.decoder(query=query, query_pos=query_pos, mlvl_feats=feat_flatten, temp_memory=temp_memory, temp_pos=temp_pos,
+                            reference_points=reference_points, spatial_flatten=spatial_flatten, level_start_index=level_start_index,
+                            pc_range=pc_range, lidar2img=data["lidar2img"], img_metas=img_metas, attn_masks=attn_masks)
 
 
 # ------------------------------------------------------------------------------------------------ coder

@@ -274,6 +274,30 @@ int far3d_attention_forward(const void* q, const void* k, const void* v, int dty
  * the exp differ at the last bit). */
 int far3d_attention_f32_variant(int variant);
 
+/* Batched, masked multi-head attention core: per sample b and head h
+ *   out[b] = softmax(q[b] k[b]^T * scale + M[b,h] + P[b]) v[b]      (flash-style, no score tensor in HBM; ONE launch for all samples).
+ * The attention of torch.nn.MultiheadAttention with `attn_mask` and `key_padding_mask`, as mmcv's wrapper calls it for any batch size
+ *   (call site models/utils/detr3d_transformer.py:385-394; the mask is the one models/dense_heads/farhead.py `prepare_for_dn` builds).
+ *   far3d_attention_forward stays the engine's one-sample kernel; this entry does not know the engine's key hole.
+ * q (B, Aq, heads*32), k/v (B, Nk, heads*32) of `dtype` (F32 -> exact fp32 MFMA, BF16 -> bf16 MFMA): row strides ldq/ldk/ldv and batch
+ *   strides bsq/bsk/bsv in elements (views of one (B, rows, 768) QKV buffer are read in place); out (B, Aq, heads*32) of out_dt
+ *   (f32 | bf16), row stride ldo, batch stride bso.  head_dim must be 32.  Pointers, row and batch strides 16-byte aligned.
+ * attn_mask, mask_kind: 0 = none (attn_mask ignored); 1 = bytes with torch.bool semantics, nonzero = the key is EXCLUDED for that query;
+ *   2 = f32 added to the scaled scores (may hold -inf).  One (Aq, Nk) matrix with row stride ldm >= Nk per (sample, head) pair, matrix
+ *   b * heads + h at attn_mask + (b * heads + h) * mask_bstride elements -- the (B*heads, Aq, Nk) layout of torch; mask_bstride = 0: one
+ *   matrix shared by all samples and heads.
+ * key_padding (optional, NULL = none): (B, Nk) contiguous bytes, nonzero = the key is excluded for every query of the sample.
+ * A query whose keys are all excluded gets NaN in every element of its row (torch: 0 / 0); other rows are unaffected.  K / V rows of
+ *   excluded keys must hold finite numbers (an excluded probability is an exact 0 that still multiplies V).
+ * Probabilities are exp2((s - m) * log2e) with the running maximum m subtracted first; far3d_attention_f32_variant is not read.  The
+ *   bits of sample b depend on its own operands only (not on B).
+ * Bad arguments (null q/k/v/out, head_dim != 32, B / Aq / Nk / heads < 1, unknown mask_kind, ldm < Nk, misalignment) return
+ *   FAR3D_ERR_ARG, set far3d_last_error() and launch nothing. */
+int far3d_attention_batched(const void* q, const void* k, const void* v, int dtype, void* out, int out_dt, int B, int Aq, int Nk,
+                            int heads, int head_dim, int ldq, int ldk, int ldv, int ldo, long bsq, long bsk, long bsv, long bso,
+                            float scale, const void* attn_mask, int mask_kind, int ldm, long mask_bstride,
+                            const uint8_t* key_padding, void* stream);
+
 /* y = act(LayerNorm_C(x) * gamma + beta); optional y2 = y + add (next GEMM's "query + query_pos").
  * Replaces nn.LayerNorm at ref models/utils/detr3d_transformer.py:304-307,398-400,506-512 and
  * models/dense_heads/farhead.py:230-239,274-277.  x,y,add,y2: f32 rows with strides ldx,ldy,lda,ldy2 (multiples of 4);
