@@ -599,7 +599,23 @@ extern "C" int far3d_prof_set_agg_timestamps(long long* buf) {
 // 8 group weights into per-token accumulators, ~100 instead of ~340 VALU instructions per patch: build phase 2.2x SLOWER, 35 us per
 // launch); patches of 65..128 tokens merged in two passes instead of the per-corner fallback (78 instead of 92 rows per query, but
 // 23.2 vs 21.2 us); three / four waves per query with one shared, evenly split work list (24.1 .. 28.3 us).
-template <typename TV, int PT, int OPT = 0, int CAPW = AGG7_CAPW>
+//
+// BATCHED (far3d_aggregate_batched; kernels 7 and 8): a batch of samples in one launch.  A workgroup is still one query of one sample and
+// nothing in it knows about the others: the sample is a second index that moves the operand bases, and the body behind the bases is the
+// one-sample code, so out[b] has the bits of the one-sample launch on sample b.  The sample is blockIdx.y and gridDim.x stays
+// 8 * q_per_xcd: workgroups are dispatched in linear order (x fastest) round-robin over the 8 XCDs, so with gridDim.x a multiple of 8
+// `blockIdx.x & 7` still names the blocks that share an XCD and a sample's queries keep the placement of the one-sample launch
+// (flattening B * A through q_per_xcd needs a division per workgroup to find the sample and makes the placement a function of B; it
+// was not measured).  Placement is a speed heuristic only; no result depends on it.  The per-sample extents are formed in 64 bits
+// (B * N * S * C may pass 2^31); inside a sample the 32-bit offsets stay.  No kernel argument is added: the extents come from AggParams,
+// and the one-sample instantiations (BATCHED = false) never look at blockIdx.y.
+#define AGG_SAMPLE_BASES(b)                                                                                                       \
+  do {                                                                                                                            \
+    feat += (b) * prm.N * prm.S * 256; ref += (b) * prm.A * 3; offs += (b) * prm.A * prm.ldO; U += (b) * prm.A * prm.ldU;          \
+    l2i += (b) * prm.N * 16;                                                                                                      \
+    out = reinterpret_cast<char*>(out) + (b) * prm.A * 256 * (prm.out_dt == FAR3D_DT_F32 ? 4 : 2);                                \
+  } while (0)
+template <typename TV, int PT, int OPT = 0, int CAPW = AGG7_CAPW, bool BATCHED = false>
 __global__ __launch_bounds__(128) void aggregate_v7_kernel(const TV* __restrict__ feat, const float* __restrict__ ref,
                                                            const float* __restrict__ offs, const float* __restrict__ l2i,
                                                            const float* __restrict__ U, const float* __restrict__ Vc,
@@ -611,6 +627,11 @@ __global__ __launch_bounds__(128) void aggregate_v7_kernel(const TV* __restrict_
   const int t = threadIdx.x, lane = t & 63, wv = __builtin_amdgcn_readfirstlane(t >> 6);   // wave index: scalar
   const int P = PT ? PT : prm.P, L = prm.L, N = prm.N;
   const int NP = N * P, J = L * P, NLP = NP * L;
+  if constexpr (BATCHED) {
+    const long b = blockIdx.y;
+    AGG_SAMPLE_BASES(b);
+    Vc += b * N * (J * 8);
+  }
   float* w_s = reinterpret_cast<float*>(smem);                            // [NLP][8] exp(logit - max): UN-normalised weights
   float2* uv_s = reinterpret_cast<float2*>(w_s + NLP * 8);                // [NP] normalised image coordinates
   float4* bb_s = reinterpret_cast<float4*>(uv_s + ((NP + 1) & ~1));       // [AGG4_MAX_N] (umin, umax, vmin, vmax) per camera
@@ -1055,7 +1076,9 @@ __device__ __forceinline__ void agg8_gather(const TV* __restrict__ feat, const u
 // global workspace (per wave: AGG_GCAP entries of offset + 8 weights, count; per slot: the 8 softmax denominators) instead of being
 // gathered; aggregate_gather_kernel below is the other half.  VERDICT r5 item 3 (c) asked for the split to be measured.
 #define AGG_GCAP 1024
-template <typename TV, int PT, int PRIO = 1, int LOOPNB = 4, int CAP = AGG8_CAPW, bool SPLIT = false, bool SORTED = false, int DEAL_ = -1, int PHASE = 0>
+// BATCHED: far3d_aggregate_batched's instantiations, blockIdx.y = sample (AGG_SAMPLE_BASES above kernel 7); without perm, SPLIT, SORTED.
+template <typename TV, int PT, int PRIO = 1, int LOOPNB = 4, int CAP = AGG8_CAPW, bool SPLIT = false, bool SORTED = false, int DEAL_ = -1, int PHASE = 0,
+          bool BATCHED = false>
 __global__ __launch_bounds__(128, 4) void aggregate_v8_kernel(const TV* __restrict__ feat, const float* __restrict__ ref,
                                                            const float* __restrict__ offs, const float* __restrict__ l2i,
                                                            const float* __restrict__ U, const float* __restrict__ tab,
@@ -1075,6 +1098,12 @@ __global__ __launch_bounds__(128, 4) void aggregate_v8_kernel(const TV* __restri
   const int t = threadIdx.x, lane = t & 63, wv = __builtin_amdgcn_readfirstlane(t >> 6);
   const int P = PT ? PT : prm.P, L = prm.L, N = prm.N;
   const int n4 = L * P * 2;                                               // float4 per camera row of the tables (<= 128)
+  if constexpr (BATCHED) {
+    static_assert(!SPLIT && !SORTED && PHASE == 0, "the batched launch has no sibling split, sorted mode or list-build phase");
+    const long b = blockIdx.y;
+    AGG_SAMPLE_BASES(b);
+    tab += b * (2 + N) * (n4 * 4);
+  }
   constexpr int CAPT = CAP + AGG8_PAD;
   float2* pxy_s = reinterpret_cast<float2*>(smem);                        // [8][4][16] pixel coordinates per (camera, level, point)
   float* stat_s = reinterpret_cast<float*>(pxy_s + 8 * 4 * 16);           // [8] softmax denominators (+ 8 pad)
@@ -1874,5 +1903,76 @@ extern "C" int far3d_aggregate_forward(const void* feat, int feat_dtype, const f
     }
   }
   FAR3D_CHECK_LAUNCH("far3d_aggregate_forward");
+  return FAR3D_OK;
+}
+
+// A batch of samples through kernel 8 / kernel 7 in one launch (include/far3d_hip.h).  The checks are far3d_aggregate_forward's, per
+// sample; what belongs to the engine's one-sample call (perm, sorted mode, sibling split, A/B variants) has no batched form.
+extern "C" int far3d_aggregate_batched(const void* feat, int feat_dtype, const float* ref, const float* offsets,
+                                       const float* lidar2img, const float* U, const float* Vc, const float* cam_tables,
+                                       void* out, int out_dt, int B, int A, int N, int S, int C, int G, int P, int L,
+                                       const int32_t* level_hw, const int32_t* level_start, const float* pc_range,
+                                       float pad_h, float pad_w, int ldU, int ldOffs, void* stream) {
+  FAR3D_CHECK_ARG(C == 256 && G == 8, "far3d_aggregate_batched: fused kernel is built for C=256,G=8 (got C=%d G=%d)", C, G);
+  FAR3D_CHECK_ARG(L >= 1 && L <= AGG_MAX_L, "far3d_aggregate_batched: L=%d out of range [1,%d]", L, AGG_MAX_L);
+  FAR3D_CHECK_ARG(N >= 1 && N <= AGG4_MAX_N && P >= 1 && N * P <= 256 && N * P * L <= AGG_MAX_NLP,
+                  "far3d_aggregate_batched: N=%d (<=%d), N*P=%d (<=256) or N*P*L=%d (<=%d) too large", N, AGG4_MAX_N, N * P, N * P * L, AGG_MAX_NLP);
+  FAR3D_CHECK_ARG(feat_dtype == FAR3D_DT_F32 || feat_dtype == FAR3D_DT_BF16,
+                  "far3d_aggregate_batched: unsupported feature dtype %d", feat_dtype);
+  FAR3D_CHECK_ARG(out_dt == FAR3D_DT_F32 || out_dt == FAR3D_DT_BF16, "far3d_aggregate_batched: unsupported output dtype %d", out_dt);
+  FAR3D_CHECK_ARG(B >= 0 && B <= 65535, "far3d_aggregate_batched: B=%d out of range [0,65535] (the sample is the grid's y index)", B);
+  FAR3D_CHECK_ARG(A >= 0 && S > 0 && (long)N * S * C < (1L << 31),
+                  "far3d_aggregate_batched: bad sizes A=%d S=%d (N*S*C of one sample must fit int32)", A, S);
+  if (B == 0 || A == 0) return FAR3D_OK;
+  FAR3D_CHECK_ARG(feat && ref && offsets && lidar2img && U && (Vc || cam_tables) && out && level_hw && level_start && pc_range,
+                  "far3d_aggregate_batched: null pointer argument");
+  const size_t esz = feat_dtype == FAR3D_DT_F32 ? 4 : 2;
+  const bool v8 = cam_tables && N <= 8 && P <= 16 && (size_t)N * S * C * esz < (1ull << 32);     // far3d_aggregate_forward's variant 0
+  FAR3D_CHECK_ARG(v8 || Vc, "far3d_aggregate_batched: kernel 7 (no cam_tables, N=%d > 8, P=%d > 16 or a sample's value maps >= 4 GiB) needs Vc", N, P);
+  AggParams prm;
+  prm.A = A; prm.N = N; prm.S = S; prm.P = P; prm.L = L;
+  for (int l = 0; l < AGG_MAX_L; ++l) {
+    prm.H[l] = l < L ? level_hw[2 * l] : 1;
+    prm.W[l] = l < L ? level_hw[2 * l + 1] : 1;
+    prm.start[l] = l < L ? level_start[l] : 0;
+    if (l < L)
+      FAR3D_CHECK_ARG(prm.H[l] > 0 && prm.W[l] > 0 && prm.start[l] >= 0 && prm.start[l] + prm.H[l] * prm.W[l] <= S,
+                      "far3d_aggregate_batched: level %d (%dx%d @%d) exceeds S=%d", l, prm.H[l], prm.W[l], prm.start[l], S);
+  }
+  for (int d = 0; d < 3; ++d) { prm.pc_lo[d] = pc_range[d]; prm.pc_span[d] = pc_range[3 + d] - pc_range[d]; }
+  prm.pad_w = pad_w; prm.pad_h = pad_h;
+  prm.ipw = 1.f / pad_w; prm.iph = 1.f / pad_h;
+  for (int l = 0; l < AGG_MAX_L; ++l) { prm.Wf[l] = (float)prm.W[l]; prm.Hf[l] = (float)prm.H[l]; }
+  prm.q_per_xcd = cdiv(A, 8);
+  prm.split_part = nullptr; prm.split_tick = nullptr; prm.split_extra = 0;
+  prm.out_dt = out_dt;
+  prm.ldU = ldU > 0 ? ldU : L * P * G;
+  prm.ldO = ldOffs > 0 ? ldOffs : P * 3;
+  FAR3D_CHECK_ARG(prm.ldU >= L * P * G && prm.ldU % 4 == 0 && ((uintptr_t)U % 16) == 0 && prm.ldO >= P * 3,
+                  "far3d_aggregate_batched: U rows must be 16-byte aligned (ldU=%d) and strides >= row length", prm.ldU);
+  const dim3 grid(8 * prm.q_per_xcd, B);       // x: a multiple of 8 (blockIdx.x & 7 = XCD), y: the sample
+  hipStream_t st = (hipStream_t)stream;
+  const int* no_perm = nullptr;
+  if (v8) {
+    const float4* no_qbase = nullptr;
+    if (feat_dtype == FAR3D_DT_F32) {
+      if (P == 13) hipLaunchKernelGGL((aggregate_v8_kernel<float, 13, 1, 4, AGG8_CAPW, false, false, -1, 0, true>), grid, dim3(128), AGG8_LDS, st, (const float*)feat, ref, offsets, lidar2img, U, cam_tables, no_perm, out, prm, no_qbase);
+      else hipLaunchKernelGGL((aggregate_v8_kernel<float, 0, 1, 4, AGG8_CAPW, false, false, -1, 0, true>), grid, dim3(128), AGG8_LDS, st, (const float*)feat, ref, offsets, lidar2img, U, cam_tables, no_perm, out, prm, no_qbase);
+    } else {
+      if (P == 13) hipLaunchKernelGGL((aggregate_v8_kernel<bf16_t, 13, 1, 4, AGG8_CAPW, false, false, -1, 0, true>), grid, dim3(128), AGG8_LDS, st, (const bf16_t*)feat, ref, offsets, lidar2img, U, cam_tables, no_perm, out, prm, no_qbase);
+      else hipLaunchKernelGGL((aggregate_v8_kernel<bf16_t, 0, 1, 4, AGG8_CAPW, false, false, -1, 0, true>), grid, dim3(128), AGG8_LDS, st, (const bf16_t*)feat, ref, offsets, lidar2img, U, cam_tables, no_perm, out, prm, no_qbase);
+    }
+  } else {
+    const int NP = N * P;
+    const size_t lds7 = (size_t)NP * L * 32 + (size_t)((NP + 1) & ~1) * 8 + AGG4_MAX_N * 16 + 32 * 4 + AGG4_MAX_N * 4 + (size_t)2 * AGG7_CAPW * 36;
+    if (feat_dtype == FAR3D_DT_F32) {
+      if (P == 13) hipLaunchKernelGGL((aggregate_v7_kernel<float, 13, 0, AGG7_CAPW, true>), grid, dim3(128), lds7, st, (const float*)feat, ref, offsets, lidar2img, U, Vc, no_perm, out, prm);
+      else hipLaunchKernelGGL((aggregate_v7_kernel<float, 0, 0, AGG7_CAPW, true>), grid, dim3(128), lds7, st, (const float*)feat, ref, offsets, lidar2img, U, Vc, no_perm, out, prm);
+    } else {
+      if (P == 13) hipLaunchKernelGGL((aggregate_v7_kernel<bf16_t, 13, 0, AGG7_CAPW, true>), grid, dim3(128), lds7, st, (const bf16_t*)feat, ref, offsets, lidar2img, U, Vc, no_perm, out, prm);
+      else hipLaunchKernelGGL((aggregate_v7_kernel<bf16_t, 0, 0, AGG7_CAPW, true>), grid, dim3(128), lds7, st, (const bf16_t*)feat, ref, offsets, lidar2img, U, Vc, no_perm, out, prm);
+    }
+  }
+  FAR3D_CHECK_LAUNCH("far3d_aggregate_batched");
   return FAR3D_OK;
 }

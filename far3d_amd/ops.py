@@ -276,6 +276,51 @@ def _agg_batched(ref, offsets, lidar2img, U, Vc, who):
     return B, A, N, ref, _batch_rows(offsets, B, A, "offsets", who), lidar2img, _batch_rows(U, B, A, "U", who), Vc
 
 
+def aggregate_batched(feat, ref, offsets, lidar2img, U, Vc, level_hw, level_start, pc_range, pad_hw,
+                      num_groups=8, out=None, out_dtype=torch.float32, tables=None):
+    """aggregate_forward for a batch of samples in ONE launch (far3d_aggregate_batched): the fused kernel with the sample as a second
+    grid index.  feat (B*N,S,256) or (B,N,S,256) f32|bf16; ref (B,A,3); offsets (B,A,P,3) or (B,A,P*3); lidar2img (B,N,4,4);
+    U (B,A,L*P*G); Vc (B,N,L*P*G) -- the batched operands agg_operands takes (or one sample's, without B); U / offsets may be
+    row-strided views (column blocks of a merged-GEMM output; U's stride a multiple of 4 floats).  tables: agg_tables(Vc)
+    (B, 2+N, L*P*G), computed here (one more launch) when kernel 8 applies and the caller did not pass them.  Returns (B,A,256) of
+    out_dtype; out[b] has the bits of aggregate_forward on sample b, whatever B is.  The shape family is aggregate_fused_supported's."""
+    lib = _lib.require_device()
+    B, A, N, ref, offs, l2i, U2, Vc = _agg_batched(ref, offsets, lidar2img, U, Vc, "aggregate_batched")
+    _chk(feat, "feat")
+    if feat.dim() == 4:
+        feat = feat.reshape(-1, *feat.shape[2:])
+    if feat.dim() != 3 or feat.shape[0] != B * N:
+        raise ValueError("aggregate_batched: feat %s does not hold B*N = %d*%d maps (S, C)" % (tuple(feat.shape), B, N))
+    _, S, C = feat.shape
+    L, G = len(level_hw), int(num_groups)
+    P = offs.shape[1] // 3
+    J = L * P * G
+    if offs.shape[1] != P * 3 or U2.shape[1] != J or Vc.shape[2] != J:
+        raise ValueError("aggregate_batched: inconsistent shapes offsets%s U%s Vc%s (L=%d P=%d G=%d)" %
+                         (tuple(offs.shape), tuple(U2.shape), tuple(Vc.shape), L, P, G))
+    if out is None:
+        out = torch.empty((B, A, C), dtype=out_dtype, device=feat.device)
+    else:
+        _chk(out, "out", ndim=3)
+        if tuple(out.shape) != (B, A, C):
+            raise ValueError("aggregate_batched: out must be (B,A,C) = %s, got %s" % ((B, A, C), tuple(out.shape)))
+    if tables is None and B * A > 0 and N <= 8 and P <= 16:
+        tables = agg_tables(Vc)
+    if tables is not None:
+        _chk(tables, "tables", torch.float32, 3)
+        if tuple(tables.shape) != (B, 2 + N, J):
+            raise ValueError("aggregate_batched: tables must be (B, 2+N, L*P*G) = %s, got %s" % ((B, 2 + N, J), tuple(tables.shape)))
+    hw_keep, hw_p = _host_i32([list(x) for x in level_hw])
+    st_keep, st_p = _host_i32(list(level_start))
+    pc_keep, pc_p = _host_f32(list(pc_range))
+    _lib.check(lib.far3d_aggregate_batched(_ptr(feat), _dt(feat), _ptr(ref), _ptr(offs), _ptr(l2i), _ptr(U2), _ptr(Vc),
+                                           _ptr(tables) if tables is not None else None, _ptr(out), _dt(out), B, A, N, S, C, G, P, L,
+                                           hw_p, st_p, pc_p, float(pad_hw[0]), float(pad_hw[1]),
+                                           U2.stride(0) if B * A > 0 else 0, offs.stride(0) if B * A > 0 else 0, _stream(feat)),
+               "far3d_aggregate_batched")
+    return out
+
+
 def agg_operands(ref, offsets, lidar2img, U, Vc, num_levels, num_groups, pc_range, pad_hw, expand=True, key_points=False):
     """The two MSDA operands of the aggregation in the reference's layout (far3d_agg_operands; reference detr3d_transformer.py:535-555).
 

@@ -132,10 +132,11 @@ class DeformableFeatureAggregationCuda(nn.Module):
     """Reference: models/utils/detr3d_transformer.py:483-569 (same kwargs, same parameter names, same forward args).
 
     One sample at the fused kernel's shape family (ops.aggregate_fused_supported: the reference configuration) runs 3 small GEMMs + ONE
-    far3d_aggregate_forward launch + the output projection.  Any other embed_dims / num_groups with (C / G) % 4 == 0, num_levels,
-    num_pts, camera count (the limits of far3d_agg_operands, include/far3d_hip.h) and any batch size runs the reference's own sequence
-    on the device, ops.aggregate_general: far3d_agg_operands -> far3d_msda_forward -> far3d_camera_sum.  sampling_operands(...) returns
-    the two tensors the reference hands to its MSDA operator, and the key points."""
+    far3d_aggregate_forward launch + the output projection; several samples at that family run the same layers on all bs * A rows and
+    ONE far3d_aggregate_batched launch (ops.aggregate_batched: per sample the bits of the one-sample launch).  Any other embed_dims /
+    num_groups with (C / G) % 4 == 0, num_levels, num_pts, camera count (the limits of far3d_agg_operands, include/far3d_hip.h), at
+    any batch size, runs the reference's own sequence on the device, ops.aggregate_general: far3d_agg_operands -> far3d_msda_forward
+    -> far3d_camera_sum.  sampling_operands(...) returns the two tensors the reference hands to its MSDA operator, and the key points."""
 
     def __init__(self, embed_dims=256, num_groups=8, num_levels=4, num_cams=6, dropout=0.1, num_pts=13, im2col_step=64,
                  batch_first=True, bias=1.0):
@@ -212,14 +213,34 @@ class DeformableFeatureAggregationCuda(nn.Module):
         out = ops.linear(agg.view(bs * A, self.embed_dims), self._pack(x.device)["oproj"], res=x)
         return out.view(bs, A, self.embed_dims)   # dropout is identity at inference
 
+    def _forward_batched(self, instance_feature, query_pos, feat_flatten, reference_points, spatial_flatten, level_start_index,
+                         pc_range, lidar2img_mat, img_metas):
+        """Several samples at the fused kernel's shape family: the module's layers on all bs * A rows, ONE far3d_aggregate_batched launch
+        (ops.aggregate_batched: per sample the bits of the one-sample launch), the output projection on all rows."""
+        bs, A = reference_points.shape[:2]
+        x, ref, offs, l2i, U, Vc = self._batched_operands(instance_feature, query_pos, reference_points, lidar2img_mat)
+        hw = [tuple(int(v) for v in r) for r in spatial_flatten.tolist()]
+        starts = [int(v) for v in level_start_index.tolist()]
+        pad = img_metas[0]["pad_shape"][0]
+        feat = feat_flatten
+        if feat.dtype not in (torch.float32, torch.bfloat16):
+            feat = feat.float()
+        agg = ops.aggregate_batched(feat.contiguous(), ref, offs, l2i, U, Vc, hw, starts, [float(v) for v in pc_range.tolist()],
+                                    (pad[0], pad[1]), num_groups=self.num_groups)
+        out = ops.linear(agg.view(bs * A, self.embed_dims), self._pack(x.device)["oproj"], res=x)
+        return out.view(bs, A, self.embed_dims)   # dropout is identity at inference
+
     @torch.no_grad()
     def forward(self, instance_feature, query_pos, feat_flatten, reference_points, spatial_flatten, level_start_index,
                 pc_range, lidar2img_mat, img_metas):
         _lib.require_device()
         bs, A = reference_points.shape[:2]
-        if bs != 1 or not ops.aggregate_fused_supported(self.embed_dims, self.num_groups, int(spatial_flatten.shape[0]),
-                                                        lidar2img_mat.shape[1], self.num_pts):
+        if not ops.aggregate_fused_supported(self.embed_dims, self.num_groups, int(spatial_flatten.shape[0]),
+                                             lidar2img_mat.shape[1], self.num_pts):
             return self._forward_general(instance_feature, query_pos, feat_flatten, reference_points, spatial_flatten, level_start_index,
+                                         pc_range, lidar2img_mat, img_metas)
+        if bs != 1:
+            return self._forward_batched(instance_feature, query_pos, feat_flatten, reference_points, spatial_flatten, level_start_index,
                                          pc_range, lidar2img_mat, img_metas)
         dev = instance_feature.device
         P = self._pack(dev)

@@ -82,7 +82,8 @@ int far3d_msda_forward(const void* value, int value_dtype, const int64_t* spatia
  * changes results (row a of `out` is always query a); an entry ~a (negative) means "row a holds no query": a zero row is
  * written and nothing else is done (far3d_agg_order produces such entries).  With perm, A counts the ENTRIES of perm (workgroups);
  * the rows they name may lie anywhere in ref / offsets / U / out (a subset of a larger query set).  Requires C=256, G=8, L<=4, N<=16,
- * N*P<=256, N*P*L<=384; every other shape, and a batch, runs as far3d_agg_operands -> far3d_msda_forward -> far3d_camera_sum (below).
+ * N*P<=256, N*P*L<=384; a batch of samples of this family is far3d_aggregate_batched (below), and every other shape runs as
+ * far3d_agg_operands -> far3d_msda_forward -> far3d_camera_sum (below).
  * cam_tables: the per-layer softmax factors of Vc from far3d_agg_tables / far3d_agg_order ((2+N)*L*P*G floats), or NULL.
  * variant: 0 = default: kernel 8 when cam_tables is given and N<=8, P<=16, value maps < 4 GiB, else kernel 7; 9 = kernel 8 with sibling
  * workgroups for heavy queries (below).
@@ -119,6 +120,24 @@ int far3d_aggregate_forward(const void* feat, int feat_dtype, const float* ref, 
  * unnormalised 256-float sum in split_partials ([rows][2][256] f32) and draws a ticket from split_tickets ([rows] int32, ZERO at rest,
  * returned to zero); the second arrival adds the partials in part order and writes the row -- deterministic, run to run and graph vs
  * eager.  Unmarked queries take kernel 8's path unchanged.  The three split_* arguments are ignored by the other variants. */
+
+/* far3d_aggregate_forward for a BATCH of samples in one launch: kernel 8 (cam_tables given, N<=8, P<=16, one sample's value maps
+ * < 4 GiB) or kernel 7 (otherwise; needs Vc) with the sample as the grid's second index -- variant 0's choice, per sample.
+ * feat (B,N,S,C=256) f32|bf16 contiguous (the reference's feat_flatten (B*N,S,C)); ref (B,A,3) f32; offsets and U: rows b*A + a of ONE
+ * 2-D f32 buffer each, row strides ldOffs / ldU in floats (0 = dense; U rows 16-byte aligned, ldU % 4 == 0), as far3d_agg_operands
+ * takes them; lidar2img (B,N,4,4) f32; Vc (B,N,J) f32 or NULL, J = L*P*G; cam_tables (B,2+N,J) f32 from far3d_agg_tables with
+ * layers = B, or NULL; out (B,A,256) of dtype out_dt; the remaining arguments and the shape family (C=256, G=8, L<=4, N<=16,
+ * N*P<=256, N*P*L<=384, N*S*C of ONE sample < 2^31) are far3d_aggregate_forward's; B <= 65535.  The offsets between samples are
+ * formed in 64 bits: B*N*S*C may pass 2^31.  No perm, no sorted mode, no sibling split, no A/B variants: those belong to the engine's
+ * one-sample call.
+ * B == 0 or A == 0: FAR3D_OK, nothing launched.  Anything refused: FAR3D_ERR_ARG with the sizes in far3d_last_error(), nothing launched.
+ * Contract: out[b] is BIT-IDENTICAL to far3d_aggregate_forward on sample b's operands (variant = 0, perm = NULL, qbase = NULL, that
+ * sample's tables); it does not depend on B, and it is the same from run to run. */
+int far3d_aggregate_batched(const void* feat, int feat_dtype, const float* ref, const float* offsets,
+                            const float* lidar2img, const float* U, const float* Vc, const float* cam_tables,
+                            void* out, int out_dt, int B, int A, int N, int S, int C, int G, int P, int L,
+                            const int32_t* level_hw, const int32_t* level_start, const float* pc_range,
+                            float pad_h, float pad_w, int ldU, int ldOffs, void* stream);
 
 /* Softmax factors of the aggregation logits' camera part, for `layers` decoder layers in one launch (block = layer):
  * Vc (layers, N, J) f32 (far3d_cam_embed_chain's output, J = L*P*G, J % 4 == 0) -> tables (layers, 2+N, J) f32 =
