@@ -44,11 +44,29 @@ __device__ __forceinline__ int vt_pos(int key) {
   return (key & ~15) | (sw << 2) | (key & 3);
 }
 
-template <typename T, int NS>     // NS: key-range parts per workgroup (2 waves each)
+// STREAMS (far3d_attention_streams; both kernels below): B samples in one launch.  A workgroup is still (query block, head) of ONE sample
+// and nothing in it knows about the others: the sample is one more grid index that moves the q / k / v / out bases by b times a
+// per-sample stride (64-bit, elements) and selects hole_count[b]; the body behind the bases is the one-sample code, so out[b] has the
+// bits of the one-sample launch on sample b.  The strides arrive as ONE trailing kernel argument that only the streams instantiations
+// have (BS = AttnStreams; the one-sample instantiations have an empty pack: their argument list, and their code, are what they were).
+struct AttnStreams { long bsq, bsk, bsv, bso; };
+__device__ __forceinline__ const AttnStreams& attn_streams_arg(const AttnStreams& s) { return s; }
+#define ATTN_SAMPLE_BASES(b, s)                                                                                     \
+  do {                                                                                                              \
+    Q += (b) * (s).bsq; K += (b) * (s).bsk; V += (b) * (s).bsv;                                                     \
+    O = reinterpret_cast<char*>(O) + (b) * (s).bso * (out_dt == FAR3D_DT_F32 ? 4 : 2);                              \
+    if (hole_count) hole_count += (b);                                                                              \
+  } while (0)
+
+template <typename T, int NS, typename... BS>     // NS: key-range parts per workgroup (2 waves each); BS: AttnStreams (blockIdx.z = sample) or nothing
 __global__ __launch_bounds__(128 * NS) void attn_fwd_kernel(const T* __restrict__ Q, const T* __restrict__ K,
                                                             const T* __restrict__ V, void* __restrict__ O, int out_dt, int Aq,
                                                             int Nk, int ldq, int ldk, int ldv, int ldo, float scale,
-                                                            const int* __restrict__ hole_count, int hole_start, int hole_end) {
+                                                            const int* __restrict__ hole_count, int hole_start, int hole_end, BS... bs) {
+  if constexpr (sizeof...(BS) > 0) {
+    const long b = blockIdx.z;
+    ATTN_SAMPLE_BASES(b, attn_streams_arg(bs...));
+  }
   // Workgroup = 64 queries of one head, 2*NS waves.  Waves 2p, 2p+1 walk part p of the keys for queries [0,32) / [32,64)
   // (flash-decoding style split); the NS partial (max, sum, O) states are merged through LDS at the end.  The loop is a chain
   // of latencies (global load -> LDS -> MFMA -> exp -> MFMA, ~1.7 us per 64-key tile), and 200 workgroups of 4 waves leave most
@@ -274,11 +292,16 @@ __global__ __launch_bounds__(128 * NS) void attn_fwd_kernel(const T* __restrict_
 // loads of L2-resident rows (a head's K and V are 590 KB; workgroup id % heads = head, so with 8 heads an XCD's L2 holds ONE head).  The
 // next 32-key tile's 20 loads are in flight under the current tile's 32 MFMAs; waves run free of each other until the merge of the key
 // parts (one barrier).  Same arithmetic as the staged kernel per 32-key tile: exact products, fp32 accumulation, online softmax.
-template <int QB, int NS, int QW = 1>     // QB query blocks per workgroup, NS key parts (waves = QB * NS); a wave owns QW x 32 queries
+// BS: AttnStreams (blockIdx.y = sample, see STREAMS above) or nothing
+template <int QB, int NS, int QW = 1, typename... BS>     // QB query blocks per workgroup, NS key parts (waves = QB * NS); a wave owns QW x 32 queries
 __global__ __launch_bounds__(64 * QB * NS) void attn_f32_direct_kernel(const float* __restrict__ Q, const float* __restrict__ K,
                                                                       const float* __restrict__ V, void* __restrict__ O, int out_dt, int Aq,
                                                                       int Nk, int heads, int ldq, int ldk, int ldv, int ldo, float scale,
-                                                                      const int* __restrict__ hole_count, int hole_start, int hole_end) {
+                                                                      const int* __restrict__ hole_count, int hole_start, int hole_end, BS... bs) {
+  if constexpr (sizeof...(BS) > 0) {
+    const long b = blockIdx.y;
+    ATTN_SAMPLE_BASES(b, attn_streams_arg(bs...));
+  }
   // QW = 2: one set of K / V fragments feeds two independent MFMA chains (queries l31 and 32 + l31 of the block): half the loads per
   // product and a second chain to issue while the first one's result is on its way
   __shared__ float mb[(NS - 1) * QB * QW * 18 * 64];
@@ -509,5 +532,44 @@ extern "C" int far3d_attention_forward(const void* q, const void* k, const void*
                        out, out_dt, Aq, Nk, ldq, ldk, ldv, ldo, scale, (const int*)hole_count, hole_start, hole_end);
   }
   FAR3D_CHECK_LAUNCH("far3d_attention_forward");
+  return FAR3D_OK;
+}
+
+// far3d_attention_forward for B samples in one launch: the streams instantiations (STREAMS above) of the two kernels that entry launches
+// by default -- bf16: the staged kernel with 4 key parts, grid (query blocks, heads, B); fp32: the register-fed kernel 2 x 4, grid
+// (query blocks * heads, B).  far3d_attention_f32_variant is not read: a batch always takes the default fp32 form.
+extern "C" int far3d_attention_streams(const void* q, const void* k, const void* v, int dtype, void* out, int out_dt, int B, int Aq, int Nk,
+                                       int heads, int head_dim, int ldq, int ldk, int ldv, int ldo, long bsq, long bsk, long bsv, long bso,
+                                       float scale, const int32_t* hole_count, int hole_start, int hole_end, void* stream) {
+  const char* who = "far3d_attention_streams";
+  FAR3D_CHECK_ARG(q && k && v && out, "%s: null pointer argument", who);
+  FAR3D_CHECK_ARG(head_dim == ATT_D, "%s: head_dim must be %d (got %d)", who, ATT_D, head_dim);
+  FAR3D_CHECK_ARG(B > 0 && Aq > 0 && Nk > 0 && heads > 0, "%s: bad sizes B=%d Aq=%d Nk=%d heads=%d", who, B, Aq, Nk, heads);
+  FAR3D_CHECK_ARG(B <= 65535 && heads <= 65535, "%s: B=%d / heads=%d above the grid limit 65535", who, B, heads);
+  FAR3D_CHECK_ARG(dtype == FAR3D_DT_F32 || dtype == FAR3D_DT_BF16, "%s: unsupported dtype %d", who, dtype);
+  FAR3D_CHECK_ARG(!hole_count || (0 <= hole_start && hole_start <= hole_end && hole_end <= Nk), "%s: bad key hole [%d, %d) for Nk=%d", who,
+                  hole_start, hole_end, Nk);
+  if (!hole_count) hole_start = hole_end = 0;
+  const int es = dtype == FAR3D_DT_F32 ? 4 : 2;
+  FAR3D_CHECK_ARG(bsq >= 0 && bsk >= 0 && bsv >= 0 && bso >= 0, "%s: negative batch stride", who);
+  FAR3D_CHECK_ARG(((uintptr_t)q % 16 == 0) && ((uintptr_t)k % 16 == 0) && ((uintptr_t)v % 16 == 0) && ((uintptr_t)out % 16 == 0) &&
+                  (ldq * es) % 16 == 0 && (ldk * es) % 16 == 0 && (ldv * es) % 16 == 0 && ldo % 4 == 0 &&
+                  (bsq * es) % 16 == 0 && (bsk * es) % 16 == 0 && (bsv * es) % 16 == 0 && bso % 4 == 0 &&
+                  (out_dt == FAR3D_DT_F32 || out_dt == FAR3D_DT_BF16),
+                  "%s: pointers / row strides / batch strides must be 16-byte aligned", who);
+  const AttnStreams bs{bsq, bsk, bsv, bso};
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == FAR3D_DT_F32) {
+    constexpr int QB = 2, NS = 4, QW = 1;
+    const int nqb = (Aq + 32 * QB * QW - 1) / (32 * QB * QW);
+    hipLaunchKernelGGL((attn_f32_direct_kernel<QB, NS, QW, AttnStreams>), dim3(nqb * heads, B), dim3(64 * QB * NS), 0, st, (const float*)q,
+                       (const float*)k, (const float*)v, out, out_dt, Aq, Nk, heads, ldq, ldk, ldv, ldo, scale, (const int*)hole_count, hole_start,
+                       hole_end, bs);
+  } else {
+    hipLaunchKernelGGL((attn_fwd_kernel<bf16_t, 4, AttnStreams>), dim3((Aq + 63) / 64, heads, B), dim3(512), 0, st, (const bf16_t*)q,
+                       (const bf16_t*)k, (const bf16_t*)v, out, out_dt, Aq, Nk, ldq, ldk, ldv, ldo, scale, (const int*)hole_count, hole_start,
+                       hole_end, bs);
+  }
+  FAR3D_CHECK_LAUNCH(who);
   return FAR3D_OK;
 }

@@ -194,6 +194,7 @@ class Far3DEngine:
                                  (self.cfg["backbone"], odd[0], self.precision, ", ".join(k for k, v in PRECISIONS.items() if not v.get("pair"))))
         self.convs = {}           # name -> PackedConv of every conv layer of the per-camera stages
         self._bufs = {}
+        self.token_slices = {}      # buffer-set key -> callable (N, S, dtype) -> that set's token buffer (_token_buffer; streams.StreamBatch)
         self._ins = {}              # static input buffers per buffer-set parity (graph replay reads them)
         self._graph = None
         self._graph_outs = None
@@ -514,6 +515,13 @@ class Far3DEngine:
             self._bufs[key] = b
         return b
 
+    def _token_buffer(self, N, S, dtype):
+        """The frame's token-major value maps (N, S, 256).  A buffer set with an entry in token_slices (a scene stream of
+        streams.StreamBatch) takes what that callable hands out -- slice b of the batch's ONE (B, N, S, 256) allocation, so that
+        decoder_streams reads every stream's maps without a copy; every other set owns its buffer."""
+        owner = self.token_slices.get(self._par)
+        return owner(N, S, dtype) if owner is not None else self._buf(("tokens",), (N, S, 256), dtype)
+
     # ------------------------------------------------------------------------------------------ a2: backbone
     def _layer3(self, src, layer, out=None):
         """One 3x3 layer of the backbone on the NHWC view `src` (+ BN + ReLU) into `out` (None: a fresh map).  A plain spec's layer is one
@@ -645,7 +653,7 @@ class Far3DEngine:
         hw = [(f.shape[1], f.shape[2]) for f in ins]
         hw.append(self.fpn_out[n].out_hw(*hw[-1]))
         starts, S = level_starts(hw)
-        tokens = self._buf(("tokens",), (N, S, 256), val)
+        tokens = self._token_buffer(N, S, val)
         lat = [None] * n
         for i in range(n - 1, -1, -1):   # top-down: laterals[i-1] += nearest_upsample(laterals[i])
             lat[i] = ops.conv2d_nhwc(ins[i], self.fpn_lat[i], out=self._buf(("lat", i), (N, hw[i][0], hw[i][1], 256 * self.cs), act),
@@ -930,6 +938,78 @@ class Far3DEngine:
                 ops.add_cast(ws.outs[li], qpos, at, out_sum=X2[:A, :E], out_a=X2[:A, E:])
         return ws.outs
 
+    def decoder_streams(self, X2, x0, qpos, tokens, ref, hw, starts, lidar2img, pad_hw, A):
+        """`decoder` for B scene streams in ONE pass: X2, x0, qpos, tokens, ref, lidar2img are lists of B per-stream operands as
+        `decoder` takes them (same shapes in every stream); hw, starts, pad_hw, A are shared.  Returns (B, layers, A, E) f32 whose
+        [b] is, bit for bit, decoder(...) on stream b's operands in its unfused form (fused_rows off; no hole: the static top-K
+        proposal mode) -- in every decoder dtype and whatever B is.
+        Per layer ONE far3d_attention_streams launch, ONE far3d_aggregate_batched launch, and every row-local launch (out-projection,
+        the three LayerNorms, logit / offset linear, output projection, FFN) once over all B * A rows of (B, A, .) working buffers.
+        The GEMMs go through ops.linear_streams, which takes its tile from ONE stream's row count, so a tile table keyed on rows
+        cannot choose another K order; the LayerNorms, the attention and the aggregation give a row the same bits whatever rows the
+        launch covers (_decoder_layer).  Per stream stay: the launches that read the caller's own buffers (layer 0's in-projection
+        and the memory rows' K / V GEMM from X2[b]), cam_embed_chain, and small copies of x0 / qpos / ref / lidar2img into the
+        batched buffers.  The value maps are not copied when tokens[b] are the slices of one (B, N, S, 256) allocation
+        (_token_buffer); otherwise they are stacked."""
+        cfg = self.cfg
+        B, E, nL, at = len(X2), cfg["embed_dims"], len(self.layers), self.prec["dec"]
+        Kt = X2[0].shape[0]
+        if any(tuple(x.shape) != (Kt, 2 * E) for x in X2) or any(tuple(t.shape) != tuple(tokens[0].shape) for t in tokens) or \
+                not (len(x0) == len(qpos) == len(tokens) == len(ref) == len(lidar2img) == B):
+            raise ValueError("decoder_streams: every stream needs operands of the same shapes (one X2, x0, qpos, tokens, ref, lidar2img each)")
+        nJ = cfg["num_groups"] * cfg["num_levels"] * cfg["num_pts"]
+        nO = cfg["num_pts"] * 3
+        N = lidar2img[0].shape[0]
+        buf = lambda name, shape, dt: self._buf(("ds_" + name, B), shape, dt)
+        outs = buf("outs", (nL, B, A, E), torch.float32)
+        QKV = buf("qkv", (B, Kt, nL * 3 * E), at)                  # per stream and layer a [q | k | v] column block
+        XW = buf("xw", (B, A, 2 * E), at)                          # [x1+pos | x1] operand of the logit / offset GEMM
+        XN = buf("xn", (B, A, 2 * E), at)                          # [x+pos | x] operand of the next layer's in-projection
+        UL = buf("ul", (B, A, -(-(nJ + nO) // 64) * 64), torch.float32)
+        X0, QP = buf("x0", (B, A, E), torch.float32), buf("qpos", (B, A, E), torch.float32)
+        x1, x2 = buf("x1", (B, A, E), torch.float32), buf("x2", (B, A, E), torch.float32)
+        x2b = buf("x2b", (B, A, E), at) if at == torch.bfloat16 else None
+        agg_out, att = buf("agg_out", (B, A, E), at), buf("att_out", (B, A, E), at)
+        REF, L2I = buf("ref", (B, A, 3), torch.float32), buf("l2i", (B, N, 4, 4), torch.float32)
+        VC = buf("vc", (nL, B, N, nJ), torch.float32)              # camera term of the aggregation logits, bias included
+        TAB = buf("agg_tab", (nL, B, 2 + N, nJ), torch.float32)
+        t0 = tokens[0]
+        if all(t.is_contiguous() and t.dtype == t0.dtype and t.data_ptr() == t0.data_ptr() + b * t0.numel() * t0.element_size()
+               for b, t in enumerate(tokens)):
+            tok = t0.as_strided((B,) + tuple(t0.shape), (t0.numel(),) + tuple(t0.stride()))   # slices of one allocation: read in place
+        else:
+            tok = torch.stack(list(tokens))
+        for b in range(B):
+            X0[b].copy_(x0[b]); QP[b].copy_(qpos[b]); REF[b].copy_(ref[b]); L2I[b].copy_(lidar2img[b])
+            if Kt > A:
+                ops.linear(X2[b][A:], self.memkv, out=QKV[b, A:], out_dtype=at)
+            VC[:, b].copy_(ops.cam_embed_chain(lidar2img[b], self.cam_chain))
+            ops.linear(X2[b][:A], self.layers[0]["qkv"], out=QKV[b, :A, :3 * E], out_dtype=at)
+        # the same table pass as far3d_agg_order's (agg_tables_body): the bits of the one-stream decoder's tables, where its kernel reads them
+        tabs = N <= 8 and cfg["num_pts"] <= 16
+        if tabs:
+            ops.agg_tables(VC.view(nL * B, N, nJ), out=TAB.view(nL * B, 2 + N, nJ))
+        flat = lambda t: t.view(B * A, t.shape[2])
+        for li, ly in enumerate(self.layers):
+            c0 = li * 3 * E
+            if li > 0:
+                ops.linear_streams(XN, ly["qkv"], out=QKV[:, :A, c0:c0 + 3 * E])
+            x = X0 if li == 0 else outs[li - 1]
+            ops.attention_streams(QKV[:, :A, c0:c0 + E], QKV[:, :, c0 + E:c0 + 2 * E], QKV[:, :, c0 + 2 * E:c0 + 3 * E],
+                                  num_heads=cfg["num_heads"], out=att)
+            y = ops.linear_streams(att, ly["out"], res=x)
+            ops.layernorm(flat(y), *ly["norms"][0], out=flat(x1), add=flat(QP), y2=flat(XW)[:, :E], yb=flat(XW)[:, E:])
+            ops.linear_streams(XW, ly["wl"], out=UL[:, :, :nJ + nO])
+            ops.aggregate_batched(tok, REF, UL[:, :, nJ:nJ + nO], L2I, UL[:, :, :nJ], VC[li], hw, starts, cfg["pc_range"], pad_hw,
+                                  num_groups=cfg["num_groups"], out=agg_out, tables=TAB[li] if tabs else None)
+            y = ops.linear_streams(agg_out, ly["oproj"], res=x1)
+            ops.layernorm(flat(y), *ly["norms"][1], out=flat(x2), yb=None if x2b is None else flat(x2b))
+            hdn = ops.linear_streams(x2 if x2b is None else x2b, ly["ffn1"], act="relu", out_dtype=at)
+            y = ops.linear_streams(hdn, ly["ffn2"], res=x2)
+            nxt = dict(add=flat(QP), y2=flat(XN)[:, :E], yb=flat(XN)[:, E:]) if li + 1 < nL else {}
+            ops.layernorm(flat(y), *ly["norms"][2], out=flat(outs[li]), **nxt)
+        return outs.permute(1, 0, 2, 3)
+
     # ------------------------------------------------------------------------------------------ one frame
     @_with_tile_tables
     def camera_stage(self, img, dd, cam_ids, pad_hw, block_rows=None):
@@ -1025,7 +1105,16 @@ class Far3DEngine:
     def head_stage(self, tokens, ref2d, ctx, M, dd, img_metas, hw, starts, pad_hw, m_dev=None, qshard=None):
         """The cross-camera part: streaming memory, query construction, 6-layer decoder, heads, decode (a6-a12).
         M: adaptive-query ROWS.  m_dev (int32 device scalar; fixed-capacity threshold mode): only the first m_dev of them are
-        queries, rows [nq + m_dev, nq + M) are the masked hole (their inputs are zero-filled by proposal_gather)."""
+        queries, rows [nq + m_dev, nq + M) are the masked hole (their inputs are zero-filled by proposal_gather).
+        Three steps: _head_prepare (memory, query construction: the decoder's operands), the decoder, _head_finish (heads, decode,
+        memory update).  streams.StreamBatch runs the first and the last per scene stream around ONE decoder_streams pass."""
+        hs = self._head_prepare(tokens, ref2d, ctx, M, dd, img_metas, m_dev)
+        outs_dec = self.decoder(hs.X2, hs.x0, hs.qpos, tokens, hs.ref, hw, starts, hs.lidar2img, pad_hw, hs.A, hole=hs.hole, qshard=qshard)
+        return self._head_finish(hs, outs_dec)
+
+    def _head_prepare(self, tokens, ref2d, ctx, M, dd, img_metas, m_dev=None):
+        """The part of head_stage in front of the decoder (a6): scene change, memory pre-update, temporal codes, the query-major
+        state buffers -> the decoder's operands and what _head_finish needs, as one object."""
         cfg = self.cfg
         E = cfg["embed_dims"]
         lidar2img = dd["lidar2img"][0]
@@ -1066,9 +1155,17 @@ class Far3DEngine:
         ops.row_affine_ln(m["emb"][0], g, b, out=TQ[nq + M:])
         X2 = self._buf(("x2op",), (Kt, 2 * E), at)
         ops.add_cast(TQ, QP, at, out_sum=X2[:, :E], out_a=X2[:, E:])
-        ref = RF[:A]
         hole = (m_dev, nq, nq + M) if m_dev is not None else None
-        outs_dec = self.decoder(X2, TQ[:A], QP[:A], tokens, ref, hw, starts, lidar2img, pad_hw, A, hole=hole, qshard=qshard)
+        return SimpleNamespace(X2=X2, x0=TQ[:A], qpos=QP[:A], ref=RF[:A], tokens=tokens, lidar2img=lidar2img, A=A, M=M, m=m, m_dev=m_dev,
+                               hole=hole, dd=dd)
+
+    def _head_finish(self, hs, outs_dec):
+        """The part of head_stage behind the decoder: the shared cls / reg heads over all layers, finalize, decode, the memory's
+        post-update.  hs: _head_prepare's result; outs_dec (layers, A, E) f32, contiguous."""
+        cfg = self.cfg
+        E, at = cfg["embed_dims"], self.prec["dec"]
+        fast = at == torch.bfloat16
+        A, M, m, m_dev, hole, ref, tokens, dd = hs.A, hs.M, hs.m, hs.m_dev, hs.hole, hs.ref, hs.tokens, hs.dd
         # ---- a10: shared heads over all layers at once (farhead.py:646-664)
         flat = outs_dec.view(-1, E)
         flatb = ops.nan_to_num_(flat, bf16_copy=fast)

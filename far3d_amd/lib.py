@@ -44,6 +44,7 @@ SIGNATURES = {
     "far3d_conv_tile_caps": (c_int, [c_int] * 3),
     "far3d_attention_forward": (c_int, [_p, _p, _p, c_int, _p, c_int] + [c_int] * 8 + [c_float, _p, c_int, c_int, _p]),
     "far3d_attention_f32_variant": (c_int, [c_int]),
+    "far3d_attention_streams": (c_int, [_p, _p, _p, c_int, _p, c_int] + [c_int] * 9 + [c_long] * 4 + [c_float, _p, c_int, c_int, _p]),
     "far3d_attention_batched": (c_int, [_p, _p, _p, c_int, _p, c_int] + [c_int] * 9 + [c_long] * 4 +
                                 [c_float, _p, c_int, c_int, c_long, _p, _p]),
     "far3d_layernorm": (c_int, [_p, _p, _p, _p, c_int, c_int, c_int, c_int, c_float, c_int, _p, c_int, _p, c_int, c_int, _p, c_int, c_int, _p]),

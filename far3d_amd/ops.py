@@ -782,16 +782,54 @@ def linear(x, pc, act=None, res=None, out=None, out_dtype=torch.float32, tile=0)
     rv = None
     if res is not None:
         rv = res.as_strided((1, 1, M, pc.Cout), (M * res.stride(0), M * res.stride(0), res.stride(0), 1))
-    if tile == 0 and x.dtype == torch.bfloat16 and pc.w.dtype == torch.bfloat16 and x.shape[1] % 32 == 0 and \
-            _tuned_tile(pc.Cout, x.shape[1], 1, 1, M) == 0:
-        tile = 80     # untuned small GEMM: 64x64 pipelined tile (the winner on every decoder-sized shape of the table)
-    if tile == 0 and F32X_LINEAR_TILE and x.dtype == torch.float32 and pc.w.dtype == torch.float32 and pc.w_code == DT_F32 and \
-            x.shape[1] % 32 == 0 and x.stride(0) % 4 == 0 and x.data_ptr() % 16 == 0 and M * x.stride(0) * 4 < 2 ** 31 - 1:
+    conv2d_nhwc(xv, pc, out=ov, act=act, res=rv, tile=tile or _linear_own_tile(x, pc))
+    return out
+
+
+def _linear_own_tile(x, pc):
+    """The tile linear() chooses itself for x (M,K), before the tile table is asked (0: it leaves the choice to conv2d_nhwc)."""
+    M, K = x.shape
+    if x.dtype == torch.bfloat16 and pc.w.dtype == torch.bfloat16 and K % 32 == 0 and _tuned_tile(pc.Cout, K, 1, 1, M) == 0:
+        return 80     # untuned small GEMM: 64x64 pipelined tile (the winner on every decoder-sized shape of the table)
+    if F32X_LINEAR_TILE and x.dtype == torch.float32 and pc.w.dtype == torch.float32 and pc.w_code == DT_F32 and \
+            K % 32 == 0 and x.stride(0) % 4 == 0 and x.data_ptr() % 16 == 0 and M * x.stride(0) * 4 < 2 ** 31 - 1:
         # exact fp32 on the LDS-DMA pipelined kernel (round 6): the GEMMs of the fp32 / in-tolerance engines' decoder and FarHead.  The
         # choice must NOT depend on the number of rows: the query-sharded decoder launches row subsets and has to reproduce the replicated
         # decoder bit for bit (a row's bits depend on the kernel, not on which rows share its launch)
-        tile = f32x_linear_tile(pc.Cout, x.shape[1])
-    conv2d_nhwc(xv, pc, out=ov, act=act, res=rv, tile=tile)
+        return f32x_linear_tile(pc.Cout, K)
+    return 0
+
+
+def linear_tile(x, pc, out_dtype=torch.float32, res=None, out=None):
+    """The tile linear(x, pc, ...) with the same optional arguments runs on (0 = kernel heuristic): linear's own choice, then the tile
+    table's.  For callers that must give other rows the bits of THIS launch (linear_streams)."""
+    M = x.shape[0]
+    tile = _linear_own_tile(x, pc)
+    v4 = lambda t: None if t is None else t.as_strided((1, 1, M, t.shape[1]), (M * t.stride(0), M * t.stride(0), t.stride(0), 1))
+    return _conv_plan(v4(x), pc, out.dtype if out is not None else out_dtype, v4(res), None, None, tile, v4(out))[2]
+
+
+def linear_streams(x, pc, act=None, res=None, out=None, out_dtype=torch.float32):
+    """linear() for B row blocks in ONE launch (the image-stride form of far3d_conv2d_nhwc, one image per block): x (B,M,K), res / out
+    (B,M,Cout), each with unit inner stride and any row and block stride, so the blocks may be views of larger per-stream buffers.
+    The tile is linear's choice for ONE block's M rows (linear_tile), never for B*M: a tile table keyed on the row count cannot pick
+    another K order, and out[b] has the bits of linear(x[b], ...)."""
+    if x.dim() != 3 or x.stride(2) != 1:
+        raise ValueError("linear_streams: x must be (B,M,K) with unit inner stride")
+    B, M, K = x.shape
+    if out is None:
+        out = torch.empty((B, M, pc.Cout), dtype=out_dtype, device=x.device)
+    for t, n in ((out, "out"), (res, "res")):
+        if t is not None and (t.dim() != 3 or tuple(t.shape) != (B, M, pc.Cout) or t.stride(2) != 1):
+            raise ValueError("linear_streams: %s must be (%d,%d,%d) with unit inner stride" % (n, B, M, pc.Cout))
+    if ((B - 1) * x.stride(0) + M * x.stride(1)) * x.element_size() >= 2 ** 31 - 1:     # linear()'s own limit, for the whole launch
+        raise ValueError("linear_streams: the %d blocks of x span 2 GiB or more; split the launch" % B)
+    tile = linear_tile(x[0], pc, res=None if res is None else res[0], out=out[0])
+    if tile == 0:
+        raise ValueError("linear_streams: linear() leaves this shape (K=%d, Cout=%d, %s) to the kernel's heuristic, which may depend on "
+                         "the row count" % (K, pc.Cout, x.dtype))
+    v4 = lambda t: t.as_strided((B, 1, M, t.shape[2]), (t.stride(0), M * t.stride(1), t.stride(1), 1), t.storage_offset())
+    conv2d_nhwc(v4(x), pc, out=v4(out), act=act, res=None if res is None else v4(res), tile=tile)
     return out
 
 
@@ -975,6 +1013,37 @@ def attention_forward(q, k, v, num_heads=8, out=None, out_dtype=torch.float32, h
     _lib.check(lib.far3d_attention_forward(_ptr(q), _ptr(k), _ptr(v), _dt(q), _ptr(out), _dt(out), Aq, Nk, num_heads, hd,
                                            q.stride(0), k.stride(0), v.stride(0), out.stride(0),
                                            float(hd) ** -0.5, *_hole(hole), _stream(q)), "far3d_attention_forward")
+    return out
+
+
+def attention_streams(q, k, v, num_heads=8, out=None, out_dtype=torch.float32, hole=None):
+    """attention_forward for B samples in ONE launch (far3d_attention_streams): out[b] has the bits of attention_forward on sample b.
+    q (B,Aq,E), k/v (B,Nk,E) f32|bf16 with unit inner stride (views of one (B,rows,layers*3*E) buffer are read in place); out (B,Aq,E).
+    hole: None or (counts int32 device tensor (B,), start, end): sample b masks the keys [start + counts[b], end).
+    attention_f32_variant does not apply: a batch always takes the default fp32 kernel."""
+    lib = _lib.require_device()
+    for t, n in ((q, "q"), (k, "k"), (v, "v")):
+        if not isinstance(t, torch.Tensor) or t.dim() != 3 or t.stride(2) != 1 or not t.is_cuda:
+            raise ValueError("attention_streams: %s must be a 3-D device tensor (B, rows, E) with unit inner stride" % n)
+    if not (q.dtype == k.dtype == v.dtype):
+        raise TypeError("attention_streams: q/k/v dtypes differ")
+    B, Aq, E = q.shape
+    Nk = k.shape[1]
+    if k.shape != (B, Nk, E) or v.shape != (B, Nk, E):
+        raise ValueError("attention_streams: k/v must be (%d, Nk, %d), got %s / %s" % (B, E, tuple(k.shape), tuple(v.shape)))
+    if E % num_heads:
+        raise ValueError("attention_streams: embed dim %d is not a multiple of num_heads %d" % (E, num_heads))
+    hd = E // num_heads
+    if out is None:
+        out = torch.empty((B, Aq, E), dtype=out_dtype, device=q.device)
+    elif tuple(out.shape) != (B, Aq, E) or out.stride(2) != 1 or not out.is_cuda:
+        raise ValueError("attention_streams: out must be a (%d, %d, %d) device tensor with unit inner stride" % (B, Aq, E))
+    if hole is not None and hole[0].numel() != B:
+        raise ValueError("attention_streams: the hole needs one count per sample (%d), got %d" % (B, hole[0].numel()))
+    _lib.check(lib.far3d_attention_streams(_ptr(q), _ptr(k), _ptr(v), _dt(q), _ptr(out), _dt(out), B, Aq, Nk, num_heads, hd,
+                                           q.stride(1), k.stride(1), v.stride(1), out.stride(1),
+                                           q.stride(0), k.stride(0), v.stride(0), out.stride(0), float(hd) ** -0.5,
+                                           *_hole(hole), _stream(q)), "far3d_attention_streams")
     return out
 
 

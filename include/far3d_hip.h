@@ -293,6 +293,24 @@ int far3d_attention_forward(const void* q, const void* k, const void* v, int dty
  * the exp differ at the last bit). */
 int far3d_attention_f32_variant(int variant);
 
+/* far3d_attention_forward for B samples in ONE launch: the engine's attention kernel with the sample as one more grid index (several
+ *   scene streams on one engine, Far3DEngine.decoder_streams).  out[b] has the BITS of far3d_attention_forward on sample b's operands
+ *   and hole_count[b], whatever B is: a workgroup moves its q / k / v / out bases by b times the batch stride and runs the one-sample
+ *   code.
+ * q (B, Aq, heads*32), k/v (B, Nk, heads*32) of `dtype`, row strides ldq/ldk/ldv and batch strides bsq/bsk/bsv in elements (views of
+ *   one (B, rows, layers*3*E) QKV buffer are read in place); out (B, Aq, heads*32) of out_dt (f32 | bf16), row stride ldo, batch
+ *   stride bso.  dtype, out_dt, head_dim = 32, scale and the alignment rules are far3d_attention_forward's; the batch strides are
+ *   16-byte aligned too and not negative.
+ * hole_count: NULL (no mask) or a DEVICE int32 array of B counts, one per sample; hole_start / hole_end are shared by all samples:
+ *   sample b excludes the keys [hole_start + hole_count[b], hole_end).
+ * far3d_attention_f32_variant does NOT apply: this entry always launches the default fp32 form (the register-fed kernel, 64-query
+ *   workgroups x 4 key parts), so with a non-default variant set the one-sample entry gives other last bits than this one.
+ * Bad arguments (null q/k/v/out, head_dim != 32, B / Aq / Nk / heads < 1, a hole outside [0, Nk], misalignment) return FAR3D_ERR_ARG,
+ *   set far3d_last_error() and launch nothing. */
+int far3d_attention_streams(const void* q, const void* k, const void* v, int dtype, void* out, int out_dt, int B, int Aq, int Nk,
+                            int heads, int head_dim, int ldq, int ldk, int ldv, int ldo, long bsq, long bsk, long bsv, long bso,
+                            float scale, const int32_t* hole_count, int hole_start, int hole_end, void* stream);
+
 /* Batched, masked multi-head attention core: per sample b and head h
  *   out[b] = softmax(q[b] k[b]^T * scale + M[b,h] + P[b]) v[b]      (flash-style, no score tensor in HBM; ONE launch for all samples).
  * The attention of torch.nn.MultiheadAttention with `attn_mask` and `key_padding_mask`, as mmcv's wrapper calls it for any batch size
