@@ -3,46 +3,16 @@
 // Replaces the bmm/softmax/bmm inside torch.nn.MultiheadAttention as wrapped by mmcv MultiheadAttention
 // (reference cfg projects/configs/far3d.py:112-116; in-tree statement models/utils/petr_transformer.py:286-326).
 //
-// gfx950 mapping.  Workgroup = 4 waves = 128 queries of one head; a wave owns 32 queries.  Scores are computed
-// TRANSPOSED, S^T = K Q^T, so the MFMA C layout puts one query per lane column: lane (q = lane&31, hi = lane>>5)
-// holds 16 of the 32 keys of a tile for ITS query, the partner lane q+32 the other 16 -> the row max / row sum
-// are 15 in-register ops + one cross-half shuffle, and the running max / rescale are per-lane scalars.
-// O^T = V^T P^T accumulates with the same column = query mapping.  K/V tiles of 64 keys go through LDS once per
-// workgroup (K row-major, padded rows; V transposed with the key order permuted inside 16-key groups so that the
-// bf16 MFMA A-fragment is ONE ds_read_b128); the next tile's global loads are in flight during the MFMAs.
-// T = bf16: v_mfma_f32_32x32x16_bf16.  T = float: exact-fp32 v_mfma_f32_32x32x2_f32 (parity mode).
-#include "common.hpp"
+// Two kernels, both for one sample or (STREAMS below) for B samples in one launch:
+//   attn_fwd_kernel         bf16 (and the fp32 A/B variants 2 / 4): K/V tiles of 64 keys go through LDS once per workgroup, the next
+//                           tile's global loads are in flight during the MFMAs;
+//   attn_f32_direct_kernel  fp32: a wave feeds its MFMAs from registers it loads itself, no LDS and no barrier in the key loop.
+// The fragment layouts (S^T = K Q^T, one query per lane column -> the row max / row sum are 15 in-register ops + one cross-half shuffle
+// and the running max / rescale are per-lane scalars), the Q load, the K/V staging, the scores and PV steps and the merge of the key
+// parts are the shared pieces of attn_core.hpp, which attn_batch.hip (far3d_attention_batched) composes too.  What is written here is
+// what only these kernels have: the key hole, each kernel's online-softmax step, the register-fed key loop, and the launchers.
+#include "attn_core.hpp"
 #include <atomic>
-
-typedef __attribute__((__vector_size__(8 * sizeof(__bf16)))) __bf16 bf16x8_t;
-typedef __attribute__((__vector_size__(16 * sizeof(float)))) float f32x16_t;
-typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
-
-#define ATT_D 32
-#define ATT_KT 64
-
-template <typename T> struct ACfg;
-template <> struct ACfg<bf16_t> { static constexpr int KROW = 80, VROW = 144, KSUB = 2, CH = 1; };   // bytes
-template <> struct ACfg<float> { static constexpr int KROW = 144, VROW = 144, KSUB = 4, CH = 2; };
-
-template <typename T>
-__device__ __forceinline__ void mma_att(f32x16_t& acc, const u32x4_t& a, const u32x4_t& b) {
-  if constexpr (sizeof(T) == 2) {
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), acc, 0, 0, 0);
-  } else {
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(a.x), __uint_as_float(b.x), acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(a.y), __uint_as_float(b.y), acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(a.z), __uint_as_float(b.z), acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(a.w), __uint_as_float(b.w), acc, 0, 0, 0);
-  }
-}
-
-// position of key k inside a permuted 16-key group: quads 1 and 2 swapped (matches the S^T register order)
-__device__ __forceinline__ int vt_pos(int key) {
-  const int quad = (key >> 2) & 3;
-  const int sw = (quad == 1) ? 2 : ((quad == 2) ? 1 : quad);
-  return (key & ~15) | (sw << 2) | (key & 3);
-}
 
 // STREAMS (far3d_attention_streams; both kernels below): B samples in one launch.  A workgroup is still (query block, head) of ONE sample
 // and nothing in it knows about the others: the sample is one more grid index that moves the q / k / v / out bases by b times a
@@ -51,12 +21,13 @@ __device__ __forceinline__ int vt_pos(int key) {
 // have (BS = AttnStreams; the one-sample instantiations have an empty pack: their argument list, and their code, are what they were).
 struct AttnStreams { long bsq, bsk, bsv, bso; };
 __device__ __forceinline__ const AttnStreams& attn_streams_arg(const AttnStreams& s) { return s; }
-#define ATTN_SAMPLE_BASES(b, s)                                                                                     \
-  do {                                                                                                              \
-    Q += (b) * (s).bsq; K += (b) * (s).bsk; V += (b) * (s).bsv;                                                     \
-    O = reinterpret_cast<char*>(O) + (b) * (s).bso * (out_dt == FAR3D_DT_F32 ? 4 : 2);                              \
-    if (hole_count) hole_count += (b);                                                                              \
-  } while (0)
+template <typename T>
+__device__ __forceinline__ void attn_sample_bases(long b, const AttnStreams& s, int out_dt, const T* __restrict__& Q, const T* __restrict__& K,
+                                                  const T* __restrict__& V, void* __restrict__& O, const int* __restrict__& hole_count) {
+  Q += b * s.bsq; K += b * s.bsk; V += b * s.bsv;
+  O = reinterpret_cast<char*>(O) + b * s.bso * (out_dt == FAR3D_DT_F32 ? 4 : 2);
+  if (hole_count) hole_count += b;
+}
 
 template <typename T, int NS, typename... BS>     // NS: key-range parts per workgroup (2 waves each); BS: AttnStreams (blockIdx.z = sample) or nothing
 __global__ __launch_bounds__(128 * NS) void attn_fwd_kernel(const T* __restrict__ Q, const T* __restrict__ K,
@@ -65,17 +36,14 @@ __global__ __launch_bounds__(128 * NS) void attn_fwd_kernel(const T* __restrict_
                                                             const int* __restrict__ hole_count, int hole_start, int hole_end, BS... bs) {
   if constexpr (sizeof...(BS) > 0) {
     const long b = blockIdx.z;
-    ATTN_SAMPLE_BASES(b, attn_streams_arg(bs...));
+    attn_sample_bases(b, attn_streams_arg(bs...), out_dt, Q, K, V, O, hole_count);
   }
   // Workgroup = 64 queries of one head, 2*NS waves.  Waves 2p, 2p+1 walk part p of the keys for queries [0,32) / [32,64)
   // (flash-decoding style split); the NS partial (max, sum, O) states are merged through LDS at the end.  The loop is a chain
   // of latencies (global load -> LDS -> MFMA -> exp -> MFMA, ~1.7 us per 64-key tile), and 200 workgroups of 4 waves leave most
   // SIMDs with a single wave: more parts = fewer serial tiles per wave and more waves per SIMD (bf16: NS = 4, 9 tiles per wave
   // at 2312 keys; fp32 keeps NS = 2, its tiles do not fit four times into the static LDS budget).
-  constexpr int NT = 128 * NS;
-  constexpr int KROW = ACfg<T>::KROW, VROW = ACfg<T>::VROW, KSUB = ACfg<T>::KSUB, CH = ACfg<T>::CH;
-  constexpr int E = 16 / sizeof(T);
-  constexpr int KBYTES = ATT_KT * KROW, VBYTES = (sizeof(T) == 2 ? ATT_D : ATT_KT) * VROW;
+  constexpr int KBYTES = AttCfg<T>::KBYTES, VBYTES = AttCfg<T>::VBYTES;
   // static LDS up to the 64 KB static limit (the shipped NS = 2 / 4 instantiations, unchanged); the 8-part variant's 78 KB are dynamic
   constexpr int LDS_TOTAL = NS * KBYTES + NS * VBYTES;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_dyn[];
@@ -97,60 +65,8 @@ __global__ __launch_bounds__(128 * NS) void attn_fwd_kernel(const T* __restrict_
   unsigned char* Ks = KsAll + half * KBYTES;
   unsigned char* Vs = VsAll + half * VBYTES;
 
-  // Q fragments (B operand: column = query), held in registers for the whole key loop
-  u32x4_t qf[KSUB];
-#pragma unroll
-  for (int kk = 0; kk < KSUB; ++kk) {
-    qf[kk] = u32x4_t{0u, 0u, 0u, 0u};
-    if (q_ok) {
-      const T* src = Q + (long)q * ldq + head * ATT_D + kk * 2 * E + hi * E;
-      qf[kk] = *reinterpret_cast<const u32x4_t*>(src);
-      if constexpr (sizeof(T) == 4) {  // torch scales q before the product (F.multi_head_attention_forward)
-        qf[kk].x = __float_as_uint(__uint_as_float(qf[kk].x) * scale);
-        qf[kk].y = __float_as_uint(__uint_as_float(qf[kk].y) * scale);
-        qf[kk].z = __float_as_uint(__uint_as_float(qf[kk].z) * scale);
-        qf[kk].w = __float_as_uint(__uint_as_float(qf[kk].w) * scale);
-      }
-    }
-  }
-
-  // cooperative staging of NS K/V tiles per iteration (one per part): chunk id -> (part, key, 16-B piece)
-  constexpr int CPK = ATT_D * sizeof(T) / 16;  // 16-B chunks per key row: 4 (bf16) / 8 (f32)
-  constexpr int CH2 = 2 * CH;
-  u32x4_t kreg[CH2], vreg[CH2];
-  auto gload = [&](int it) __attribute__((always_inline)) {
-#pragma unroll
-    for (int c = 0; c < CH2; ++c) {
-      const int id = t + c * NT, h = id / (ATT_KT * CPK), rem = id % (ATT_KT * CPK), key = rem / CPK, ck = rem % CPK;
-      const int tl = it + h * htiles;
-      const int gk = tl * ATT_KT + key;
-      kreg[c] = u32x4_t{0u, 0u, 0u, 0u};
-      vreg[c] = u32x4_t{0u, 0u, 0u, 0u};
-      if (tl < ntiles && gk < Nk) {
-        kreg[c] = *reinterpret_cast<const u32x4_t*>(K + (long)gk * ldk + head * ATT_D + ck * E);
-        vreg[c] = *reinterpret_cast<const u32x4_t*>(V + (long)gk * ldv + head * ATT_D + ck * E);
-      }
-    }
-  };
-  auto lstore = [&]() __attribute__((always_inline)) {
-#pragma unroll
-    for (int c = 0; c < CH2; ++c) {
-      const int id = t + c * NT, h = id / (ATT_KT * CPK), rem = id % (ATT_KT * CPK), key = rem / CPK, ck = rem % CPK;
-      *reinterpret_cast<u32x4_t*>(KsAll + h * KBYTES + key * KROW + ck * 16) = kreg[c];
-      unsigned char* vs = VsAll + h * VBYTES;
-      if constexpr (sizeof(T) == 2) {
-        const int pos = vt_pos(key);
-        const uint32_t w[4] = {vreg[c].x, vreg[c].y, vreg[c].z, vreg[c].w};
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const uint16_t val = (uint16_t)((e & 1) ? (w[e >> 1] >> 16) : (w[e >> 1] & 0xffffu));
-          *reinterpret_cast<uint16_t*>(vs + (ck * 8 + e) * VROW + pos * 2) = val;
-        }
-      } else {
-        *reinterpret_cast<u32x4_t*>(vs + key * VROW + ck * 16) = vreg[c];
-      }
-    }
-  };
+  ATT_LOAD_Q(T, qf, Q + (long)q * ldq + head * ATT_D, q_ok, hi, scale);
+  ATT_STAGE(T, NS, gload, lstore, kreg, vreg, K, V, ldk, ldv, head, Nk, ntiles, htiles, t, KsAll, VsAll);
 
   f32x16_t o;
 #pragma unroll
@@ -165,18 +81,7 @@ __global__ __launch_bounds__(128 * NS) void attn_fwd_kernel(const T* __restrict_
     if (more) gload(it + 1);
     const int tile = it + half * htiles;
     if (tile < ntiles && !(tile * ATT_KT >= hole_lo && (tile + 1) * ATT_KT <= hole_end)) {   // wave-uniform; tiles inside the hole are skipped
-      // ---- S^T = K Q^T for the two 32-key sub-tiles
-      f32x16_t s[2];
-#pragma unroll
-      for (int u = 0; u < 2; ++u) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) s[u][r] = 0.f;
-#pragma unroll
-        for (int kk = 0; kk < KSUB; ++kk) {
-          const u32x4_t a = *reinterpret_cast<const u32x4_t*>(Ks + (u * 32 + l31) * KROW + kk * 32 + hi * 16);
-          mma_att<T>(s[u], a, qf[kk]);
-        }
-      }
+      ATT_SCORES(T, s, Ks, qf, l31, hi);
       // ---- online softmax (per-lane query)
       const int kbase = tile * ATT_KT + 4 * hi;
       float mloc = -INFINITY;
@@ -208,31 +113,7 @@ __global__ __launch_bounds__(128 * NS) void attn_fwd_kernel(const T* __restrict_
       m_run = m_new;
 #pragma unroll
       for (int r = 0; r < 16; ++r) o[r] *= alpha;
-
-      // ---- O^T += V^T P^T
-      if constexpr (sizeof(T) == 2) {
-#pragma unroll
-        for (int u = 0; u < 2; ++u)
-#pragma unroll
-          for (int g = 0; g < 2; ++g) {
-            u32x4_t b;
-            b.x = pack_bf16x2(s[u][8 * g + 0], s[u][8 * g + 1]);
-            b.y = pack_bf16x2(s[u][8 * g + 2], s[u][8 * g + 3]);
-            b.z = pack_bf16x2(s[u][8 * g + 4], s[u][8 * g + 5]);
-            b.w = pack_bf16x2(s[u][8 * g + 6], s[u][8 * g + 7]);
-            const u32x4_t a = *reinterpret_cast<const u32x4_t*>(Vs + l31 * VROW + ((u * 32 + 16 * g) + hi * 8) * 2);
-            o = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), o, 0, 0, 0);
-          }
-      } else {
-#pragma unroll
-        for (int u = 0; u < 2; ++u)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const int key = u * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
-            const float a = *reinterpret_cast<const float*>(Vs + key * VROW + l31 * 4);
-            o = __builtin_amdgcn_mfma_f32_32x32x2f32(a, s[u][r], o, 0, 0, 0);
-          }
-      }
+      ATT_PV(T, o, s, Vs, l31, hi);
     }
     __syncthreads();
     if (more) lstore();
@@ -242,46 +123,10 @@ __global__ __launch_bounds__(128 * NS) void attn_fwd_kernel(const T* __restrict_
   // ---- merge the key parts: waves of parts 1..NS-1 publish (m, l, O) per lane, waves 0,1 combine in part order and store
   float l_tot = l_run + __shfl_xor(l_run, 32);   // both lane halves of a query share m_run
   float* mb = reinterpret_cast<float*>(smem);    // [NS-1 parts][2 waves][18][64 lanes]
-  if (half >= 1) {
-    float* dst = mb + ((half - 1) * 2 + (wv & 1)) * 18 * 64 + lane;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) dst[r * 64] = o[r];
-    dst[16 * 64] = m_run;
-    dst[17 * 64] = l_tot;
-  }
+  if (half >= 1) ATT_MERGE_PUBLISH(mb, (half - 1) * 2 + (wv & 1), lane, o, m_run, l_tot);
   __syncthreads();
-  if (half == 0 && q_ok) {
-    float m = m_run;
-#pragma unroll
-    for (int p = 1; p < NS; ++p) m = fmaxf(m, mb[((p - 1) * 2 + (wv & 1)) * 18 * 64 + lane + 16 * 64]);
-    const float mu = (m == -INFINITY) ? 0.f : m;
-    float ap[NS];                                  // a part that saw no key has m = -inf -> weight 0
-    ap[0] = expf(m_run - mu);
-    float den = l_tot * ap[0];
-#pragma unroll
-    for (int p = 1; p < NS; ++p) {
-      const float* src = mb + ((p - 1) * 2 + (wv & 1)) * 18 * 64 + lane;
-      ap[p] = expf(src[16 * 64] - mu);
-      den += src[17 * 64] * ap[p];
-    }
-    const float inv = 1.f / den;
-    const long off = (long)q * ldo + head * ATT_D + 4 * hi;
-#pragma unroll
-    for (int qd = 0; qd < 4; ++qd) {
-      float acc[4];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) acc[e] = o[4 * qd + e] * ap[0];
-#pragma unroll
-      for (int p = 1; p < NS; ++p) {
-        const float* src = mb + ((p - 1) * 2 + (wv & 1)) * 18 * 64 + lane;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) acc[e] += src[(4 * qd + e) * 64] * ap[p];
-      }
-      const float4 r = make_float4(acc[0] * inv, acc[1] * inv, acc[2] * inv, acc[3] * inv);
-      if (out_dt == FAR3D_DT_F32) *reinterpret_cast<float4*>(reinterpret_cast<float*>(O) + off + 8 * qd) = r;
-      else *reinterpret_cast<uint2*>(reinterpret_cast<bf16_t*>(O) + off + 8 * qd) = make_uint2(pack_bf16x2(r.x, r.y), pack_bf16x2(r.z, r.w));
-    }
-  }
+  if (half == 0 && q_ok)
+    ATT_MERGE_STORE(NS, mb, (p - 1) * 2 + (wv & 1), lane, o, m_run, l_tot, ATT_EXPF_DIFF, O, (long)q * ldo + head * ATT_D + 4 * hi, out_dt);
 }
 
 // fp32, round 6: the key loop WITHOUT LDS and without barriers.  The staged kernel above walks its 64-key tiles in lockstep (two workgroup
@@ -300,7 +145,7 @@ __global__ __launch_bounds__(64 * QB * NS) void attn_f32_direct_kernel(const flo
                                                                       const int* __restrict__ hole_count, int hole_start, int hole_end, BS... bs) {
   if constexpr (sizeof...(BS) > 0) {
     const long b = blockIdx.y;
-    ATTN_SAMPLE_BASES(b, attn_streams_arg(bs...));
+    attn_sample_bases(b, attn_streams_arg(bs...), out_dt, Q, K, V, O, hole_count);
   }
   // QW = 2: one set of K / V fragments feeds two independent MFMA chains (queries l31 and 32 + l31 of the block): half the loads per
   // product and a second chain to issue while the first one's result is on its way
@@ -328,7 +173,7 @@ __global__ __launch_bounds__(64 * QB * NS) void attn_f32_direct_kernel(const flo
   const float* Vh = V + head * ATT_D + l31;
   u32x4_t kf[2][4];
   float vf[2][16];
-  auto gload = [&](int tile, u32x4_t (&kd)[4], float (&vd)[16]) __attribute__((always_inline)) {
+  auto fetch = [&](int tile, u32x4_t (&kd)[4], float (&vd)[16]) __attribute__((always_inline)) {
     const int k0 = tile * 32;
     const float* kr = Kh + (long)min(k0 + l31, Nk - 1) * ldk;           // rows past Nk: a valid row, masked below
 #pragma unroll
@@ -404,28 +249,22 @@ __global__ __launch_bounds__(64 * QB * NS) void attn_f32_direct_kernel(const flo
       for (int w = 0; w < QW; ++w) o[w] = __builtin_amdgcn_mfma_f32_32x32x2f32(vd[r], s[w][r], o[w], 0, 0, 0);
   };
   if (t0 < t1) {
-    gload(t0, kf[0], vf[0]);
+    fetch(t0, kf[0], vf[0]);
     for (int tile = t0; tile < t1; tile += 2) {
-      if (tile + 1 < t1) gload(tile + 1, kf[1], vf[1]);
+      if (tile + 1 < t1) fetch(tile + 1, kf[1], vf[1]);
       compute(tile, kf[0], vf[0]);
       if (tile + 1 >= t1) break;
-      if (tile + 2 < t1) gload(tile + 2, kf[0], vf[0]);
+      if (tile + 2 < t1) fetch(tile + 2, kf[0], vf[0]);
       compute(tile + 1, kf[1], vf[1]);
     }
   }
-  // ---- merge the key parts in part order (as the staged kernel)
+  // ---- merge the key parts in part order, per chain w
   float l_tot[QW];
 #pragma unroll
   for (int w = 0; w < QW; ++w) l_tot[w] = l_run[w] + __shfl_xor(l_run[w], 32);
   if (part >= 1) {
 #pragma unroll
-    for (int w = 0; w < QW; ++w) {
-      float* dst = mb + (((part - 1) * QB + qb) * QW + w) * 18 * 64 + lane;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) dst[r * 64] = o[w][r];
-      dst[16 * 64] = m_run[w];
-      dst[17 * 64] = l_tot[w];
-    }
+    for (int w = 0; w < QW; ++w) ATT_MERGE_PUBLISH(mb, ((part - 1) * QB + qb) * QW + w, lane, o[w], m_run[w], l_tot[w]);
   }
   __syncthreads();
   if (part != 0) return;
@@ -433,36 +272,7 @@ __global__ __launch_bounds__(64 * QB * NS) void attn_f32_direct_kernel(const flo
   for (int w = 0; w < QW; ++w) {
     const int q = q0 + 32 * w;
     if (q >= Aq) continue;
-    float m = m_run[w];
-#pragma unroll
-    for (int p = 1; p < NS; ++p) m = fmaxf(m, mb[(((p - 1) * QB + qb) * QW + w) * 18 * 64 + lane + 16 * 64]);
-    const float mu = (m == -INFINITY) ? 0.f : m;
-    float ap[NS];
-    ap[0] = expf(m_run[w] - mu);
-    float den = l_tot[w] * ap[0];
-#pragma unroll
-    for (int p = 1; p < NS; ++p) {
-      const float* src = mb + (((p - 1) * QB + qb) * QW + w) * 18 * 64 + lane;
-      ap[p] = expf(src[16 * 64] - mu);
-      den += src[17 * 64] * ap[p];
-    }
-    const float inv = 1.f / den;
-    const long off = (long)q * ldo + head * ATT_D + 4 * hi;
-#pragma unroll
-    for (int qd = 0; qd < 4; ++qd) {
-      float acc[4];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) acc[e] = o[w][4 * qd + e] * ap[0];
-#pragma unroll
-      for (int p = 1; p < NS; ++p) {
-        const float* src = mb + (((p - 1) * QB + qb) * QW + w) * 18 * 64 + lane;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) acc[e] += src[(4 * qd + e) * 64] * ap[p];
-      }
-      const float4 r = make_float4(acc[0] * inv, acc[1] * inv, acc[2] * inv, acc[3] * inv);
-      if (out_dt == FAR3D_DT_F32) *reinterpret_cast<float4*>(reinterpret_cast<float*>(O) + off + 8 * qd) = r;
-      else *reinterpret_cast<uint2*>(reinterpret_cast<bf16_t*>(O) + off + 8 * qd) = make_uint2(pack_bf16x2(r.x, r.y), pack_bf16x2(r.z, r.w));
-    }
+    ATT_MERGE_STORE(NS, mb, ((p - 1) * QB + qb) * QW + w, lane, o[w], m_run[w], l_tot[w], ATT_EXPF_DIFF, O, (long)q * ldo + head * ATT_D + 4 * hi, out_dt);
   }
 }
 
@@ -481,21 +291,22 @@ extern "C" int far3d_attention_f32_variant(int variant) {
   return g_attn_f32_variant.exchange(variant, std::memory_order_relaxed);
 }
 
+// the key hole of the two entries below: inside [0, Nk]; without a count there is none
+static int attn_check_hole(const char* who, const int32_t* hole_count, int& hole_start, int& hole_end, int Nk) {
+  FAR3D_CHECK_ARG(!hole_count || (0 <= hole_start && hole_start <= hole_end && hole_end <= Nk), "%s: bad key hole [%d, %d) for Nk=%d", who,
+                  hole_start, hole_end, Nk);
+  if (!hole_count) hole_start = hole_end = 0;
+  return FAR3D_OK;
+}
+
 extern "C" int far3d_attention_forward(const void* q, const void* k, const void* v, int dtype, void* out, int out_dt, int Aq,
                                        int Nk, int heads, int head_dim, int ldq, int ldk, int ldv, int ldo,
                                        float scale, const int32_t* hole_count, int hole_start, int hole_end, void* stream) {
-  FAR3D_CHECK_ARG(q && k && v && out, "far3d_attention_forward: null pointer argument");
-  FAR3D_CHECK_ARG(head_dim == ATT_D, "far3d_attention_forward: head_dim must be %d (got %d)", ATT_D, head_dim);
-  FAR3D_CHECK_ARG(Aq > 0 && Nk > 0 && heads > 0, "far3d_attention_forward: bad sizes Aq=%d Nk=%d heads=%d", Aq, Nk, heads);
-  FAR3D_CHECK_ARG(dtype == FAR3D_DT_F32 || dtype == FAR3D_DT_BF16, "far3d_attention_forward: unsupported dtype %d", dtype);
-  FAR3D_CHECK_ARG(!hole_count || (0 <= hole_start && hole_start <= hole_end && hole_end <= Nk), "far3d_attention_forward: bad key hole [%d, %d) for Nk=%d",
-                  hole_start, hole_end, Nk);
-  if (!hole_count) hole_start = hole_end = 0;
-  const int es = dtype == FAR3D_DT_F32 ? 4 : 2;
-  FAR3D_CHECK_ARG(((uintptr_t)q % 16 == 0) && ((uintptr_t)k % 16 == 0) && ((uintptr_t)v % 16 == 0) && ((uintptr_t)out % 16 == 0) &&
-                  (ldq * es) % 16 == 0 && (ldk * es) % 16 == 0 && (ldv * es) % 16 == 0 && ldo % 4 == 0 &&
-                  (out_dt == FAR3D_DT_F32 || out_dt == FAR3D_DT_BF16),
-                  "far3d_attention_forward: pointers / row strides must be 16-byte aligned");
+  const char* who = "far3d_attention_forward";
+  if (const int rc = attn_check_operands(who, q, k, v, out, head_dim, false, 1, Aq, Nk, heads)) return rc;
+  if (const int rc = attn_check_dtype(who, dtype)) return rc;
+  if (const int rc = attn_check_hole(who, hole_count, hole_start, hole_end, Nk)) return rc;
+  if (const int rc = attn_check_layout(who, q, k, v, out, dtype, out_dt, ldq, ldk, ldv, ldo, nullptr)) return rc;
   dim3 grid((Aq + 63) / 64, heads);
   hipStream_t st = (hipStream_t)stream;
   // key parts per workgroup (2 waves each): fp32 2, bf16 4 (an 8-part bf16 instantiation was measured in round 4 -- 27.4 vs 28 us,
@@ -517,7 +328,7 @@ extern "C" int far3d_attention_forward(const void* q, const void* k, const void*
     else if (parts == 118) FAR3D_ATTN_DIRECT(1, 8, 2);      // 64 queries per wave
 #undef FAR3D_ATTN_DIRECT
     else if (parts == 4) {
-      constexpr int lds = 4 * (ATT_KT * ACfg<float>::KROW + ATT_KT * ACfg<float>::VROW);
+      constexpr int lds = 4 * (AttCfg<float>::KBYTES + AttCfg<float>::VBYTES);
       static std::atomic<unsigned long long> lds_ok{0};
       if (const int rc = far3d_allow_lds(reinterpret_cast<const void*>(&attn_fwd_kernel<float, 4>), lds, lds_ok, "far3d_attention_forward")) return rc;
       hipLaunchKernelGGL((attn_fwd_kernel<float, 4>), grid, dim3(512), lds, st, (const float*)q, (const float*)k, (const float*)v, out, out_dt,
@@ -542,21 +353,12 @@ extern "C" int far3d_attention_streams(const void* q, const void* k, const void*
                                        int heads, int head_dim, int ldq, int ldk, int ldv, int ldo, long bsq, long bsk, long bsv, long bso,
                                        float scale, const int32_t* hole_count, int hole_start, int hole_end, void* stream) {
   const char* who = "far3d_attention_streams";
-  FAR3D_CHECK_ARG(q && k && v && out, "%s: null pointer argument", who);
-  FAR3D_CHECK_ARG(head_dim == ATT_D, "%s: head_dim must be %d (got %d)", who, ATT_D, head_dim);
-  FAR3D_CHECK_ARG(B > 0 && Aq > 0 && Nk > 0 && heads > 0, "%s: bad sizes B=%d Aq=%d Nk=%d heads=%d", who, B, Aq, Nk, heads);
+  const long strides[4] = {bsq, bsk, bsv, bso};
+  if (const int rc = attn_check_operands(who, q, k, v, out, head_dim, true, B, Aq, Nk, heads)) return rc;
   FAR3D_CHECK_ARG(B <= 65535 && heads <= 65535, "%s: B=%d / heads=%d above the grid limit 65535", who, B, heads);
-  FAR3D_CHECK_ARG(dtype == FAR3D_DT_F32 || dtype == FAR3D_DT_BF16, "%s: unsupported dtype %d", who, dtype);
-  FAR3D_CHECK_ARG(!hole_count || (0 <= hole_start && hole_start <= hole_end && hole_end <= Nk), "%s: bad key hole [%d, %d) for Nk=%d", who,
-                  hole_start, hole_end, Nk);
-  if (!hole_count) hole_start = hole_end = 0;
-  const int es = dtype == FAR3D_DT_F32 ? 4 : 2;
-  FAR3D_CHECK_ARG(bsq >= 0 && bsk >= 0 && bsv >= 0 && bso >= 0, "%s: negative batch stride", who);
-  FAR3D_CHECK_ARG(((uintptr_t)q % 16 == 0) && ((uintptr_t)k % 16 == 0) && ((uintptr_t)v % 16 == 0) && ((uintptr_t)out % 16 == 0) &&
-                  (ldq * es) % 16 == 0 && (ldk * es) % 16 == 0 && (ldv * es) % 16 == 0 && ldo % 4 == 0 &&
-                  (bsq * es) % 16 == 0 && (bsk * es) % 16 == 0 && (bsv * es) % 16 == 0 && bso % 4 == 0 &&
-                  (out_dt == FAR3D_DT_F32 || out_dt == FAR3D_DT_BF16),
-                  "%s: pointers / row strides / batch strides must be 16-byte aligned", who);
+  if (const int rc = attn_check_dtype(who, dtype)) return rc;
+  if (const int rc = attn_check_hole(who, hole_count, hole_start, hole_end, Nk)) return rc;
+  if (const int rc = attn_check_layout(who, q, k, v, out, dtype, out_dt, ldq, ldk, ldv, ldo, strides)) return rc;
   const AttnStreams bs{bsq, bsk, bsv, bso};
   hipStream_t st = (hipStream_t)stream;
   if (dtype == FAR3D_DT_F32) {

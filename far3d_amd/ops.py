@@ -1016,28 +1016,42 @@ def attention_forward(q, k, v, num_heads=8, out=None, out_dtype=torch.float32, h
     return out
 
 
+def _batched_qkv(fn, q, k, v, num_heads):
+    """Operand checks of the batched attention entries `fn`: q (B,Aq,E), k/v (B,Nk,E) device tensors of one dtype with unit inner stride,
+    E a multiple of num_heads.  Returns (B, Aq, Nk, E, head_dim)."""
+    for t, n in ((q, "q"), (k, "k"), (v, "v")):
+        if not isinstance(t, torch.Tensor) or t.dim() != 3 or t.stride(2) != 1 or not t.is_cuda:
+            raise ValueError("%s: %s must be a 3-D device tensor (B, rows, E) with unit inner stride" % (fn, n))
+    if not (q.dtype == k.dtype == v.dtype):
+        raise TypeError("%s: q/k/v dtypes differ" % fn)
+    B, Aq, E = q.shape
+    Nk = k.shape[1]
+    if k.shape != (B, Nk, E) or v.shape != (B, Nk, E):
+        raise ValueError("%s: k/v must be (%d, Nk, %d), got %s / %s" % (fn, B, E, tuple(k.shape), tuple(v.shape)))
+    if E % num_heads:
+        raise ValueError("%s: embed dim %d is not a multiple of num_heads %d" % (fn, E, num_heads))
+    return B, Aq, Nk, E, E // num_heads
+
+
+def _batched_out(fn, out, q, out_dtype):
+    """`out` of the batched attention entries `fn`: q's shape, unit inner stride, on the device; allocated in out_dtype when None.  Its
+    own step because attention_batched validates its masks first, and the order decides which error a call with two faults raises."""
+    B, Aq, E = q.shape
+    if out is None:
+        out = torch.empty((B, Aq, E), dtype=out_dtype, device=q.device)
+    elif tuple(out.shape) != (B, Aq, E) or out.stride(2) != 1 or not out.is_cuda:
+        raise ValueError("%s: out must be a (%d, %d, %d) device tensor with unit inner stride" % (fn, B, Aq, E))
+    return out
+
+
 def attention_streams(q, k, v, num_heads=8, out=None, out_dtype=torch.float32, hole=None):
     """attention_forward for B samples in ONE launch (far3d_attention_streams): out[b] has the bits of attention_forward on sample b.
     q (B,Aq,E), k/v (B,Nk,E) f32|bf16 with unit inner stride (views of one (B,rows,layers*3*E) buffer are read in place); out (B,Aq,E).
     hole: None or (counts int32 device tensor (B,), start, end): sample b masks the keys [start + counts[b], end).
     attention_f32_variant does not apply: a batch always takes the default fp32 kernel."""
     lib = _lib.require_device()
-    for t, n in ((q, "q"), (k, "k"), (v, "v")):
-        if not isinstance(t, torch.Tensor) or t.dim() != 3 or t.stride(2) != 1 or not t.is_cuda:
-            raise ValueError("attention_streams: %s must be a 3-D device tensor (B, rows, E) with unit inner stride" % n)
-    if not (q.dtype == k.dtype == v.dtype):
-        raise TypeError("attention_streams: q/k/v dtypes differ")
-    B, Aq, E = q.shape
-    Nk = k.shape[1]
-    if k.shape != (B, Nk, E) or v.shape != (B, Nk, E):
-        raise ValueError("attention_streams: k/v must be (%d, Nk, %d), got %s / %s" % (B, E, tuple(k.shape), tuple(v.shape)))
-    if E % num_heads:
-        raise ValueError("attention_streams: embed dim %d is not a multiple of num_heads %d" % (E, num_heads))
-    hd = E // num_heads
-    if out is None:
-        out = torch.empty((B, Aq, E), dtype=out_dtype, device=q.device)
-    elif tuple(out.shape) != (B, Aq, E) or out.stride(2) != 1 or not out.is_cuda:
-        raise ValueError("attention_streams: out must be a (%d, %d, %d) device tensor with unit inner stride" % (B, Aq, E))
+    B, Aq, Nk, E, hd = _batched_qkv("attention_streams", q, k, v, num_heads)
+    out = _batched_out("attention_streams", out, q, out_dtype)
     if hole is not None and hole[0].numel() != B:
         raise ValueError("attention_streams: the hole needs one count per sample (%d), got %d" % (B, hole[0].numel()))
     _lib.check(lib.far3d_attention_streams(_ptr(q), _ptr(k), _ptr(v), _dt(q), _ptr(out), _dt(out), B, Aq, Nk, num_heads, hd,
@@ -1054,18 +1068,7 @@ def attention_batched(q, k, v, num_heads=8, attn_mask=None, key_padding_mask=Non
     hold -inf; a dtype other than float32 is cast on the host).  key_padding_mask (B,Nk) bool / uint8: nonzero excludes the key.
     A query without any key left gets NaN in its whole row, as torch does."""
     lib = _lib.require_device()
-    for t, n in ((q, "q"), (k, "k"), (v, "v")):
-        if not isinstance(t, torch.Tensor) or t.dim() != 3 or t.stride(2) != 1 or not t.is_cuda:
-            raise ValueError("attention_batched: %s must be a 3-D device tensor (B, rows, E) with unit inner stride" % n)
-    if not (q.dtype == k.dtype == v.dtype):
-        raise TypeError("attention_batched: q/k/v dtypes differ")
-    B, Aq, E = q.shape
-    Nk = k.shape[1]
-    if k.shape != (B, Nk, E) or v.shape != (B, Nk, E):
-        raise ValueError("attention_batched: k/v must be (%d, Nk, %d), got %s / %s" % (B, E, tuple(k.shape), tuple(v.shape)))
-    if E % num_heads:
-        raise ValueError("attention_batched: embed dim %d is not a multiple of num_heads %d" % (E, num_heads))
-    hd = E // num_heads
+    B, Aq, Nk, E, hd = _batched_qkv("attention_batched", q, k, v, num_heads)
     kind, mptr, ldm, mbs = 0, None, 0, 0
     if attn_mask is not None:
         if not isinstance(attn_mask, torch.Tensor) or not attn_mask.is_cuda:
@@ -1102,10 +1105,7 @@ def attention_batched(q, k, v, num_heads=8, attn_mask=None, key_padding_mask=Non
         key_padding_mask = key_padding_mask.contiguous()
         key_padding_mask = key_padding_mask.view(torch.uint8) if key_padding_mask.dtype == torch.bool else key_padding_mask
         pptr = _ptr(key_padding_mask)
-    if out is None:
-        out = torch.empty((B, Aq, E), dtype=out_dtype, device=q.device)
-    elif tuple(out.shape) != (B, Aq, E) or out.stride(2) != 1 or not out.is_cuda:
-        raise ValueError("attention_batched: out must be a (%d, %d, %d) device tensor with unit inner stride" % (B, Aq, E))
+    out = _batched_out("attention_batched", out, q, out_dtype)
     _lib.check(lib.far3d_attention_batched(_ptr(q), _ptr(k), _ptr(v), _dt(q), _ptr(out), _dt(out), B, Aq, Nk, num_heads, hd,
                                            q.stride(1), k.stride(1), v.stride(1), out.stride(1),
                                            q.stride(0), k.stride(0), v.stride(0), out.stride(0), float(hd) ** -0.5,

@@ -65,6 +65,30 @@ def test_attention_bf16_mode(hip_lib):
     assert (got - want).abs().mean().item() < 1e-3
 
 
+@pytest.mark.parametrize("Aq,Nk", [(1, 1), (33, 65)])
+def test_attention_smallest_inputs_reach_the_merge(hip_lib, Aq, Nk):
+    """The merge of the key parts with the smallest inputs, in every kernel form.  (1, 1): every part but the first saw no key (m = -inf,
+    weight 0) and every query lane but one is out of range.  (33, 65): a second wave with one live lane and a second tile of one key."""
+    from far3d_amd import ops
+    g = torch.Generator().manual_seed(100 * Aq + Nk)
+    q, k, v = (torch.randn(n, 256, generator=g) for n in (Aq, Nk, Nk))
+    want = _mha_core(q, k, v, 8)
+    for variant in (0, 14, 118, 4, 2):
+        prev = ops.attention_f32_variant(variant)
+        try:
+            got = ops.attention_forward(q.to(DEV), k.to(DEV), v.to(DEV)).cpu()
+        finally:
+            ops.attention_f32_variant(prev)
+        err = (got - want).abs().max().item()
+        print("f32 variant %d (%d, %d): max %.3e" % (variant, Aq, Nk, err))
+        assert err < 2e-5, variant
+    qb, kb, vb = (t.to(torch.bfloat16) for t in (q, k, v))
+    want = _mha_core(qb.float(), kb.float(), vb.float(), 8)
+    d = (ops.attention_forward(qb.to(DEV), kb.to(DEV), vb.to(DEV)).cpu() - want).abs()
+    print("bf16 (%d, %d): max %.3e mean %.3e" % (Aq, Nk, d.max().item(), d.mean().item()))
+    assert d.max().item() < 1e-2 and d.mean().item() < 1e-3
+
+
 def test_attention_strided_views_of_one_buffer(hip_lib):
     """q/k/v produced by one GEMM into a (rows, 768) buffer are consumed in place."""
     from far3d_amd import ops
