@@ -500,32 +500,53 @@ __global__ __launch_bounds__(TOPK_THREADS) void decode_topk_kernel(DecodeParams 
 // layer's outputs and do not depend on each other: workgroup 0 decodes, workgroup 1 ranks the max-class scores -- one launch, the two
 // latency chains side by side on two CUs (in the frame each such launch costs ~8 us of cold start on top of its own time).  Same code
 // paths as the two stand-alone kernels: identical results.
-template <int MAXV>
+//
+// STREAMS (far3d_decode_topk_mem_streams): B scene streams in one launch of 2 * B workgroups.  A workgroup is still the decode or the
+// memory ranking of ONE stream and knows nothing about the others: the stream is a second grid index (blockIdx.y) that moves every
+// operand's base by b times a per-operand stride (64-bit, elements); the body behind the bases is the one-stream code, so stream b
+// gets the bits of the one-stream launch on its operands.  The strides arrive as ONE trailing kernel argument that only the streams
+// instantiations have (BS = DecodeStreams; the one-stream instantiations have an empty pack: their argument list, and their code,
+// are what they were).
+struct DecodeStreams { long cls, box, boxes, scores, labels, keep, vals2, idx2; };
+__device__ __forceinline__ const DecodeStreams& decode_streams_arg(const DecodeStreams& s) { return s; }
+template <int MAXV, typename... BS>     // BS: DecodeStreams (blockIdx.y = stream) or nothing
 __global__ __launch_bounds__(TOPK_THREADS) void decode_topk_mem_kernel(DecodeParams p, int n, const float* __restrict__ vals2, int n2, int K2,
-                                                                       long* __restrict__ idx2) {
+                                                                       long* __restrict__ idx2, BS... bs) {
+  const float* cls = p.cls;
+  const float* box = p.box;
+  float* boxes = p.boxes;
+  float* scores = p.scores;
+  long* labels = p.labels;
+  unsigned char* keep = p.keep;
+  if constexpr (sizeof...(BS) > 0) {
+    const long sb = blockIdx.y;
+    const DecodeStreams& s = decode_streams_arg(bs...);
+    cls += sb * s.cls; box += sb * s.box; boxes += sb * s.boxes; scores += sb * s.scores; labels += sb * s.labels; keep += sb * s.keep;
+    vals2 += sb * s.vals2; idx2 += sb * s.idx2;
+  }
   __shared__ unsigned long long sel[TOPK_MAXK];
   if (blockIdx.x == 1) {
     block_topk_sorted<4>(vals2, n2, K2, sel);
     for (int i = threadIdx.x; i < K2; i += TOPK_THREADS) idx2[i] = (long)(0xffffffffu - (unsigned)(sel[i] & 0xffffffffull));
     return;
   }
-  block_topk_sorted<MAXV>(p.cls, n, p.K, sel);
+  block_topk_sorted<MAXV>(cls, n, p.K, sel);
   for (int i = threadIdx.x; i < p.K; i += TOPK_THREADS) {
     const unsigned long long e = sel[i];
     const int idx = (int)(0xffffffffu - (unsigned)(e & 0xffffffffull));
     const float logit = ord_val((unsigned)(e >> 32));
     const int q = idx / p.ncls;
-    p.labels[i] = (long)(idx - q * p.ncls);
-    p.scores[i] = 1.f / (1.f + expf(-logit));
-    const float* b = p.box + (long)q * p.code;
-    float* o = p.boxes + (long)i * (p.code - 1);
+    labels[i] = (long)(idx - q * p.ncls);
+    scores[i] = 1.f / (1.f + expf(-logit));
+    const float* b = box + (long)q * p.code;
+    float* o = boxes + (long)i * (p.code - 1);
     const float cx = b[0], cy = b[1], cz = b[2];
     const float w = expf(b[3]), l = expf(b[4]), h = expf(b[5]);
     o[0] = cx; o[1] = cy; o[2] = cz - h * 0.5f;
     o[3] = w; o[4] = l; o[5] = h;
     o[6] = atan2f(b[6], b[7]);
     for (int k = 8; k < p.code; ++k) o[k - 1] = b[k];
-    p.keep[i] = (cx >= p.lo[0] && cy >= p.lo[1] && cz >= p.lo[2] && cx <= p.hi[0] && cy <= p.hi[1] && cz <= p.hi[2]) ? 1 : 0;
+    keep[i] = (cx >= p.lo[0] && cy >= p.lo[1] && cz >= p.lo[2] && cx <= p.hi[0] && cy <= p.hi[1] && cz <= p.hi[2]) ? 1 : 0;
   }
 }
 
@@ -618,6 +639,76 @@ extern "C" int far3d_decode_topk_mem(const float* cls_last, const float* box_las
   else
     hipLaunchKernelGGL(decode_topk_mem_kernel<TOPK_MAXV>, dim3(2), dim3(TOPK_THREADS), 0, st, p, (int)n, mem_scores, mem_n, mem_K, (long*)mem_idx_out);
   FAR3D_CHECK_LAUNCH("far3d_decode_topk_mem");
+  return FAR3D_OK;
+}
+
+// far3d_decode_topk_mem for B scene streams: one launch of the STREAMS instantiations (grid (2, B)) where the one-stream entry takes its
+// fused launch; otherwise that entry per stream, each with its own slice of the workspace.  Every size rule of the one-stream entry is
+// checked here first, so that a bad argument launches nothing for any stream.
+extern "C" int far3d_decode_topk_mem_streams(const float* cls_last, const float* box_last, int B, int A, int num_classes, int code_size,
+                                             int K, const float* post_center_range, float* boxes, float* scores, int64_t* labels,
+                                             unsigned char* keep, void* workspace, long workspace_bytes, const float* mem_scores,
+                                             int mem_n, int mem_K, int64_t* mem_idx_out, const long* batch_strides, void* stream) {
+  const char* who = "far3d_decode_topk_mem_streams";
+  FAR3D_CHECK_ARG(cls_last, "%s: cls_last is a null pointer", who);
+  FAR3D_CHECK_ARG(box_last, "%s: box_last is a null pointer", who);
+  FAR3D_CHECK_ARG(post_center_range, "%s: post_center_range is a null pointer", who);
+  FAR3D_CHECK_ARG(boxes, "%s: boxes is a null pointer", who);
+  FAR3D_CHECK_ARG(scores, "%s: scores is a null pointer", who);
+  FAR3D_CHECK_ARG(labels, "%s: labels is a null pointer", who);
+  FAR3D_CHECK_ARG(keep, "%s: keep is a null pointer", who);
+  FAR3D_CHECK_ARG(mem_scores, "%s: mem_scores is a null pointer", who);
+  FAR3D_CHECK_ARG(mem_idx_out, "%s: mem_idx_out is a null pointer", who);
+  FAR3D_CHECK_ARG(batch_strides, "%s: batch_strides is a null pointer", who);
+  FAR3D_CHECK_ARG(B >= 1 && B <= 65535, "%s: B=%d outside 1 .. 65535 (the grid's second index)", who, B);
+  FAR3D_CHECK_ARG(mem_n > 0 && mem_n <= TOPK_THREADS * TOPK_MAXV && mem_K > 0 && mem_K <= mem_n && mem_K <= TOPK_MAXK,
+                  "%s: need 0 < mem_K <= min(mem_n, %d), mem_n <= %d (got mem_n=%d mem_K=%d)", who, TOPK_MAXK, TOPK_THREADS * TOPK_MAXV, mem_n, mem_K);
+  const long n = (long)A * num_classes;
+  FAR3D_CHECK_ARG(A > 0 && num_classes > 0 && code_size >= 8 && K > 0 && K <= TOPK_MAXK && n < (1L << 30) && K <= n,
+                  "%s: bad sizes A=%d num_classes=%d code_size=%d K=%d (K <= %d)", who, A, num_classes, code_size, K, TOPK_MAXK);
+  if (n > DECODE_CHUNK) {
+    const int nchunks = (int)((n + DECODE_CHUNK - 1) / DECODE_CHUNK);
+    const long ncand = (long)nchunks * K;
+    FAR3D_CHECK_ARG(ncand <= DECODE_CHUNK, "%s: A*num_classes=%ld needs %d chunks x K=%d candidates > %d", who, n, nchunks, K, DECODE_CHUNK);
+    FAR3D_CHECK_ARG(workspace && workspace_bytes >= ncand * 8 && ((uintptr_t)workspace % 8) == 0 && workspace_bytes % 8 == 0,
+                    "%s: A*num_classes=%ld > %d needs a workspace of B x workspace_bytes, workspace_bytes >= FAR3D_DECODE_WS_BYTES = %ld per "
+                    "stream and a multiple of 8, 8-byte aligned (got %ld)", who, n, DECODE_CHUNK, ncand * 8, workspace ? workspace_bytes : 0L);
+  }
+  // a stream's block of every operand lies behind the previous stream's: a smaller stride would make two workgroups share addresses
+  const long extent[8] = {n, (long)A * code_size, (long)K * (code_size - 1), K, K, K, mem_n, mem_K};
+  static const char* const names[8] = {"cls_last", "box_last", "boxes", "scores", "labels", "keep", "mem_scores", "mem_idx_out"};
+  for (int i = 0; i < 8; ++i)
+    FAR3D_CHECK_ARG(B == 1 || batch_strides[i] >= extent[i], "%s: batch_strides[%d] (%s) = %ld elements is below one stream's %ld", who, i,
+                    names[i], batch_strides[i], extent[i]);
+  const bool fused = n <= DECODE_CHUNK && mem_n <= TOPK_THREADS * 4;
+  const long* bs = batch_strides;
+  if (!fused) {
+    for (long b = 0; b < B; ++b) {
+      void* ws = workspace ? (char*)workspace + b * workspace_bytes : nullptr;
+      if (const int rc = far3d_decode_topk_mem(cls_last + b * bs[0], box_last + b * bs[1], A, num_classes, code_size, K, post_center_range,
+                                               boxes + b * bs[2], scores + b * bs[3], labels + b * bs[4], keep + b * bs[5], ws, workspace_bytes,
+                                               mem_scores + b * bs[6], mem_n, mem_K, mem_idx_out + b * bs[7], stream))
+        return rc;
+    }
+    return FAR3D_OK;
+  }
+  DecodeParams p;
+  p.cls = cls_last; p.box = box_last; p.boxes = boxes; p.scores = scores; p.labels = (long*)labels; p.keep = keep;
+  p.A = A; p.ncls = num_classes; p.code = code_size; p.K = K;
+  for (int k = 0; k < 3; ++k) { p.lo[k] = post_center_range[k]; p.hi[k] = post_center_range[3 + k]; }
+  const DecodeStreams ds{bs[0], bs[1], bs[2], bs[3], bs[4], bs[5], bs[6], bs[7]};
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 grid(2, B);
+  if (n <= TOPK_THREADS * 4)
+    hipLaunchKernelGGL((decode_topk_mem_kernel<4, DecodeStreams>), grid, dim3(TOPK_THREADS), 0, st, p, (int)n, mem_scores, mem_n, mem_K,
+                       (long*)mem_idx_out, ds);
+  else if (n <= TOPK_THREADS * 16)
+    hipLaunchKernelGGL((decode_topk_mem_kernel<16, DecodeStreams>), grid, dim3(TOPK_THREADS), 0, st, p, (int)n, mem_scores, mem_n, mem_K,
+                       (long*)mem_idx_out, ds);
+  else
+    hipLaunchKernelGGL((decode_topk_mem_kernel<TOPK_MAXV, DecodeStreams>), grid, dim3(TOPK_THREADS), 0, st, p, (int)n, mem_scores, mem_n, mem_K,
+                       (long*)mem_idx_out, ds);
+  FAR3D_CHECK_LAUNCH(who);
   return FAR3D_OK;
 }
 

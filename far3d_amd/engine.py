@@ -195,6 +195,7 @@ class Far3DEngine:
         self.convs = {}           # name -> PackedConv of every conv layer of the per-camera stages
         self._bufs = {}
         self.token_slices = {}      # buffer-set key -> callable (N, S, dtype) -> that set's token buffer (_token_buffer; streams.StreamBatch)
+        self.image_slices = {}      # buffer-set key -> callable (shape) -> that set's staged image buffer (_stage_inputs; streams.StreamBatch)
         self._ins = {}              # static input buffers per buffer-set parity (graph replay reads them)
         self._graph = None
         self._graph_outs = None
@@ -538,6 +539,45 @@ class Far3DEngine:
         tmp = ops.dwconv3x3_nhwc(src, layer["dw"], s, out=self._buf(("dw_tmp",) + shape, shape, self.prec["act"]), pair=self.pair)
         return ops.conv2d_nhwc(tmp, layer["pw"], out=out, act="relu")
 
+    def backbone_geometry(self, H, W):
+        """The backbone's maps for an H x W image, per image: dict(stem=(h, w, stored channels) of the stem1 / stem2 outputs, stages=[dict(
+        h, w, cat / cat_next / out = stored channels of the stage's first concat buffer, of its later blocks' (0: one block) and of its
+        block outputs)]).  backbone() takes its buffer shapes from here, and camera_image_span() its bound: one source for both."""
+        spec, cs = self.spec, self.cs
+        Lb = spec["layer_per_block"]
+        h, w = (H - 1) // 2 + 1, (W - 1) // 2 + 1                  # stem1: 3x3 / stride 2 / pad 1
+        geo = dict(stem=(h, w, max(spec["stem"][:2]) * cs), stages=[])
+        h, w = (h - 1) // 2 + 1, (w - 1) // 2 + 1                  # stem3: 3x3 / stride 2 / pad 1
+        in_ch = spec["stem"][2]
+        for si, nblk in enumerate(spec["block_per_stage"]):
+            sc, oc = spec["stage_conv_ch"][si], spec["stage_out_ch"][si]
+            if si > 0:                                             # MaxPool2d(3, 2, ceil_mode=True)
+                hp, wp = h, w
+                h, w = -(-(hp - 3) // 2) + 1, -(-(wp - 3) // 2) + 1
+                if (h - 1) * 2 >= hp:
+                    h -= 1
+                if (w - 1) * 2 >= wp:
+                    w -= 1
+            geo["stages"].append(dict(h=h, w=w, cat=(in_ch + Lb * sc) * cs, cat_next=(oc + Lb * sc) * cs if nblk > 1 else 0,
+                                      out=oc * cs))
+            in_ch = oc
+        return geo
+
+    def camera_image_span(self, H, W):
+        """Bytes of the largest map ONE H x W image has anywhere in camera_stage: the image, the stem's im2col rows and outputs, the
+        backbone's concat buffers and block outputs (backbone_geometry), and the 2D head's widest map (both towers of a level, at the
+        first FPN level; everything behind the backbone is smaller than the backbone's own maps at that level).  The kernels bound the
+        span of ALL images of a launch (streams.stream_chunks)."""
+        es = 4 if self.prec["act"] == torch.float32 else 2
+        geo = self.backbone_geometry(H, W)
+        sh, sw, sch = geo["stem"]
+        spans = [3 * H * W * 4, sh * sw * 32 * self.cs * es, sh * sw * sch * es]
+        spans += [g["h"] * g["w"] * max(g["cat"], g["cat_next"], g["out"]) * es for g in geo["stages"]]
+        if len(geo["stages"]) > 1:
+            g = geo["stages"][1]
+            spans.append(g["h"] * g["w"] * 512 * self.cs * 4)
+        return max(spans)
+
     @_with_tile_tables
     def backbone(self, img, keep_stage2=True):
         """img (N,3,H,W) f32 NCHW on device -> [stage2..stage5] dense NHWC maps (pair mode: 2C stored bf16 channels each).
@@ -571,7 +611,8 @@ class Far3DEngine:
             x = ops.stem_im2col(img, act, pair=pair)
             x = ops.conv2d_nhwc(x, self.bb["stem1"], act="relu")
         x = self._layer3(x, self.bb["stem2"])
-        H, W = (x.shape[1] - 1) // 2 + 1, (x.shape[2] - 1) // 2 + 1       # stem3: 3x3 / stride 2 / pad 1
+        geo = self.backbone_geometry(img.shape[2], img.shape[3])
+        assert tuple(x.shape[1:]) == (geo["stem"][0], geo["stem"][1], spec["stem"][1] * cs), (tuple(x.shape), geo["stem"])
         in_ch = spec["stem"][2]
         outs = []
         stage_in = None   # dense input of the stage (stem3 output is written straight into the first concat buffer)
@@ -579,16 +620,11 @@ class Far3DEngine:
         next_cat = None            # ... into this tensor (the next stage's first concat buffer)
         for si, blocks in enumerate(self.bb["stages"]):
             sc, oc = spec["stage_conv_ch"][si], spec["stage_out_ch"][si]
-            if si > 0:
-                Hp, Wp = H, W
-                H, W = -(-(Hp - 3) // 2) + 1, -(-(Wp - 3) // 2) + 1
-                if (H - 1) * 2 >= Hp:
-                    H -= 1
-                if (W - 1) * 2 >= Wp:
-                    W -= 1
+            g = geo["stages"][si]
+            H, W = g["h"], g["w"]
             # this stage's first concat buffer: the SAME tensor the previous stage's last eSE pass pooled into (fetched once there and
             # handed over: a second _buf lookup with a drifted shape would silently allocate another buffer)
-            want_shape = (N, H, W, (in_ch + Lb * sc) * cs)
+            want_shape = (N, H, W, g["cat"])
             if next_cat is not None:
                 assert tuple(next_cat.shape) == want_shape, (tuple(next_cat.shape), want_shape)
                 cat, next_cat = next_cat, None
@@ -611,22 +647,23 @@ class Far3DEngine:
                     self._layer3(src, pc, out=dst)
                     src = dst
                 fuse = esums is not None and ops.conv_can_fuse_sums(cat, blk["concat"])
-                xt = ops.conv2d_nhwc(cat, blk["concat"], out=self._buf(("xt", si), (N, H, W, oc * cs), act), act="relu",
+                xt = ops.conv2d_nhwc(cat, blk["concat"], out=self._buf(("xt", si), (N, H, W, g["out"]), act), act="relu",
                                      sums=esums if fuse else None)
                 idn = cat[..., :cur_in * cs] if bi > 0 else None
                 will_fuse = fuse and ops.ese_fused_ok(xt, pair) and (idn is None or ops.ese_fused_ok(idn, pair))
                 pooled = None
                 if will_fuse and last and si + 1 < len(self.bb["stages"]):   # the next stage's input slice: MaxPool2d(3, 2, ceil) of this output
                     Hn, Wn = ops.maxpool_out_hw(H, W)
-                    nsc = spec["stage_conv_ch"][si + 1]
-                    next_cat = self._buf(("cat", si + 1, 0), (N, Hn, Wn, (oc + Lb * nsc) * cs), act)
+                    gn = geo["stages"][si + 1]
+                    assert (Hn, Wn) == (gn["h"], gn["w"]), ((Hn, Wn), gn)
+                    next_cat = self._buf(("cat", si + 1, 0), (N, Hn, Wn, gn["cat"]), act)
                     pooled = next_cat[..., :oc * cs]
                 skip_out = pooled is not None and si == 0 and not keep_stage2     # nothing but the pooling reads the stage-2 map
                 if last:
                     out = None if skip_out else self._buf(("stage", si), (N, H, W, oc * cs), act)
                     nxt = None
                 else:
-                    nxt = self._buf(("cat", si, 1 + (bi % 2)), (N, H, W, (oc + Lb * sc) * cs), act)
+                    nxt = self._buf(("cat", si, 1 + (bi % 2)), (N, H, W, g["cat_next"]), act)
                     out = nxt[..., :oc * cs]
                 if will_fuse and (out is None or ops.ese_fused_ok(out, pair)):
                     ops.ese_fused_nhwc(xt, blk["fcw"], blk["fcb"], esums, egate, identity=idn, out=out, pooled=pooled, pair=pair)
@@ -1024,14 +1061,52 @@ class Far3DEngine:
         lidar2img = dd["lidar2img"][0, lo:hi]
         # img2lidar = inverse(lidar2img) (farhead.py:798) and the 14-float MLN code (farhead.py:553-556): one launch
         img2lidar, c14 = ops.camera_prep(lidar2img, dd["intrinsics"][0, lo:hi], dd["extrinsics"][0, lo:hi])
-        hh = self.sa["reduce"](c14, act="relu")
-        mln_scale, mln_shift = self.sa["gamma"](hh), self.sa["beta"](hh)           # (n, E) each
+        per = ops.plan_images(n)
+        if per == n:
+            hh = self.sa["reduce"](c14, act="relu")
+            mln_scale, mln_shift = self.sa["gamma"](hh), self.sa["beta"](hh)           # (n, E) each
+        else:
+            # the cameras of several scene streams (camera_stage_streams): these small GEMMs choose their kernel by the row count, so
+            # they stay per stream -- each on an aligned copy of its rows, like the one-stream pass's own c14
+            mln_scale, mln_shift = (torch.empty((n, E), dtype=torch.float32, device=self.dev) for _ in range(2))
+            for r in range(0, n, per):
+                hh = self.sa["reduce"](c14[r:r + per].clone(), act="relu")
+                self.sa["gamma"](hh, out=mln_scale[r:r + per])
+                self.sa["beta"](hh, out=mln_shift[r:r + per])
         feats = self.backbone(img, keep_stage2=False)
         raw, tokens, hw, starts = self.fpn(feats, mln_scale, mln_shift)
         st = dict(tokens=tokens, hw=hw, starts=starts, raw=raw, lidar2img=lidar2img, cams=(lo, hi))
         cls, reg, depth_logit = self.roi_head(raw)
         st.update(self.proposals(cls, reg, depth_logit, img2lidar, tokens, block_rows))
         return st
+
+    def camera_stage_streams(self, dds, pad_hw, key, img):
+        """camera_stage ONCE on the images of len(dds) scene streams (streams.StreamBatch): dds the streams' staged inputs
+        (_stage_inputs), each of N cameras; img (len(dds) * N, 3, H, W) their images, stream-major -- the buffer the streams staged
+        into (image_slices); key: the buffer set of this pass, whose token buffer (token_slices) spans the streams' slices of the
+        batch's one allocation.  lidar2img / intrinsics / extrinsics are the
+        streams' concatenated, so camera b * N + n is camera n of stream b everywhere; proposal selection and gather work per camera,
+        and in the static top-K mode stream b's rows are [b * N * K, (b + 1) * N * K) of the joint ref2d / ctx / box2d / score2d.
+        Every launch chooses its tile as ONE stream's N images would (ops.tiles_as_for), so each image has the bits of its own
+        stream's camera_stage.  Returns one `st` dict per stream, views into the joint results."""
+        cfg = self.cfg
+        nb, N, K = len(dds), dds[0]["img"].shape[0], cfg["proposal_topk"]
+        if K is None or self.md_k > 1:
+            raise ValueError("camera_stage_streams: the static top-K proposal mode with single-depth proposals only")
+        if tuple(img.shape) != (nb * N,) + tuple(dds[0]["img"].shape[1:]):
+            raise ValueError("camera_stage_streams: img %s is not the %d streams' %d images each" % (tuple(img.shape), nb, N))
+        joint = {k: torch.cat([dd[k] for dd in dds], dim=1) for k in ("lidar2img", "intrinsics", "extrinsics")}
+        with self.buffers(key), ops.tiles_as_for(N, nb * N):
+            st = self.camera_stage(img, joint, range(nb * N), pad_hw, block_rows=nb * N * K)
+        rows = lambda t, b, per: t[b * per:(b + 1) * per]
+        res = []
+        for b in range(nb):
+            res.append(dict(tokens=rows(st["tokens"], b, N), raw=[rows(r, b, N) for r in st["raw"]], hw=st["hw"], starts=st["starts"],
+                            lidar2img=rows(st["lidar2img"], b, N), cams=(0, N), depth_logit=rows(st["depth_logit"], b, N),
+                            peak_weight=rows(st["peak_weight"], b, N), sel_idx=rows(st["sel_idx"], b, N), sel_cnt=rows(st["sel_cnt"], b, N),
+                            m_dev=st["m_dev"], overflow=st["overflow"],
+                            **{k: rows(st[k], b, N * K) for k in ("ref2d", "ctx", "box2d", "score2d")}))
+        return res
 
     def proposals(self, cls, reg, depth_logit, img2lidar, tokens, block_rows=None):
         """a5 + the adaptive-query part of a6: peak selection and 3D proposal construction for n cameras.
@@ -1192,6 +1267,56 @@ class Far3DEngine:
         outs["result"] = result
         return outs
 
+    def _head_finish_streams(self, hss, outs_dec, enter):
+        """_head_finish for B scene streams (streams.StreamBatch): hss the B _head_prepare results, outs_dec decoder_streams' result
+        (B, layers, A, E), enter(b) a context manager that makes the engine stream b (its buffer set and streaming memory).  Returns the
+        B result dicts of _head_finish, bit for bit.  The row-local work runs once over all streams' rows on (B, layers * A, .)
+        buffers: ONE gathering copy of the decoder's (layers, B, A, E) rows into stream-major order, nan_to_num, the cls / reg branches
+        through ops.linear_streams (the tile of ONE stream's layers * A rows) and ops.layernorm (row-local); the decode and the
+        memory update's top-k of all streams are ONE far3d_decode_topk_mem_streams launch.  Per stream stay head_finalize and
+        memory_post_update.  The unfused branches only (StreamBatch refuses fused_rows)."""
+        cfg = self.cfg
+        E, at, nl, ncls, code = cfg["embed_dims"], self.prec["dec"], cfg["num_layers"], cfg["num_classes"], cfg["code_size"]
+        fast = at == torch.bfloat16
+        B, A = len(hss), hss[0].A
+        buf = lambda name, shape, dt: self._buf(("hs_" + name, B), shape, dt)
+        OD = buf("outs_dec", (B, nl, A, E), torch.float32)
+        OD.copy_(outs_dec)
+        flat = OD.view(-1, E)
+        flatb = ops.nan_to_num_(flat, bf16_copy=fast)
+        hin = (flatb if fast else flat).view(B, nl * A, E)
+        rows = lambda t: t.view(B * nl * A, t.shape[2])
+        blocks = lambda t: t.view(B, nl * A, t.shape[1])
+        r1 = ops.layernorm(rows(ops.linear_streams(hin, self.cls_b[0].pc)), *self.cls_ln[0], act="relu", bf16_copy=fast)
+        r2 = ops.layernorm(rows(ops.linear_streams(blocks(r1[1] if fast else r1), self.cls_b[1].pc)), *self.cls_ln[1], act="relu", bf16_copy=fast)
+        CLS = ops.linear_streams(blocks(r2[1] if fast else r2), self.cls_b[2].pc, out=buf("cls", (B, nl * A, ncls), torch.float32))
+        rr = ops.linear_streams(hin, self.reg_b[0].pc, act="relu", out_dtype=at)
+        rr = ops.linear_streams(ops.linear_streams(rr, self.reg_b[1].pc, act="relu", out_dtype=at), self.reg_b[2].pc)
+        BOX, SC = buf("box", (B, nl * A, code), torch.float32), buf("score", (B, A), torch.float32)
+        for b, hs in enumerate(hss):
+            ops.head_finalize(rr[b], hs.ref, CLS[b], cfg["pc_range"], nl, ncls, out=(BOX[b], SC[b]))
+        results, idx = self.decode_streams(CLS.view(B, nl, A, ncls)[:, -1], BOX.view(B, nl, A, code)[:, -1], SC, cfg["topk_proposals"])
+        res = []
+        for b, hs in enumerate(hss):
+            all_cls, all_box = CLS[b].view(nl, 1, A, ncls), BOX[b].view(nl, 1, A, code)
+            with enter(b):
+                ops.memory_post_update(hs.m, idx[b], OD[b, -1], all_box[-1][0], hs.dd["ego_pose"], hs.dd["timestamp"], self.mem)
+            outs = dict(all_cls_scores=all_cls, all_bbox_preds=all_box, outs_dec=OD[b], num_adaptive=hs.M, num_adaptive_dev=hs.m_dev,
+                        feat_flatten=hs.tokens, reference_points=hs.ref, memory_topk=idx[b])
+            outs["result"] = {k: v[b] for k, v in results.items()}
+            res.append(outs)
+        return res
+
+    def decode_streams(self, cls_last, box_last, mem_scores, mem_K):
+        """`decode` of B scene streams in one launch: cls_last (B, A, num_classes) / box_last (B, A, code_size) the last layer's logits
+        and boxes, mem_scores (B, A) -- views with contiguous streams.  -> (dict of (B, .) results, idx (B, mem_K))."""
+        cfg = self.cfg
+        B, A, ncls = cls_last.shape
+        K = min(cfg["max_num"], A * ncls)
+        need = ops.decode_ws_bytes(A * ncls, K)
+        ws = self._buf(("decode_ws_streams", B), (B * need,), torch.uint8) if need else None
+        return ops.decode_topk_mem_streams(cls_last, box_last, K, cfg.get("post_center_range", cfg["pc_range"]), mem_scores, mem_K, workspace=ws)
+
     def _stage_inputs(self, data):
         """Copy the frame's inputs into static device buffers (so that a captured graph can be replayed on them)."""
         dev = self.dev
@@ -1205,7 +1330,10 @@ class Far3DEngine:
             # (re)allocation: graphs captured on the old buffers of THIS parity are stale.  The single-graph mode drops its graph
             # here; the pipeline's per-parity graphs are dropped by FramePipeline.slot BEFORE it decides to replay (this dict is no
             # longer the one they were captured on), and its streams are never dropped, so a scene start can always wait for heads in flight.
-            cur = dict(img=torch.empty(tuple(img.shape), dtype=torch.float32, device=dev))
+            # a buffer set with an entry in image_slices (a scene stream of streams.StreamBatch) stages its images in the slice that callable
+            # hands out -- its part of ONE (B * N, 3, H, W) buffer, which camera_stage_streams reads without a copy
+            owner = self.image_slices.get(self._par)
+            cur = dict(img=owner(tuple(img.shape)) if owner is not None else torch.empty(tuple(img.shape), dtype=torch.float32, device=dev))
             for k in keys:
                 cur[k] = torch.empty(tuple(data[k].shape), dtype=torch.float64 if k == "timestamp" else torch.float32, device=dev)
             self._ins[self._par] = cur

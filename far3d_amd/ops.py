@@ -431,6 +431,61 @@ def use_tile_tables(bf16_table, pair_table=None):
         _TABLE_SEL.cur = prev
 
 
+@contextlib.contextmanager
+def tiles_as_for(images, of):
+    """Inside the block (this thread only), a convolution on `of` images chooses its tile as the same layer on `images` images would:
+    the table lookups of _conv_plan and group_tile see images / of of the pixels, and where they leave the choice to the library's
+    heuristic (tile 0) and that heuristic reads the pixel count, the launch gets the heuristic's answer for `images` images as an
+    explicit tile -- or is refused by name where no explicit tile reproduces it (_pin_auto_tile).  For a pass over the images of several
+    scene streams at once (Far3DEngine.camera_stage_streams): a tile fixes the order in which a pixel's products are added, so every
+    image keeps the bits of its own stream's pass.  Calls on any other image count (linear(): one image) are not touched."""
+    images, of = int(images), int(of)
+    if images < 1 or of % images:
+        raise ValueError("tiles_as_for: %d images is not a whole number of blocks of %d" % (of, images))
+    prev = getattr(_TABLE_SEL, "as_for", None)
+    _TABLE_SEL.as_for = (images, of)
+    try:
+        yield
+    finally:
+        _TABLE_SEL.as_for = prev
+
+
+def plan_images(N):
+    """The image count whose tile choice a launch on N images takes (tiles_as_for; N itself outside one)."""
+    sel = getattr(_TABLE_SEL, "as_for", None)
+    return sel[0] if sel is not None and sel[1] == N else N
+
+
+def _auto_tile(npix, Cout):
+    """igemm_auto_tile (csrc/igemm_kernels.hpp): the register-staged kernel's tile for tile = 0."""
+    if Cout <= 64:
+        return 2 if npix >= 128 * 512 else 3
+    if -(-npix // 128) * -(-Cout // 128) >= 512:
+        return 1
+    return 4 if -(-npix // 64) * -(-Cout // 128) >= 512 else 3
+
+
+def _pin_auto_tile(x, pc, pair_in, n, Ho, Wo):
+    """tile = 0 on x's N images, to be chosen as for n < N of them: what far3d_conv2d_nhwc's own choice (csrc/igemm.hip,
+    igemm_pair.hip) reads the pixel count for, answered for n images.  Pair-stored 3x3 / stride 1 / pad 1 and 1x1 / stride 1 layers
+    have fixed defaults (160 / 179) and stay 0.  The register-staged kernel's heuristic (igemm_auto_tile) becomes an explicit id 1-5,
+    which takes the same kernel.  fp32 rows x split weights on a 1x1 layer may take tiles 479 / 480 by the pixel count, and whether
+    they do depends on alignment the library checks: left at 0 where neither heuristic changes its answer, refused otherwise."""
+    N = x.shape[0]
+    one, all_ = n * Ho * Wo, N * Ho * Wo
+    g1 = (pc.KH, pc.KW, pc.stride, pc.pad) == (1, 1, 1, 0)
+    g3 = (pc.KH, pc.KW, pc.stride, pc.pad) == (3, 3, 1, 1)
+    if pair_in and (g1 or g3):
+        return 0
+    if not pair_in and x.dtype == torch.float32 and pc.w_code == DT_F32_BF16X3 and g1:
+        big = lambda px: -(-px // 128) * -(-pc.Cout // 128) >= 2048
+        if big(one) != big(all_) or _auto_tile(one, pc.Cout) != _auto_tile(all_, pc.Cout):
+            raise ValueError("tiles_as_for: the 1x1 layer %d -> %d on fp32 rows with split weights has no tile-table entry, and the library's "
+                             "choice for %d images differs from its choice for %d; run it per %d images" % (pc.Cin, pc.Cout, N, n, n))
+        return 0
+    return _auto_tile(one, pc.Cout)
+
+
 GROUP_MAX = 16                  # FAR3D_WS_GROUP_MAX in include/far3d_hip.h
 GROUP_TILE_TABLE = "tuning_mi355x_groups.json"
 
@@ -588,12 +643,16 @@ def _conv_plan(x, pc, out_dtype, res=None, y2=None, sums=None, tile=0, out=None)
              ((pc.KH == 3 and pc.KW == 3 and pc.pad == 1 and sums is None) or
               (pc.KH == 1 and pc.KW == 1 and pc.pad == 0 and pair_in and (sums is None or (Ho * Wo >= 256 and Cin >= 192)))) and
              Cin % 32 == 0 and pc.Cout % 32 == 0 and out_dtype == torch.bfloat16 and dense)
+    Nt = plan_images(N)          # tiles_as_for: the image count whose choice this launch takes
+    auto = tile == 0
     if pair_in:
-        tile = _pair_tile(pc, Cin, N * H * W, tile, ws_ok)
+        tile = _pair_tile(pc, Cin, Nt * H * W, tile, ws_ok)
     elif tile == 0 and x.dtype == torch.bfloat16:
-        tile = _tuned_tile(pc.Cout, Cin, pc.KH, pc.stride, N * H * W, ws_ok=ws_ok)
+        tile = _tuned_tile(pc.Cout, Cin, pc.KH, pc.stride, Nt * H * W, ws_ok=ws_ok)
     elif tile == 0 and pc.w_code == DT_F32_BF16X3:
-        tile = _tuned_tile(pc.Cout, Cin, pc.KH, pc.stride, N * H * W, "tuning_mi355x_bf16x3.json")
+        tile = _tuned_tile(pc.Cout, Cin, pc.KH, pc.stride, Nt * H * W, "tuning_mi355x_bf16x3.json")
+    if auto and tile == 0 and Nt != N:
+        tile = _pin_auto_tile(x, pc, pair_in, Nt, Ho, Wo)
     return pair_in, ws_ok, tile
 
 
@@ -676,6 +735,9 @@ def group_tile(name, npix, table=None):
     cands = _table(table or GROUP_TILE_TABLE, groups=True).get(name)
     if not cands:
         return 0
+    sel = getattr(_TABLE_SEL, "as_for", None)
+    if sel is not None:          # tiles_as_for: npix counts the pixels of sel[1] images; the group is chosen as for sel[0] of them
+        npix = npix * sel[0] // sel[1]
     npx, tile = min(cands, key=lambda c: abs(c[0] - npix))
     return tile if 4 * abs(npx - npix) <= npx else 0
 
@@ -1975,17 +2037,24 @@ def memory_prepare(state, ego_pose_inv, timestamp, pseudo_ref, dim_t256, prev_ex
     return m, temp_ref, nerf, tpos
 
 
-def head_finalize(reg, ref, cls_all, pc_range, layers, num_classes, hole=None):
+def head_finalize(reg, ref, cls_all, pc_range, layers, num_classes, hole=None, out=None):
     """reg (layers*A, code) -> box (layers*A, code) with metres in [:3]; score (A,) = max-class sigmoid of the last layer.
     cls_all: the contiguous (layers, ..., A, num_classes) logits.  hole: rows without a query get score -inf and -inf logits in
-    every layer, written into cls_all in place (see _hole)."""
+    every layer, written into cls_all in place (see _hole).  out: optional contiguous f32 (box, score) to write into."""
     lib = _lib.require_device()
     A, code = ref.shape[0], reg.shape[1]
     _chk(cls_all, "cls_all", torch.float32)
     if cls_all.numel() != layers * A * num_classes:
         raise ValueError("head_finalize: cls_all must hold layers * A * num_classes logits")
-    box = torch.empty_like(reg)
-    score = torch.empty((A,), dtype=torch.float32, device=reg.device)
+    if out is not None:
+        box, score = out
+        _chk(box, "out box", torch.float32)
+        _chk(score, "out score", torch.float32)
+        if tuple(box.shape) != tuple(reg.shape) or tuple(score.shape) != (A,):
+            raise ValueError("head_finalize: out must be (box %s, score (%d,))" % (tuple(reg.shape), A))
+    else:
+        box = torch.empty_like(reg)
+        score = torch.empty((A,), dtype=torch.float32, device=reg.device)
     pk, pp = _host_f32(list(pc_range))
     _lib.check(lib.far3d_head_finalize(_ptr(reg), _ptr(ref), _ptr(cls_all), _ptr(box), _ptr(score), layers, A, code, num_classes, pp,
                                        *_hole(hole), _stream(reg)), "far3d_head_finalize")
@@ -2132,6 +2201,43 @@ def decode_topk(cls_last, box_last, K, post_center_range, workspace=None, mem_sc
     _lib.check(lib.far3d_decode_topk(_ptr(cls_last), _ptr(box_last), A, ncls, code, int(K), rp, _ptr(boxes), _ptr(scores), _ptr(labels),
                                      _ptr(keep), _ptr(workspace) if need else None, need, _stream(cls_last)), "far3d_decode_topk")
     return res
+
+
+def decode_topk_mem_streams(cls_last, box_last, K, post_center_range, mem_scores, mem_K, workspace=None):
+    """decode_topk(..., mem_scores, mem_K) for B scene streams in ONE launch of 2 * B workgroups (far3d_decode_topk_mem_streams):
+    cls_last (B, A, ncls), box_last (B, A, code), mem_scores (B, n) f32, each stream's block contiguous, any stride between the blocks (so
+    they may be views into larger buffers).  Returns (dict(boxes_3d (B, K, code-1), scores_3d (B, K), labels_3d (B, K) i64, keep (B, K)
+    bool), idx (B, mem_K) i64); [b] of each has the bits of the one-stream call on stream b's operands, whatever B is.  Shapes outside
+    the fused launch (A * ncls > 40960 or n > 4096) run the one-stream entry per stream; workspace: optional uint8 device buffer of
+    B * decode_ws_bytes(A * ncls, K) bytes for that case (allocated here when needed and not given)."""
+    lib = _lib.require_device()
+    for t, name in ((cls_last, "cls_last"), (box_last, "box_last")):
+        if t.dim() != 3 or t.dtype != torch.float32 or not t.is_cuda or not t[0].is_contiguous():
+            raise ValueError("decode_topk_mem_streams: %s must be a (B, A, C) float32 device tensor with contiguous streams" % name)
+    if mem_scores.dim() != 2 or mem_scores.dtype != torch.float32 or not mem_scores.is_cuda or mem_scores.stride(1) != 1:
+        raise ValueError("decode_topk_mem_streams: mem_scores must be a (B, n) float32 device tensor with unit inner stride")
+    B, A, ncls = cls_last.shape
+    code = box_last.shape[2]
+    if box_last.shape[:2] != (B, A) or mem_scores.shape[0] != B:
+        raise ValueError("decode_topk_mem_streams: cls_last %s, box_last %s and mem_scores %s disagree on (B, A)" %
+                         (tuple(cls_last.shape), tuple(box_last.shape), tuple(mem_scores.shape)))
+    K, mem_K, dev = int(K), int(mem_K), cls_last.device
+    boxes = torch.empty((B, K, code - 1), dtype=torch.float32, device=dev)
+    scores = torch.empty((B, K), dtype=torch.float32, device=dev)
+    labels = torch.empty((B, K), dtype=torch.int64, device=dev)
+    keep = torch.empty((B, K), dtype=torch.bool, device=dev)
+    idx = torch.empty((B, mem_K), dtype=torch.int64, device=dev)
+    rk, rp = _host_f32(list(post_center_range))
+    need = decode_ws_bytes(A * ncls, K)
+    if need and (workspace is None or workspace.numel() * workspace.element_size() < B * need):
+        workspace = torch.empty((B * need,), dtype=torch.uint8, device=dev)
+    strides = (ctypes.c_long * 8)(cls_last.stride(0), box_last.stride(0), boxes.stride(0), scores.stride(0), labels.stride(0), keep.stride(0),
+                                  mem_scores.stride(0), idx.stride(0))
+    _lib.check(lib.far3d_decode_topk_mem_streams(_ptr(cls_last), _ptr(box_last), B, A, ncls, code, K, rp, _ptr(boxes), _ptr(scores), _ptr(labels),
+                                                 _ptr(keep), _ptr(workspace) if need else None, need, _ptr(mem_scores), mem_scores.shape[1],
+                                                 mem_K, _ptr(idx), ctypes.cast(strides, ctypes.c_void_p), _stream(cls_last)),
+               "far3d_decode_topk_mem_streams")
+    return dict(boxes_3d=boxes, scores_3d=scores, labels_3d=labels, keep=keep), idx
 
 
 def camera_prep(lidar2img, intrinsics=None, extrinsics=None):

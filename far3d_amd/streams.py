@@ -1,11 +1,16 @@
-"""StreamBatch: several scene streams on ONE engine -- one set of weights, one decoder pass per call for all of them.
+"""StreamBatch: several scene streams on ONE engine -- one set of weights, one pass per call for all of them.
 
 Far3DEngine.forward_frame runs one scene stream (its `B == 1` assertion stays).  StreamBatch(engine, streams=B) takes one frame per
-stream and call: the camera stage and the head's bookkeeping (memory prepare, position codes, MLN rows, cls / reg branches, finalize,
-decode, memory update) run per stream on the engine's own code, each stream in its own buffer set and with its own streaming memory;
-the six decoder layers run once for all streams (Far3DEngine.decoder_streams: per layer one far3d_attention_streams launch, one
-far3d_aggregate_batched launch, every row-local launch over all B * A rows).  Every stream's outputs are, bit for bit, those of a
-plain engine with the same weights fed that stream's frames -- whatever B is, and for B = 1 too.
+stream and call.  Per stream stay the parts that carry a stream's own state: staging its inputs, the streaming memory (memory prepare,
+scene change, memory update), the query construction and head_finalize, each stream in its own buffer set.  Shared by all streams:
+  * the six decoder layers (Far3DEngine.decoder_streams: per layer one far3d_attention_streams launch, one far3d_aggregate_batched
+    launch, every row-local launch over all B * A rows) -- always;
+  * camera_batch: the camera stage (backbone, FPN, 2D head, proposals) as ONE pass over the B * N images of the B frames
+    (Far3DEngine.camera_stage_streams), in chunks of streams where the kernels' 32-bit extents bound a launch (stream_chunks);
+  * head_batch: the cls / reg branches over every stream's layers * A rows as one launch sequence, and the decode and memory top-k of
+    all streams as ONE far3d_decode_topk_mem_streams launch (Far3DEngine._head_finish_streams).
+With both switches off a call is the per-stream camera stage and head around the one decoder pass.  Every stream's outputs are, bit
+for bit, those of a plain engine with the same weights fed that stream's frames -- whatever B is, for B = 1 too, with any switches.
 
 Scope: eager execution on one GPU in the static top-K proposal mode (cfg proposal_topk = K) with single-depth proposals and the
 unfused decoder layers.  That mode has no hole of unused query rows, which far3d_aggregate_batched cannot skip.  Everything else is
@@ -16,6 +21,29 @@ import functools
 import torch
 
 from . import ops
+
+# What the convolution entries bound for ONE launch (csrc/igemm.hip, far3d_conv2d_nhwc; csrc/conv_ws.hip, the grouped entry): the span
+# of all images of an input map in bytes -- ((N - 1) * image stride + H * W * pixel stride) * element size < 0x7fffffff -- and the
+# pixel count, N * H * W < 2^31 - 4096.  A map of at least one byte per pixel meets the second whenever it meets the first.
+SPAN_LIMIT_BYTES = 0x7fffffff
+
+
+def stream_chunks(streams, images, image_span, limit=SPAN_LIMIT_BYTES, max_streams=None):
+    """Sizes of the camera passes for `streams` scene streams of `images` cameras each: a list of stream counts, in stream order, that
+    sums to `streams`.  image_span: bytes of the largest map one image has in the pass (Far3DEngine.camera_image_span); a pass of n
+    streams keeps n * images * image_span below `limit`, the bound of the kernels' 32-bit extents, so the library never has to refuse
+    a launch for the chunking to be found.  max_streams caps the streams per pass.  A pass is never empty: where even one stream is
+    over the limit the passes are single streams, which then fail or run exactly as the per-stream camera stage does."""
+    streams, images, image_span = int(streams), int(images), int(image_span)
+    if streams < 1 or images < 1 or image_span < 1:
+        raise ValueError("stream_chunks: streams=%d images=%d image_span=%d must all be positive" % (streams, images, image_span))
+    if max_streams is not None and int(max_streams) < 1:
+        raise ValueError("stream_chunks: max_streams=%s: a pass holds at least one stream" % (max_streams,))
+    per = max(1, (int(limit) - 1) // (images * image_span))          # the largest n with n * images * image_span < limit
+    if max_streams is not None:
+        per = min(per, int(max_streams))
+    per = min(per, streams)
+    return [per] * (streams // per) + ([streams % per] if streams % per else [])
 
 
 def _refusal(engine):
@@ -44,19 +72,31 @@ def _refusal(engine):
 
 
 class StreamBatch:
-    def __init__(self, engine, streams):
+    def __init__(self, engine, streams, camera_batch=True, head_batch=True, max_camera_streams=None):
+        """camera_batch / head_batch: the shared camera pass and the shared head launches (module docstring); both off is the
+        per-stream path around the one decoder pass.  max_camera_streams caps the streams of one camera pass (stream_chunks)."""
         if int(streams) < 1:
             raise ValueError("streams=%s: at least one scene stream" % (streams,))
+        if max_camera_streams is not None and int(max_camera_streams) < 1:
+            raise ValueError("max_camera_streams=%s: a camera pass holds at least one stream" % (max_camera_streams,))
         why = _refusal(engine)
         if why is not None:
             raise ValueError("StreamBatch: " + why)
         self.engine, self.streams = engine, int(streams)
+        self.camera_batch, self.head_batch, self.max_camera_streams = bool(camera_batch), bool(head_batch), max_camera_streams
+        self.camera_chunks = None   # the stream counts of the latest call's camera passes (camera_batch)
         # per stream: the streaming memory (allocated once, zeroed in place on that stream's scene change) and the scene it is in
         self._state = [dict(mem={k: torch.zeros_like(v) for k, v in engine.mem.items()}, prev_scene=None, mem_valid=False)
                        for _ in range(self.streams)]
         self._tokens = None         # (B, N, S, 256): stream b's camera stage writes slice b, the decoder pass reads all of it
+        self._images = None         # (B * N, 3, H, W): stream b stages its images in rows [b * N, (b + 1) * N) (camera_batch)
         for b in range(self.streams):
+            engine._ins.pop(self._key(b), None)      # staged inputs of an earlier runner whose id() this one has: slices of ITS buffer
             engine.token_slices[self._key(b)] = functools.partial(self._token_slice, b)
+            if self.camera_batch:
+                engine.image_slices[self._key(b)] = functools.partial(self._image_slice, b)
+            else:
+                engine.image_slices.pop(self._key(b), None)
 
     def _key(self, b):
         return ("stream", id(self), b)
@@ -66,6 +106,18 @@ class StreamBatch:
         if t is None or tuple(t.shape) != (self.streams, N, S, 256) or t.dtype != dtype:
             t = self._tokens = torch.empty((self.streams, N, S, 256), dtype=dtype, device=self.engine.dev)
         return t[b]
+
+    def _pass_tokens(self, b0, b1, n, S, dtype):
+        """The token buffer of the camera pass over streams [b0, b1): their slices of the one allocation, as (images, S, 256)."""
+        N = n // (b1 - b0)
+        self._token_slice(b0, N, S, dtype)
+        return self._tokens[b0:b1].view(n, S, 256)
+
+    def _image_slice(self, b, shape):
+        N, t = shape[0], self._images
+        if t is None or tuple(t.shape) != (self.streams * N,) + tuple(shape[1:]):
+            t = self._images = torch.empty((self.streams * N,) + tuple(shape[1:]), dtype=torch.float32, device=self.engine.dev)
+        return t[b * N:(b + 1) * N]
 
     @contextlib.contextmanager
     def _stream(self, b):
@@ -89,11 +141,30 @@ class StreamBatch:
         """Stream b's streaming memory (the dict of Far3DEngine.mem)."""
         return self._state[b]["mem"]
 
+    def _camera_streams(self, dds, pad_hw):
+        """The camera stage of all streams in as few passes as the kernels' extents allow -> the B per-stream `st` dicts."""
+        e, B = self.engine, self.streams
+        img = dds[0]["img"]
+        N = img.shape[0]
+        if any(tuple(dd["img"].shape) != tuple(img.shape) for dd in dds):
+            raise ValueError("forward_frames: every stream's frame must have the same cameras and image size")
+        if self._images is None or any(dd["img"].data_ptr() != self._images[b * N].data_ptr() for b, dd in enumerate(dds)):
+            raise RuntimeError("StreamBatch: a stream's staged images are not its slice of the joint image buffer")
+        self.camera_chunks = stream_chunks(B, N, e.camera_image_span(img.shape[2], img.shape[3]), max_streams=self.max_camera_streams)
+        sts, b0 = [], 0
+        for nb in self.camera_chunks:
+            b1 = b0 + nb
+            key = ("streams_cam", id(self), b0, b1)
+            e.token_slices[key] = functools.partial(self._pass_tokens, b0, b1)
+            sts += e.camera_stage_streams(dds[b0:b1], pad_hw, key, self._images[b0 * N:b1 * N])
+            b0 = b1
+        return sts
+
     @torch.no_grad()
     def forward_frames(self, datas, img_metas_list):
         """One frame per stream: datas[b] / img_metas_list[b] as Far3DEngine.forward_frame takes them (same image size and camera count
         in every stream).  Returns a list of B output dicts with forward_frame's keys.  Outputs live in buffers of the stream's own
-        set that its next frame overwrites: clone what must outlive it."""
+        set, or of the batch, that the next call overwrites: clone what must outlive it."""
         e, B = self.engine, self.streams
         if len(datas) != B or len(img_metas_list) != B:
             raise ValueError("forward_frames: one frame per stream (%d), got %d / %d" % (B, len(datas), len(img_metas_list)))
@@ -105,25 +176,34 @@ class StreamBatch:
             raise ValueError("forward_frames: every stream's frame must have the same padded size")
         cfg = e.cfg
         with ops.use_tile_tables(e.bf16_tile_table()):
-            sts, hss = [], []
+            sts, hss, dds = [], [], []
+            if self.camera_batch:
+                for b in range(B):
+                    with self._stream(b):
+                        dds.append(e._stage_inputs(datas[b]))
+                sts = self._camera_streams(dds, pad_hw)
             for b in range(B):
                 with self._stream(b):
-                    dd = e._stage_inputs(datas[b])
-                    st = e._camera_part(dd, pad_hw)
+                    if not self.camera_batch:
+                        dds.append(e._stage_inputs(datas[b]))
+                        sts.append(e._camera_part(dds[b], pad_hw))
+                    dd, st = dds[b], sts[b]
                     M = e.static_adaptive_rows(dd["img"].shape[0])
                     hss.append(e._head_prepare(st["tokens"], st["ref2d"], st["ctx"], M, dd, img_metas_list[b], st["m_dev"]))
-                    sts.append(st)
             pick = lambda name: [getattr(hs, name) for hs in hss]
             outs_dec = e.decoder_streams(pick("X2"), pick("x0"), pick("qpos"), pick("tokens"), pick("ref"), sts[0]["hw"], sts[0]["starts"],
                                          pick("lidar2img"), pad_hw, hss[0].A)
-            res = []
-            for b, (st, hs) in enumerate(zip(sts, hss)):
-                with self._stream(b):
-                    # the heads read a stream's layers as ONE (layers * A, E) block: the stream's rows of the pass, gathered
-                    od = e._buf(("outs_dec",), (len(e.layers), hs.A, cfg["embed_dims"]), torch.float32)
-                    od.copy_(outs_dec[b])
-                    outs = e._head_finish(hs, od)
-                    outs.update(fpn=st["raw"], depth_logit=st["depth_logit"], bbox2d=st["box2d"][:hs.M], bbox2d_scores=st["score2d"][:hs.M],
-                                sel_idx=st["sel_idx"], sel_cnt=st["sel_cnt"], proposal_overflow=st["overflow"])
-                    res.append(outs)
+            if self.head_batch:
+                res = e._head_finish_streams(hss, outs_dec, self._stream)
+            else:
+                res = []
+                for b, hs in enumerate(hss):
+                    with self._stream(b):
+                        # the heads read a stream's layers as ONE (layers * A, E) block: the stream's rows of the pass, gathered
+                        od = e._buf(("outs_dec",), (len(e.layers), hs.A, cfg["embed_dims"]), torch.float32)
+                        od.copy_(outs_dec[b])
+                        res.append(e._head_finish(hs, od))
+            for st, hs, outs in zip(sts, hss, res):
+                outs.update(fpn=st["raw"], depth_logit=st["depth_logit"], bbox2d=st["box2d"][:hs.M], bbox2d_scores=st["score2d"][:hs.M],
+                            sel_idx=st["sel_idx"], sel_cnt=st["sel_cnt"], proposal_overflow=st["overflow"])
         return res

@@ -727,6 +727,22 @@ int far3d_decode_topk_mem(const float* cls_last, const float* box_last, int A, i
                           const float* post_center_range, float* boxes, float* scores, int64_t* labels, unsigned char* keep,
                           void* workspace, long workspace_bytes, const float* mem_scores, int mem_n, int mem_K,
                           int64_t* mem_idx_out, void* stream);
+/* far3d_decode_topk_mem for B >= 1 scene streams in ONE launch of 2 * B workgroups: the same kernel with the stream as a second grid
+ * index (B <= 65535).  Every pointer names stream 0's operand; stream b's lies b * batch_strides[i] ELEMENTS of that operand behind it
+ * (64-bit), batch_strides = 8 longs on the HOST in the order cls_last, box_last, boxes, scores, labels, keep, mem_scores, mem_idx_out.
+ * For B > 1 a stride may not be below one stream's extent of its operand (A*num_classes, A*code_size, K*(code_size-1), K, K, K,
+ * mem_n, mem_K): two streams never share an address.  post_center_range and all sizes are shared.  Stream b's boxes / scores /
+ * labels / keep / mem_idx_out are bit for bit those of far3d_decode_topk_mem on stream b's operands and do not depend on B (same
+ * instantiations, chosen by A*num_classes <= 4096 / 16384 / 40960; same tie rule).
+ * Shapes outside the fused launch (A*num_classes > 40960 or mem_n > 4096): far3d_decode_topk_mem is issued per stream, stream b with
+ * the workspace slice [b * workspace_bytes, (b+1) * workspace_bytes) -- `workspace` then holds B * workspace_bytes bytes of 8-byte
+ * aligned DEVICE memory, workspace_bytes >= FAR3D_DECODE_WS_BYTES(A*num_classes, K) and a multiple of 8 (NULL / 0 otherwise).
+ * A bad argument (a null pointer, B < 1, a stride below the extent, any size rule of the one-stream entry) returns FAR3D_ERR_ARG with
+ * far3d_last_error() naming the argument, and nothing is launched for any stream. */
+int far3d_decode_topk_mem_streams(const float* cls_last, const float* box_last, int B, int A, int num_classes, int code_size, int K,
+                                  const float* post_center_range, float* boxes, float* scores, int64_t* labels, unsigned char* keep,
+                                  void* workspace, long workspace_bytes, const float* mem_scores, int mem_n, int mem_K,
+                                  int64_t* mem_idx_out, const long* batch_strides, void* stream);
 
 /* Per-frame camera calibration in one launch: img2lidar (N,4,4) = inverse(lidar2img) (ref models/dense_heads/farhead.py:798;
  * Gauss-Jordan with partial pivoting in f64) and c14 (N,14) = [fx/1e3, fy/1e3, extrinsics[:3,:4]] (ref farhead.py:553-556).
