@@ -143,6 +143,11 @@ struct AggParams {
 // block scan), and the gather loop is reduced to: broadcast record read, 4 coalesced row loads, 16 FMAs -- NB samples in
 // flight per wave.  Softmax uses the hardware exp2 path and incremental (camera, logit) indices.
 // ------------------------------------------------------------------------------------------
+// dynamic LDS of aggregate_v3_kernel: its carve-up (w_s, stat_s, scan_s, rec_s below), in bytes
+static inline size_t agg3_lds_bytes(int N, int P, int L) {
+  const int NLP = N * P * L;
+  return (size_t)(NLP * 8 > 1024 ? NLP * 8 : 1024) * 4 + 64 * 4 + 16 * 4 + (size_t)NLP * 32;
+}
 template <typename TV, int NB, int RP = 0>   // RP: bf16 row-pair gather (16-byte loads, both bilinear columns per instruction)
 __global__ __launch_bounds__(256) void aggregate_v3_kernel(const TV* __restrict__ feat, const float* __restrict__ ref,
                                                            const float* __restrict__ offs, const float* __restrict__ l2i,
@@ -615,6 +620,38 @@ extern "C" int far3d_prof_set_agg_timestamps(long long* buf) {
     l2i += (b) * prm.N * 16;                                                                                                      \
     out = reinterpret_cast<char*>(out) + (b) * prm.A * 256 * (prm.out_dt == FAR3D_DT_F32 ? 4 : 2);                                \
   } while (0)
+// The ends of the two-wave kernels (7, 8, the gather half of variant 13), one definition each.  They are function-like macros with every
+// name passed in, not functions: the text reaches the compiler as if written out in the kernel, so the kernels' machine code is what it
+// was with three copies (profiles/agg_host/README.md).  Thread t owns channels c = 2t, 2t + 1 of output row a.
+//  * AGG_ZERO_ROW2: the row of a slot without a query (perm entry ~a, far3d_agg_order): zeros, no work.
+//  * AGG_STORE_ROW2: the finished pair (r0, r1) in the output's type.
+//  * AGG_WAVE_PARTIALS: a wave's 256 partial sums into `red` ahead of the cross-wave barrier; on bf16 rows a load fetched two token rows,
+//    so the lane halves are added first.  HALVES is how the kernel adds them: kernel 7 with a shuffle, kernel 8 with its permlane swap.
+#define AGG_STORE_ROW2(out, out_dt, a, c, r0, r1)                                                                                         \
+  do {                                                                                                                                    \
+    if ((out_dt) == FAR3D_DT_F32) *reinterpret_cast<float2*>(reinterpret_cast<float*>(out) + (long)(a) * 256 + (c)) = make_float2(r0, r1); \
+    else *reinterpret_cast<unsigned*>(reinterpret_cast<bf16_t*>(out) + (long)(a) * 256 + (c)) = pack_bf16x2(r0, r1);                        \
+  } while (0)
+#define AGG_ZERO_ROW2(out, out_dt, a, c) AGG_STORE_ROW2(out, out_dt, a, c, 0.f, 0.f)
+#define AGG_HALVES_SHFL(v) v += __shfl_xor(v, 32)
+#define AGG_HALVES_SWAP(v) do { float x, y; agg_swap32(v, x, y); v = x + y; } while (0)
+#define AGG_WAVE_PARTIALS(TV, red, acc, lane, HALVES)                                                                                     \
+  do {                                                                                                                                    \
+    if constexpr (sizeof(TV) == 2) {                                                                                                      \
+      _Pragma("unroll") for (int k = 0; k < 8; ++k) HALVES(acc[k]);                                                                       \
+      if (lane < 32) {                                                                                                                    \
+        *reinterpret_cast<float4*>(red + lane * 8) = make_float4(acc[0], acc[1], acc[2], acc[3]);                                         \
+        *reinterpret_cast<float4*>(red + lane * 8 + 4) = make_float4(acc[4], acc[5], acc[6], acc[7]);                                     \
+      }                                                                                                                                   \
+    } else {                                                                                                                              \
+      *reinterpret_cast<float4*>(red + lane * 4) = make_float4(acc[0], acc[1], acc[2], acc[3]);                                           \
+    }                                                                                                                                     \
+  } while (0)
+// dynamic LDS of aggregate_v7_kernel at CAPW = AGG7_CAPW: its carve-up (w_s .. wt_all below), in bytes
+static inline size_t agg7_lds_bytes(int N, int P, int L) {
+  const int NP = N * P;
+  return (size_t)NP * L * 32 + (size_t)((NP + 1) & ~1) * 8 + AGG4_MAX_N * 16 + 32 * 4 + AGG4_MAX_N * 4 + (size_t)2 * AGG7_CAPW * 36;
+}
 template <typename TV, int PT, int OPT = 0, int CAPW = AGG7_CAPW, bool BATCHED = false>
 __global__ __launch_bounds__(128) void aggregate_v7_kernel(const TV* __restrict__ feat, const float* __restrict__ ref,
                                                            const float* __restrict__ offs, const float* __restrict__ l2i,
@@ -668,8 +705,7 @@ __global__ __launch_bounds__(128) void aggregate_v7_kernel(const TV* __restrict_
   if (a < 0) {      // ~a: row a holds no query (far3d_agg_order marks the hole of the fixed-capacity proposal mode): zero row, no work
     a = ~a;
     const int c = t * 2;
-    if (prm.out_dt == FAR3D_DT_F32) *reinterpret_cast<float2*>(reinterpret_cast<float*>(out) + (long)a * 256 + c) = make_float2(0.f, 0.f);
-    else *reinterpret_cast<unsigned*>(reinterpret_cast<bf16_t*>(out) + (long)a * 256 + c) = 0u;
+    AGG_ZERO_ROW2(out, prm.out_dt, a, c);
     return;
   }
   // query-dependent loads, all issued together: reference point, this lane's key-point offset, the query part of the logits
@@ -926,16 +962,7 @@ __global__ __launch_bounds__(128) void aggregate_v7_kernel(const TV* __restrict_
 
   // ---- cross-wave sum: partial sums go into the wave's own (now dead) list region; 1/S[g] applied once here
   float* red = wt_s;                       // 256 floats: CAPW * 8 >= 256
-  if constexpr (sizeof(TV) == 2) {
-#pragma unroll
-    for (int k = 0; k < 8; ++k) acc[k] += __shfl_xor(acc[k], 32);      // two token rows per load: add the halves
-    if (lane < 32) {
-      *reinterpret_cast<float4*>(red + lane * 8) = make_float4(acc[0], acc[1], acc[2], acc[3]);
-      *reinterpret_cast<float4*>(red + lane * 8 + 4) = make_float4(acc[4], acc[5], acc[6], acc[7]);
-    }
-  } else {
-    *reinterpret_cast<float4*>(red + lane * 4) = make_float4(acc[0], acc[1], acc[2], acc[3]);
-  }
+  AGG_WAVE_PARTIALS(TV, red, acc, lane, AGG_HALVES_SHFL);
   __syncthreads();                                                                        // B3
   AGG_TS(6);
   {
@@ -943,8 +970,7 @@ __global__ __launch_bounds__(128) void aggregate_v7_kernel(const TV* __restrict_
     const float inv = 1.f / (stat_s[16 + g] + stat_s[24 + g]);
     const float2 p0 = *reinterpret_cast<const float2*>(wt_all + c), p1 = *reinterpret_cast<const float2*>(wt_all + CAPW * 8 + c);
     const float r0 = (p0.x + p1.x) * inv, r1 = (p0.y + p1.y) * inv;
-    if (prm.out_dt == FAR3D_DT_F32) *reinterpret_cast<float2*>(reinterpret_cast<float*>(out) + (long)a * 256 + c) = make_float2(r0, r1);
-    else *reinterpret_cast<unsigned*>(reinterpret_cast<bf16_t*>(out) + (long)a * 256 + c) = pack_bf16x2(r0, r1);
+    AGG_STORE_ROW2(out, prm.out_dt, a, c, r0, r1);
   }
 }
 
@@ -1160,8 +1186,7 @@ __global__ __launch_bounds__(128, 4) void aggregate_v8_kernel(const TV* __restri
   auto hole_row = [&]() __attribute__((always_inline)) {      // ~a: row a holds no query (far3d_agg_order): zero row, no work
     a = ~a;
     const int c = t * 2;
-    if (prm.out_dt == FAR3D_DT_F32) *reinterpret_cast<float2*>(reinterpret_cast<float*>(out) + (long)a * 256 + c) = make_float2(0.f, 0.f);
-    else *reinterpret_cast<unsigned*>(reinterpret_cast<bf16_t*>(out) + (long)a * 256 + c) = 0u;
+    AGG_ZERO_ROW2(out, prm.out_dt, a, c);
   };
   // (sorted mode tests for the hole BEHIND the front end's barrier: a test here would make the whole load burst wait for perm[e] --
   // the compiler sinks the loads below the branch -- and a hole slot's operands are finite rows like any other)
@@ -1654,16 +1679,7 @@ __global__ __launch_bounds__(128, 4) void aggregate_v8_kernel(const TV* __restri
 
   // ---- cross-wave sum: partial sums go into the wave's own (now dead) list region; 1/S[g] applied once here
   float* red = wt_s;                       // 256 floats: CAPT * 8 >= 256
-  if constexpr (sizeof(TV) == 2) {
-#pragma unroll
-    for (int k = 0; k < 8; ++k) { float x, y; agg_swap32(acc[k], x, y); acc[k] = x + y; }      // two token rows per load: add the halves
-    if (lane < 32) {
-      *reinterpret_cast<float4*>(red + lane * 8) = make_float4(acc[0], acc[1], acc[2], acc[3]);
-      *reinterpret_cast<float4*>(red + lane * 8 + 4) = make_float4(acc[4], acc[5], acc[6], acc[7]);
-    }
-  } else {
-    *reinterpret_cast<float4*>(red + lane * 4) = make_float4(acc[0], acc[1], acc[2], acc[3]);
-  }
+  AGG_WAVE_PARTIALS(TV, red, acc, lane, AGG_HALVES_SWAP);
   __builtin_amdgcn_s_setprio(0);
   __syncthreads();                                                                        // the second and last barrier
   AGG_TS(6);
@@ -1699,8 +1715,7 @@ __global__ __launch_bounds__(128, 4) void aggregate_v8_kernel(const TV* __restri
       }
     }
     const float r0 = s0 * inv, r1 = s1 * inv;
-    if (prm.out_dt == FAR3D_DT_F32) *reinterpret_cast<float2*>(reinterpret_cast<float*>(out) + (long)a * 256 + c) = make_float2(r0, r1);
-    else *reinterpret_cast<unsigned*>(reinterpret_cast<bf16_t*>(out) + (long)a * 256 + c) = pack_bf16x2(r0, r1);
+    AGG_STORE_ROW2(out, prm.out_dt, a, c, r0, r1);
   }
 }
 
@@ -1738,28 +1753,17 @@ __global__ __launch_bounds__(128, 4) void aggregate_gather_kernel(const TV* __re
   const int c = t * 2, g = c >> 5;
   if (a < 0) {
     a = ~a;
-    if (prm.out_dt == FAR3D_DT_F32) *reinterpret_cast<float2*>(reinterpret_cast<float*>(out) + (long)a * 256 + c) = make_float2(0.f, 0.f);
-    else *reinterpret_cast<unsigned*>(reinterpret_cast<bf16_t*>(out) + (long)a * 256 + c) = 0u;
+    AGG_ZERO_ROW2(out, prm.out_dt, a, c);
     return;
   }
   const float sden = gstat[g];
   float* red = red_s + wv * 256;
-  if constexpr (sizeof(TV) == 2) {
-#pragma unroll
-    for (int k = 0; k < 8; ++k) { float x, y; agg_swap32(acc[k], x, y); acc[k] = x + y; }
-    if (lane < 32) {
-      *reinterpret_cast<float4*>(red + lane * 8) = make_float4(acc[0], acc[1], acc[2], acc[3]);
-      *reinterpret_cast<float4*>(red + lane * 8 + 4) = make_float4(acc[4], acc[5], acc[6], acc[7]);
-    }
-  } else {
-    *reinterpret_cast<float4*>(red + lane * 4) = make_float4(acc[0], acc[1], acc[2], acc[3]);
-  }
+  AGG_WAVE_PARTIALS(TV, red, acc, lane, AGG_HALVES_SWAP);
   __syncthreads();
   const float inv = 1.f / sden;
   const float2 p0 = *reinterpret_cast<const float2*>(red_s + c), p1 = *reinterpret_cast<const float2*>(red_s + 256 + c);
   const float r0 = (p0.x + p1.x) * inv, r1 = (p0.y + p1.y) * inv;
-  if (prm.out_dt == FAR3D_DT_F32) *reinterpret_cast<float2*>(reinterpret_cast<float*>(out) + (long)a * 256 + c) = make_float2(r0, r1);
-  else *reinterpret_cast<unsigned*>(reinterpret_cast<bf16_t*>(out) + (long)a * 256 + c) = pack_bf16x2(r0, r1);
+  AGG_STORE_ROW2(out, prm.out_dt, a, c, r0, r1);
 }
 
 // far3d_agg_tables: the softmax factors of csrc/agg_tables.hpp for `layers` decoder layers, block = layer.
@@ -1774,6 +1778,97 @@ extern "C" int far3d_agg_tables(const float* Vc, float* tables, int layers, int 
   return FAR3D_OK;
 }
 
+// ------------------------------------------------------------------------------------------
+// Host side of the fused aggregation: far3d_aggregate_forward and far3d_aggregate_batched share ONE copy of the argument checks, the
+// AggParams fill, the "kernel 8 applies" rule and the dispatch over row type and point count; the dynamic-LDS sizes stand beside the
+// carve-ups they mirror (agg3_lds_bytes, agg7_lds_bytes, AGG8_LDS).  The checks are several functions that take the entry's name (as in
+// csrc/attn_core.hpp) because each entry runs them in an order of its own, and the order decides which message a call with two faults
+// gets: forward tests the pointers first and the output dtype last; batched the sizes, then B, returns on an empty batch, then the pointers.
+// ------------------------------------------------------------------------------------------
+static inline int agg_check_pointers(const char* who, const void* feat, const float* ref, const float* offsets, const float* lidar2img,
+                                     const float* U, const float* Vc, const float* cam_tables, const void* out, const int32_t* level_hw,
+                                     const int32_t* level_start, const float* pc_range) {
+  FAR3D_CHECK_ARG(feat && ref && offsets && lidar2img && U && (Vc || cam_tables) && out && level_hw && level_start && pc_range,
+                  "%s: null pointer argument", who);
+  return FAR3D_OK;
+}
+static inline int agg_check_shape(const char* who, int C, int G, int L, int N, int P, int feat_dtype) {
+  FAR3D_CHECK_ARG(C == 256 && G == 8, "%s: fused kernel is built for C=256,G=8 (got C=%d G=%d)", who, C, G);
+  FAR3D_CHECK_ARG(L >= 1 && L <= AGG_MAX_L, "%s: L=%d out of range [1,%d]", who, L, AGG_MAX_L);
+  FAR3D_CHECK_ARG(N >= 1 && N <= AGG4_MAX_N && P >= 1 && N * P <= 256 && N * P * L <= AGG_MAX_NLP,
+                  "%s: N=%d (<=%d), N*P=%d (<=256) or N*P*L=%d (<=%d) too large", who, N, AGG4_MAX_N, N * P, N * P * L, AGG_MAX_NLP);
+  FAR3D_CHECK_ARG(feat_dtype == FAR3D_DT_F32 || feat_dtype == FAR3D_DT_BF16, "%s: unsupported feature dtype %d", who, feat_dtype);
+  return FAR3D_OK;
+}
+static inline int agg_check_out_dtype(const char* who, int out_dt) {
+  FAR3D_CHECK_ARG(out_dt == FAR3D_DT_F32 || out_dt == FAR3D_DT_BF16, "%s: unsupported output dtype %d", who, out_dt);
+  return FAR3D_OK;
+}
+// `nsc`: the entry's name for the extent that has to fit 32 bits ("N*S*C", "N*S*C of one sample")
+static inline int agg_check_extent(const char* who, int A, int N, int S, int C, const char* nsc) {
+  FAR3D_CHECK_ARG(A >= 0 && S > 0 && (long)N * S * C < (1L << 31), "%s: bad sizes A=%d S=%d (%s must fit int32)", who, A, S, nsc);
+  return FAR3D_OK;
+}
+// Variant 0 runs kernel 8 (factored softmax) where this holds, else kernel 7: the one statement of the rule (ops.aggregate_kernel8_applies)
+static inline bool agg_kernel8_applies(const float* cam_tables, int N, int P, int L, int S, int C, size_t esz) {
+  return cam_tables && N <= 8 && P <= 16 && L <= AGG_MAX_L && (size_t)N * S * C * esz < (1ull << 32);
+}
+// The level table (checked against S), the kernel parameters, the stride / alignment check of U and the offsets.  The sibling-split
+// fields are left empty (variant 9 sets them).
+static inline int agg_fill_params(const char* who, AggParams& prm, int A, int N, int S, int G, int P, int L, const int32_t* level_hw,
+                                  const int32_t* level_start, const float* pc_range, float pad_h, float pad_w, const float* U, int ldU,
+                                  int ldOffs, int out_dt) {
+  prm.A = A; prm.N = N; prm.S = S; prm.P = P; prm.L = L;
+  for (int l = 0; l < AGG_MAX_L; ++l) {
+    prm.H[l] = l < L ? level_hw[2 * l] : 1;
+    prm.W[l] = l < L ? level_hw[2 * l + 1] : 1;
+    prm.start[l] = l < L ? level_start[l] : 0;
+    if (l < L)
+      FAR3D_CHECK_ARG(prm.H[l] > 0 && prm.W[l] > 0 && prm.start[l] >= 0 && prm.start[l] + prm.H[l] * prm.W[l] <= S,
+                      "%s: level %d (%dx%d @%d) exceeds S=%d", who, l, prm.H[l], prm.W[l], prm.start[l], S);
+  }
+  for (int d = 0; d < 3; ++d) { prm.pc_lo[d] = pc_range[d]; prm.pc_span[d] = pc_range[3 + d] - pc_range[d]; }
+  prm.pad_w = pad_w; prm.pad_h = pad_h;
+  prm.ipw = 1.f / pad_w; prm.iph = 1.f / pad_h;
+  for (int l = 0; l < AGG_MAX_L; ++l) { prm.Wf[l] = (float)prm.W[l]; prm.Hf[l] = (float)prm.H[l]; }
+  prm.q_per_xcd = cdiv(A, 8);
+  prm.split_part = nullptr; prm.split_tick = nullptr; prm.split_extra = 0;
+  prm.out_dt = out_dt;
+  prm.ldU = ldU > 0 ? ldU : L * P * G;
+  prm.ldO = ldOffs > 0 ? ldOffs : P * 3;
+  FAR3D_CHECK_ARG(prm.ldU >= L * P * G && prm.ldU % 4 == 0 && ((uintptr_t)U % 16) == 0 && prm.ldO >= P * 3,
+                  "%s: U rows must be 16-byte aligned (ldU=%d) and strides >= row length", who, prm.ldU);
+  return FAR3D_OK;
+}
+
+// What every launch of kernels 7 / 8 takes: grid, stream and the operands the two kernels have in common.
+struct AggLaunch {
+  dim3 grid; hipStream_t st; const void* feat; int feat_dtype; const float *ref, *offs, *l2i, *U; const int* perm; void* out;
+};
+// The row type TV in {float, bf16_t} and the point count PT in {13: the model's, unrolled; 0: any, read from AggParams} are chosen HERE,
+// once: `f` is a generic lambda that gets a value of type TV and std::integral_constant<int, PT>.  ANY_P = false: only PT = 13 exists
+// (variant 13, whose caller has checked P == 13).
+template <bool ANY_P = true, typename F>
+static inline void agg_for_row_and_points(int feat_dtype, int P, F f) {
+  auto rows = [&](auto pt) { if (feat_dtype == FAR3D_DT_F32) f(float(), pt); else f(bf16_t(), pt); };
+  if constexpr (ANY_P) { if (P != 13) return rows(std::integral_constant<int, 0>{}); }
+  rows(std::integral_constant<int, 13>{});
+}
+template <bool SPLIT, bool SORTED, int DEAL, int PHASE = 0, bool BATCHED = false>
+static inline void agg_launch_v8(const AggLaunch& k, const float* cam_tables, const AggParams& prm, const float4* qbase) {
+  agg_for_row_and_points<PHASE == 0>(k.feat_dtype, prm.P, [&](auto row, auto pt) {
+    using TV = decltype(row);
+    hipLaunchKernelGGL((aggregate_v8_kernel<TV, decltype(pt)::value, 1, 4, AGG8_CAPW, SPLIT, SORTED, DEAL, PHASE, BATCHED>), k.grid, dim3(128), AGG8_LDS, k.st, (const TV*)k.feat, k.ref, k.offs, k.l2i, k.U, cam_tables, k.perm, k.out, prm, qbase);
+  });
+}
+template <int OPT, bool BATCHED = false>
+static inline void agg_launch_v7(const AggLaunch& k, const float* Vc, const AggParams& prm) {
+  agg_for_row_and_points(k.feat_dtype, prm.P, [&](auto row, auto pt) {
+    using TV = decltype(row);
+    hipLaunchKernelGGL((aggregate_v7_kernel<TV, decltype(pt)::value, OPT, AGG7_CAPW, BATCHED>), k.grid, dim3(128), agg7_lds_bytes(prm.N, prm.P, prm.L), k.st, (const TV*)k.feat, k.ref, k.offs, k.l2i, k.U, Vc, k.perm, k.out, prm);
+  });
+}
+
 extern "C" int far3d_aggregate_forward(const void* feat, int feat_dtype, const float* ref,
                                        const float* offsets, const float* lidar2img, const float* U,
                                        const float* Vc, const float* cam_tables, const int32_t* perm, void* out, int out_dt, int A, int N,
@@ -1781,21 +1876,15 @@ extern "C" int far3d_aggregate_forward(const void* feat, int feat_dtype, const f
                                        const float* pc_range, float pad_h, float pad_w, int ldU, int ldOffs, int variant,
                                        float* split_partials, int32_t* split_tickets, int split_extra, const float* qbase,
                                        void* stream) {
-  FAR3D_CHECK_ARG(feat && ref && offsets && lidar2img && U && (Vc || cam_tables) && out && level_hw && level_start && pc_range,
-                  "far3d_aggregate_forward: null pointer argument");
-  FAR3D_CHECK_ARG(C == 256 && G == 8, "far3d_aggregate_forward: fused kernel is built for C=256,G=8 (got C=%d G=%d)", C, G);
-  FAR3D_CHECK_ARG(L >= 1 && L <= AGG_MAX_L, "far3d_aggregate_forward: L=%d out of range [1,%d]", L, AGG_MAX_L);
-  FAR3D_CHECK_ARG(N >= 1 && N <= AGG4_MAX_N && P >= 1 && N * P <= 256 && N * P * L <= AGG_MAX_NLP,
-                  "far3d_aggregate_forward: N=%d (<=%d), N*P=%d (<=256) or N*P*L=%d (<=%d) too large", N, AGG4_MAX_N, N * P, N * P * L, AGG_MAX_NLP);
-  FAR3D_CHECK_ARG(feat_dtype == FAR3D_DT_F32 || feat_dtype == FAR3D_DT_BF16,
-                  "far3d_aggregate_forward: unsupported feature dtype %d", feat_dtype);
-  FAR3D_CHECK_ARG(A >= 0 && S > 0 && (long)N * S * C < (1L << 31), "far3d_aggregate_forward: bad sizes A=%d S=%d (N*S*C must fit int32)", A, S);
+  const char* who = "far3d_aggregate_forward";
+  if (const int rc = agg_check_pointers(who, feat, ref, offsets, lidar2img, U, Vc, cam_tables, out, level_hw, level_start, pc_range)) return rc;
+  if (const int rc = agg_check_shape(who, C, G, L, N, P, feat_dtype)) return rc;
+  if (const int rc = agg_check_extent(who, A, N, S, C, "N*S*C")) return rc;
   FAR3D_CHECK_ARG(variant == 0 || variant == 3 || variant == 7 || variant == 8 || variant == 9 || variant == 11 || variant == 12 || variant == 13,
                   "far3d_aggregate_forward: unknown kernel variant %d (0 = default: 8 where it applies, else 7; 9 = 8 + sibling workgroups for heavy queries; 12 = 8 with the greedy dealing of round 4; 13 = 8 as TWO launches (list build, gather: A/B, sorted mode, workspace in split_partials / split_tickets); 3 = round-1 kernel, 11 = 7 + VALU reductions / packed FMAs)", variant);
   FAR3D_CHECK_ARG(variant != 9 || (perm && split_partials && split_tickets && split_extra > 0),
                   "far3d_aggregate_forward: variant 9 needs perm (A main + split_extra sibling entries from far3d_agg_order), split_partials, split_tickets and split_extra > 0");
-  const size_t esz = feat_dtype == FAR3D_DT_F32 ? 4 : 2;
-  const bool v8_ok = cam_tables && N <= 8 && P <= 16 && L <= AGG_MAX_L && (size_t)N * S * C * esz < (1ull << 32);
+  const bool v8_ok = agg_kernel8_applies(cam_tables, N, P, L, S, C, feat_dtype == FAR3D_DT_F32 ? 4 : 2);
   if (variant == 0) variant = v8_ok ? 8 : 7;
   FAR3D_CHECK_ARG(variant != 9 || v8_ok, "far3d_aggregate_forward: variant 9 needs what variant 8 needs (cam_tables, N <= 8, P <= 16)");
   FAR3D_CHECK_ARG((variant != 8 && variant != 12 && variant != 13) || v8_ok, "far3d_aggregate_forward: variant 8 needs cam_tables (far3d_agg_tables), N <= 8, P <= 16 and value maps < 4 GiB (N=%d P=%d)", N, P);
@@ -1808,99 +1897,24 @@ extern "C" int far3d_aggregate_forward(const void* feat, int feat_dtype, const f
                   variant, AGG8_WCAM / 2);
   if (A == 0) return FAR3D_OK;
   AggParams prm;
-  prm.A = A; prm.N = N; prm.S = S; prm.P = P; prm.L = L;
-  for (int l = 0; l < AGG_MAX_L; ++l) {
-    prm.H[l] = l < L ? level_hw[2 * l] : 1;
-    prm.W[l] = l < L ? level_hw[2 * l + 1] : 1;
-    prm.start[l] = l < L ? level_start[l] : 0;
-    if (l < L)
-      FAR3D_CHECK_ARG(prm.H[l] > 0 && prm.W[l] > 0 && prm.start[l] >= 0 && prm.start[l] + prm.H[l] * prm.W[l] <= S,
-                      "far3d_aggregate_forward: level %d (%dx%d @%d) exceeds S=%d", l, prm.H[l], prm.W[l], prm.start[l], S);
-  }
-  for (int d = 0; d < 3; ++d) { prm.pc_lo[d] = pc_range[d]; prm.pc_span[d] = pc_range[3 + d] - pc_range[d]; }
-  prm.pad_w = pad_w; prm.pad_h = pad_h;
-  prm.ipw = 1.f / pad_w; prm.iph = 1.f / pad_h;
-  for (int l = 0; l < AGG_MAX_L; ++l) { prm.Wf[l] = (float)prm.W[l]; prm.Hf[l] = (float)prm.H[l]; }
-  prm.q_per_xcd = cdiv(A, 8);
+  if (const int rc = agg_fill_params(who, prm, A, N, S, G, P, L, level_hw, level_start, pc_range, pad_h, pad_w, U, ldU, ldOffs, out_dt)) return rc;
+  if (const int rc = agg_check_out_dtype(who, out_dt)) return rc;
   prm.split_part = split_partials; prm.split_tick = split_tickets; prm.split_extra = variant == 9 ? split_extra : 0;
-  prm.out_dt = out_dt;
-  prm.ldU = ldU > 0 ? ldU : L * P * G;
-  prm.ldO = ldOffs > 0 ? ldOffs : P * 3;
-  FAR3D_CHECK_ARG(prm.ldU >= L * P * G && prm.ldU % 4 == 0 && ((uintptr_t)U % 16) == 0 && prm.ldO >= P * 3,
-                  "far3d_aggregate_forward: U rows must be 16-byte aligned (ldU=%d) and strides >= row length", prm.ldU);
-  FAR3D_CHECK_ARG(out_dt == FAR3D_DT_F32 || out_dt == FAR3D_DT_BF16, "far3d_aggregate_forward: unsupported output dtype %d", out_dt);
-  dim3 grid(8 * prm.q_per_xcd);
-  hipStream_t st = (hipStream_t)stream;
-  if (variant == 3) {     // workgroup-per-query kernel with per-sample row-pair gather (round 1)
-    const int nlp8 = N * P * L * 8 > 1024 ? N * P * L * 8 : 1024;
-    const size_t lds3 = (size_t)nlp8 * 4 + 64 * 4 + 64 + (size_t)N * P * L * 32;
-    if (feat_dtype == FAR3D_DT_F32)
-      hipLaunchKernelGGL((aggregate_v3_kernel<float, 2>), grid, dim3(256), lds3, st, (const float*)feat, ref, offsets, lidar2img, U, Vc, perm, out, prm);
-    else
-      hipLaunchKernelGGL((aggregate_v3_kernel<bf16_t, 2, 1>), grid, dim3(256), lds3, st, (const bf16_t*)feat, ref, offsets, lidar2img, U, Vc, perm, out, prm);
-  } else if (variant == 11) {     // v7 with DPP / permlane reductions, early matrix loads, packed FMAs; A/B
-    const int NP = N * P;
-    const size_t lds7 = (size_t)NP * L * 32 + (size_t)((NP + 1) & ~1) * 8 + AGG4_MAX_N * 16 + 32 * 4 + AGG4_MAX_N * 4 + (size_t)2 * AGG7_CAPW * 36;
-    if (feat_dtype == FAR3D_DT_F32) {
-      if (P == 13) hipLaunchKernelGGL((aggregate_v7_kernel<float, 13, 1>), grid, dim3(128), lds7, st, (const float*)feat, ref, offsets, lidar2img, U, Vc, perm, out, prm);
-      else hipLaunchKernelGGL((aggregate_v7_kernel<float, 0, 1>), grid, dim3(128), lds7, st, (const float*)feat, ref, offsets, lidar2img, U, Vc, perm, out, prm);
-    } else {
-      if (P == 13) hipLaunchKernelGGL((aggregate_v7_kernel<bf16_t, 13, 1>), grid, dim3(128), lds7, st, (const bf16_t*)feat, ref, offsets, lidar2img, U, Vc, perm, out, prm);
-      else hipLaunchKernelGGL((aggregate_v7_kernel<bf16_t, 0, 1>), grid, dim3(128), lds7, st, (const bf16_t*)feat, ref, offsets, lidar2img, U, Vc, perm, out, prm);
-    }
+  const AggLaunch k = {dim3(8 * prm.q_per_xcd + prm.split_extra), (hipStream_t)stream, feat, feat_dtype, ref, offsets, lidar2img, U, perm, out};
+  const float4* qb = reinterpret_cast<const float4*>(qbase);
+  if (variant == 11) agg_launch_v7<1>(k, Vc, prm);     // v7 with DPP / permlane reductions, early matrix loads, packed FMAs; A/B
+  else if (variant == 8 && qbase) agg_launch_v8<false, true, -1>(k, cam_tables, prm, qb);      // the default kernel in sorted mode: operands in launch order
+  else if (variant == 8) agg_launch_v8<false, false, -1>(k, cam_tables, prm, nullptr);      // factored softmax, specialised front ends, work-dealt items (default)
+  else if (variant == 12) agg_launch_v8<false, false, 0>(k, cam_tables, prm, nullptr);     // kernel 8 with round 4's greedy dealing (A/B of the round-6 contiguous split)
+  else if (variant == 9) agg_launch_v8<true, false, -1>(k, cam_tables, prm, nullptr);      // variant 8 + sibling workgroups (grid: + split_extra) for the queries far3d_agg_order marked as heavy
+  else if (variant == 7) agg_launch_v7<0>(k, Vc, prm);     // 2 waves per query, levels split by parity, softmax over all 7 cameras
+  else if (variant == 3) {     // workgroup-per-query kernel with per-sample row-pair gather (round 1)
+    if (feat_dtype == FAR3D_DT_F32) hipLaunchKernelGGL((aggregate_v3_kernel<float, 2>), k.grid, dim3(256), agg3_lds_bytes(N, P, L), k.st, (const float*)feat, ref, offsets, lidar2img, U, Vc, perm, out, prm);
+    else hipLaunchKernelGGL((aggregate_v3_kernel<bf16_t, 2, 1>), k.grid, dim3(256), agg3_lds_bytes(N, P, L), k.st, (const bf16_t*)feat, ref, offsets, lidar2img, U, Vc, perm, out, prm);
   } else if (variant == 13) {     // A/B: the sorted-mode kernel as two launches -- list build (global lists), then a pure gather
-    const float4* qb = reinterpret_cast<const float4*>(qbase);
-    if (feat_dtype == FAR3D_DT_F32) {
-      hipLaunchKernelGGL((aggregate_v8_kernel<float, 13, 1, 4, AGG8_CAPW, false, true, -1, 1>), grid, dim3(128), AGG8_LDS, st, (const float*)feat, ref, offsets, lidar2img, U, cam_tables, perm, out, prm, qb);
-      hipLaunchKernelGGL((aggregate_gather_kernel<float>), grid, dim3(128), 0, st, (const float*)feat, perm, out, prm);
-    } else {
-      hipLaunchKernelGGL((aggregate_v8_kernel<bf16_t, 13, 1, 4, AGG8_CAPW, false, true, -1, 1>), grid, dim3(128), AGG8_LDS, st, (const bf16_t*)feat, ref, offsets, lidar2img, U, cam_tables, perm, out, prm, qb);
-      hipLaunchKernelGGL((aggregate_gather_kernel<bf16_t>), grid, dim3(128), 0, st, (const bf16_t*)feat, perm, out, prm);
-    }
-  } else if (variant == 8 && qbase) {      // the default kernel in sorted mode: operands in launch order
-    const float4* qb = reinterpret_cast<const float4*>(qbase);
-    if (feat_dtype == FAR3D_DT_F32) {
-      if (P == 13) hipLaunchKernelGGL((aggregate_v8_kernel<float, 13, 1, 4, AGG8_CAPW, false, true>), grid, dim3(128), AGG8_LDS, st, (const float*)feat, ref, offsets, lidar2img, U, cam_tables, perm, out, prm, qb);
-      else hipLaunchKernelGGL((aggregate_v8_kernel<float, 0, 1, 4, AGG8_CAPW, false, true>), grid, dim3(128), AGG8_LDS, st, (const float*)feat, ref, offsets, lidar2img, U, cam_tables, perm, out, prm, qb);
-    } else {
-      if (P == 13) hipLaunchKernelGGL((aggregate_v8_kernel<bf16_t, 13, 1, 4, AGG8_CAPW, false, true>), grid, dim3(128), AGG8_LDS, st, (const bf16_t*)feat, ref, offsets, lidar2img, U, cam_tables, perm, out, prm, qb);
-      else hipLaunchKernelGGL((aggregate_v8_kernel<bf16_t, 0, 1, 4, AGG8_CAPW, false, true>), grid, dim3(128), AGG8_LDS, st, (const bf16_t*)feat, ref, offsets, lidar2img, U, cam_tables, perm, out, prm, qb);
-    }
-  } else if (variant == 8) {      // factored softmax, specialised front ends, work-dealt items (default)
-    if (feat_dtype == FAR3D_DT_F32) {
-      if (P == 13) hipLaunchKernelGGL((aggregate_v8_kernel<float, 13>), grid, dim3(128), AGG8_LDS, st, (const float*)feat, ref, offsets, lidar2img, U, cam_tables, perm, out, prm, (const float4*)nullptr);
-      else hipLaunchKernelGGL((aggregate_v8_kernel<float, 0>), grid, dim3(128), AGG8_LDS, st, (const float*)feat, ref, offsets, lidar2img, U, cam_tables, perm, out, prm, (const float4*)nullptr);
-    } else {
-      if (P == 13) hipLaunchKernelGGL((aggregate_v8_kernel<bf16_t, 13>), grid, dim3(128), AGG8_LDS, st, (const bf16_t*)feat, ref, offsets, lidar2img, U, cam_tables, perm, out, prm, (const float4*)nullptr);
-      else hipLaunchKernelGGL((aggregate_v8_kernel<bf16_t, 0>), grid, dim3(128), AGG8_LDS, st, (const bf16_t*)feat, ref, offsets, lidar2img, U, cam_tables, perm, out, prm, (const float4*)nullptr);
-    }
-  } else if (variant == 12) {     // kernel 8 with round 4's greedy dealing (A/B of the round-6 contiguous split)
-    if (feat_dtype == FAR3D_DT_F32) {
-      if (P == 13) hipLaunchKernelGGL((aggregate_v8_kernel<float, 13, 1, 4, AGG8_CAPW, false, false, 0>), grid, dim3(128), AGG8_LDS, st, (const float*)feat, ref, offsets, lidar2img, U, cam_tables, perm, out, prm, (const float4*)nullptr);
-      else hipLaunchKernelGGL((aggregate_v8_kernel<float, 0, 1, 4, AGG8_CAPW, false, false, 0>), grid, dim3(128), AGG8_LDS, st, (const float*)feat, ref, offsets, lidar2img, U, cam_tables, perm, out, prm, (const float4*)nullptr);
-    } else {
-      if (P == 13) hipLaunchKernelGGL((aggregate_v8_kernel<bf16_t, 13, 1, 4, AGG8_CAPW, false, false, 0>), grid, dim3(128), AGG8_LDS, st, (const bf16_t*)feat, ref, offsets, lidar2img, U, cam_tables, perm, out, prm, (const float4*)nullptr);
-      else hipLaunchKernelGGL((aggregate_v8_kernel<bf16_t, 0, 1, 4, AGG8_CAPW, false, false, 0>), grid, dim3(128), AGG8_LDS, st, (const bf16_t*)feat, ref, offsets, lidar2img, U, cam_tables, perm, out, prm, (const float4*)nullptr);
-    }
-  } else if (variant == 9) {      // variant 8 + sibling workgroups for the queries far3d_agg_order marked as heavy
-    const dim3 grid9(8 * prm.q_per_xcd + split_extra);
-    if (feat_dtype == FAR3D_DT_F32) {
-      if (P == 13) hipLaunchKernelGGL((aggregate_v8_kernel<float, 13, 1, 4, AGG8_CAPW, true>), grid9, dim3(128), AGG8_LDS, st, (const float*)feat, ref, offsets, lidar2img, U, cam_tables, perm, out, prm, (const float4*)nullptr);
-      else hipLaunchKernelGGL((aggregate_v8_kernel<float, 0, 1, 4, AGG8_CAPW, true>), grid9, dim3(128), AGG8_LDS, st, (const float*)feat, ref, offsets, lidar2img, U, cam_tables, perm, out, prm, (const float4*)nullptr);
-    } else {
-      if (P == 13) hipLaunchKernelGGL((aggregate_v8_kernel<bf16_t, 13, 1, 4, AGG8_CAPW, true>), grid9, dim3(128), AGG8_LDS, st, (const bf16_t*)feat, ref, offsets, lidar2img, U, cam_tables, perm, out, prm, (const float4*)nullptr);
-      else hipLaunchKernelGGL((aggregate_v8_kernel<bf16_t, 0, 1, 4, AGG8_CAPW, true>), grid9, dim3(128), AGG8_LDS, st, (const bf16_t*)feat, ref, offsets, lidar2img, U, cam_tables, perm, out, prm, (const float4*)nullptr);
-    }
-  } else if (variant == 7) {     // 2 waves per query, levels split by parity, softmax over all 7 cameras
-    const int NP = N * P;
-    const size_t lds7 = (size_t)NP * L * 32 + (size_t)((NP + 1) & ~1) * 8 + AGG4_MAX_N * 16 + 32 * 4 + AGG4_MAX_N * 4 + (size_t)2 * AGG7_CAPW * 36;
-    if (feat_dtype == FAR3D_DT_F32) {
-      if (P == 13) hipLaunchKernelGGL((aggregate_v7_kernel<float, 13>), grid, dim3(128), lds7, st, (const float*)feat, ref, offsets, lidar2img, U, Vc, perm, out, prm);
-      else hipLaunchKernelGGL((aggregate_v7_kernel<float, 0>), grid, dim3(128), lds7, st, (const float*)feat, ref, offsets, lidar2img, U, Vc, perm, out, prm);
-    } else {
-      if (P == 13) hipLaunchKernelGGL((aggregate_v7_kernel<bf16_t, 13>), grid, dim3(128), lds7, st, (const bf16_t*)feat, ref, offsets, lidar2img, U, Vc, perm, out, prm);
-      else hipLaunchKernelGGL((aggregate_v7_kernel<bf16_t, 0>), grid, dim3(128), lds7, st, (const bf16_t*)feat, ref, offsets, lidar2img, U, Vc, perm, out, prm);
-    }
+    agg_launch_v8<false, true, -1, 1>(k, cam_tables, prm, qb);
+    if (feat_dtype == FAR3D_DT_F32) hipLaunchKernelGGL((aggregate_gather_kernel<float>), k.grid, dim3(128), 0, k.st, (const float*)feat, perm, out, prm);
+    else hipLaunchKernelGGL((aggregate_gather_kernel<bf16_t>), k.grid, dim3(128), 0, k.st, (const bf16_t*)feat, perm, out, prm);
   }
   FAR3D_CHECK_LAUNCH("far3d_aggregate_forward");
   return FAR3D_OK;
@@ -1913,66 +1927,22 @@ extern "C" int far3d_aggregate_batched(const void* feat, int feat_dtype, const f
                                        void* out, int out_dt, int B, int A, int N, int S, int C, int G, int P, int L,
                                        const int32_t* level_hw, const int32_t* level_start, const float* pc_range,
                                        float pad_h, float pad_w, int ldU, int ldOffs, void* stream) {
-  FAR3D_CHECK_ARG(C == 256 && G == 8, "far3d_aggregate_batched: fused kernel is built for C=256,G=8 (got C=%d G=%d)", C, G);
-  FAR3D_CHECK_ARG(L >= 1 && L <= AGG_MAX_L, "far3d_aggregate_batched: L=%d out of range [1,%d]", L, AGG_MAX_L);
-  FAR3D_CHECK_ARG(N >= 1 && N <= AGG4_MAX_N && P >= 1 && N * P <= 256 && N * P * L <= AGG_MAX_NLP,
-                  "far3d_aggregate_batched: N=%d (<=%d), N*P=%d (<=256) or N*P*L=%d (<=%d) too large", N, AGG4_MAX_N, N * P, N * P * L, AGG_MAX_NLP);
-  FAR3D_CHECK_ARG(feat_dtype == FAR3D_DT_F32 || feat_dtype == FAR3D_DT_BF16,
-                  "far3d_aggregate_batched: unsupported feature dtype %d", feat_dtype);
-  FAR3D_CHECK_ARG(out_dt == FAR3D_DT_F32 || out_dt == FAR3D_DT_BF16, "far3d_aggregate_batched: unsupported output dtype %d", out_dt);
+  const char* who = "far3d_aggregate_batched";
+  if (const int rc = agg_check_shape(who, C, G, L, N, P, feat_dtype)) return rc;
+  if (const int rc = agg_check_out_dtype(who, out_dt)) return rc;
   FAR3D_CHECK_ARG(B >= 0 && B <= 65535, "far3d_aggregate_batched: B=%d out of range [0,65535] (the sample is the grid's y index)", B);
-  FAR3D_CHECK_ARG(A >= 0 && S > 0 && (long)N * S * C < (1L << 31),
-                  "far3d_aggregate_batched: bad sizes A=%d S=%d (N*S*C of one sample must fit int32)", A, S);
+  if (const int rc = agg_check_extent(who, A, N, S, C, "N*S*C of one sample")) return rc;
   if (B == 0 || A == 0) return FAR3D_OK;
-  FAR3D_CHECK_ARG(feat && ref && offsets && lidar2img && U && (Vc || cam_tables) && out && level_hw && level_start && pc_range,
-                  "far3d_aggregate_batched: null pointer argument");
-  const size_t esz = feat_dtype == FAR3D_DT_F32 ? 4 : 2;
-  const bool v8 = cam_tables && N <= 8 && P <= 16 && (size_t)N * S * C * esz < (1ull << 32);     // far3d_aggregate_forward's variant 0
+  if (const int rc = agg_check_pointers(who, feat, ref, offsets, lidar2img, U, Vc, cam_tables, out, level_hw, level_start, pc_range)) return rc;
+  const bool v8 = agg_kernel8_applies(cam_tables, N, P, L, S, C, feat_dtype == FAR3D_DT_F32 ? 4 : 2);     // far3d_aggregate_forward's variant 0
   FAR3D_CHECK_ARG(v8 || Vc, "far3d_aggregate_batched: kernel 7 (no cam_tables, N=%d > 8, P=%d > 16 or a sample's value maps >= 4 GiB) needs Vc", N, P);
   AggParams prm;
-  prm.A = A; prm.N = N; prm.S = S; prm.P = P; prm.L = L;
-  for (int l = 0; l < AGG_MAX_L; ++l) {
-    prm.H[l] = l < L ? level_hw[2 * l] : 1;
-    prm.W[l] = l < L ? level_hw[2 * l + 1] : 1;
-    prm.start[l] = l < L ? level_start[l] : 0;
-    if (l < L)
-      FAR3D_CHECK_ARG(prm.H[l] > 0 && prm.W[l] > 0 && prm.start[l] >= 0 && prm.start[l] + prm.H[l] * prm.W[l] <= S,
-                      "far3d_aggregate_batched: level %d (%dx%d @%d) exceeds S=%d", l, prm.H[l], prm.W[l], prm.start[l], S);
-  }
-  for (int d = 0; d < 3; ++d) { prm.pc_lo[d] = pc_range[d]; prm.pc_span[d] = pc_range[3 + d] - pc_range[d]; }
-  prm.pad_w = pad_w; prm.pad_h = pad_h;
-  prm.ipw = 1.f / pad_w; prm.iph = 1.f / pad_h;
-  for (int l = 0; l < AGG_MAX_L; ++l) { prm.Wf[l] = (float)prm.W[l]; prm.Hf[l] = (float)prm.H[l]; }
-  prm.q_per_xcd = cdiv(A, 8);
-  prm.split_part = nullptr; prm.split_tick = nullptr; prm.split_extra = 0;
-  prm.out_dt = out_dt;
-  prm.ldU = ldU > 0 ? ldU : L * P * G;
-  prm.ldO = ldOffs > 0 ? ldOffs : P * 3;
-  FAR3D_CHECK_ARG(prm.ldU >= L * P * G && prm.ldU % 4 == 0 && ((uintptr_t)U % 16) == 0 && prm.ldO >= P * 3,
-                  "far3d_aggregate_batched: U rows must be 16-byte aligned (ldU=%d) and strides >= row length", prm.ldU);
-  const dim3 grid(8 * prm.q_per_xcd, B);       // x: a multiple of 8 (blockIdx.x & 7 = XCD), y: the sample
-  hipStream_t st = (hipStream_t)stream;
-  const int* no_perm = nullptr;
-  if (v8) {
-    const float4* no_qbase = nullptr;
-    if (feat_dtype == FAR3D_DT_F32) {
-      if (P == 13) hipLaunchKernelGGL((aggregate_v8_kernel<float, 13, 1, 4, AGG8_CAPW, false, false, -1, 0, true>), grid, dim3(128), AGG8_LDS, st, (const float*)feat, ref, offsets, lidar2img, U, cam_tables, no_perm, out, prm, no_qbase);
-      else hipLaunchKernelGGL((aggregate_v8_kernel<float, 0, 1, 4, AGG8_CAPW, false, false, -1, 0, true>), grid, dim3(128), AGG8_LDS, st, (const float*)feat, ref, offsets, lidar2img, U, cam_tables, no_perm, out, prm, no_qbase);
-    } else {
-      if (P == 13) hipLaunchKernelGGL((aggregate_v8_kernel<bf16_t, 13, 1, 4, AGG8_CAPW, false, false, -1, 0, true>), grid, dim3(128), AGG8_LDS, st, (const bf16_t*)feat, ref, offsets, lidar2img, U, cam_tables, no_perm, out, prm, no_qbase);
-      else hipLaunchKernelGGL((aggregate_v8_kernel<bf16_t, 0, 1, 4, AGG8_CAPW, false, false, -1, 0, true>), grid, dim3(128), AGG8_LDS, st, (const bf16_t*)feat, ref, offsets, lidar2img, U, cam_tables, no_perm, out, prm, no_qbase);
-    }
-  } else {
-    const int NP = N * P;
-    const size_t lds7 = (size_t)NP * L * 32 + (size_t)((NP + 1) & ~1) * 8 + AGG4_MAX_N * 16 + 32 * 4 + AGG4_MAX_N * 4 + (size_t)2 * AGG7_CAPW * 36;
-    if (feat_dtype == FAR3D_DT_F32) {
-      if (P == 13) hipLaunchKernelGGL((aggregate_v7_kernel<float, 13, 0, AGG7_CAPW, true>), grid, dim3(128), lds7, st, (const float*)feat, ref, offsets, lidar2img, U, Vc, no_perm, out, prm);
-      else hipLaunchKernelGGL((aggregate_v7_kernel<float, 0, 0, AGG7_CAPW, true>), grid, dim3(128), lds7, st, (const float*)feat, ref, offsets, lidar2img, U, Vc, no_perm, out, prm);
-    } else {
-      if (P == 13) hipLaunchKernelGGL((aggregate_v7_kernel<bf16_t, 13, 0, AGG7_CAPW, true>), grid, dim3(128), lds7, st, (const bf16_t*)feat, ref, offsets, lidar2img, U, Vc, no_perm, out, prm);
-      else hipLaunchKernelGGL((aggregate_v7_kernel<bf16_t, 0, 0, AGG7_CAPW, true>), grid, dim3(128), lds7, st, (const bf16_t*)feat, ref, offsets, lidar2img, U, Vc, no_perm, out, prm);
-    }
-  }
+  if (const int rc = agg_fill_params(who, prm, A, N, S, G, P, L, level_hw, level_start, pc_range, pad_h, pad_w, U, ldU, ldOffs, out_dt)) return rc;
+  // grid x: a multiple of 8 (blockIdx.x & 7 = XCD), y: the sample; no perm
+  const AggLaunch k = {dim3(8 * prm.q_per_xcd, B), (hipStream_t)stream, feat, feat_dtype, ref, offsets, lidar2img, U, nullptr, out};
+  if (v8) agg_launch_v8<false, false, -1, 0, true>(k, cam_tables, prm, nullptr);
+  else agg_launch_v7<0, true>(k, Vc, prm);
   FAR3D_CHECK_LAUNCH("far3d_aggregate_batched");
   return FAR3D_OK;
 }
+

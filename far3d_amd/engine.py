@@ -817,6 +817,15 @@ class Far3DEngine:
         bf16 and every operand set of `packed` (the layers' RowChainLayer, the heads' RowChainBranches) could be built."""
         return self.fused_rows and self.prec["dec"] == torch.bfloat16 and all(p is not None for p in packed)
 
+    def _agg_sorted_gate(self, A, split, tokens):
+        """Does the decoder store the aggregation's operands in launch order (the default kernel's sorted mode)?  Only where the
+        library takes them (ops.aggregate_sorted_applies): any other configuration runs unsorted on the kernel variant 0 picks.
+        tokens: the (N, S, C) value maps."""
+        cfg = self.cfg
+        N, S, C = tokens.shape
+        return bool(self.agg_sorted and split is None and self.agg_variant in (0, 8) and A > 0 and
+                    ops.aggregate_sorted_applies(N, cfg["num_pts"], cfg["num_levels"], S, C, tokens.element_size()))
+
     def _decoder_setup(self, X2, x0, qpos, tokens, ref, hw, starts, lidar2img, pad_hw, A, hole, rows=None):
         """The decoder's per-frame working set (buffers, static operands, the aggregation's order and tables) as one object, and the
         query-independent launches.  rows None: the replicated run over all A queries; rows (a0, a1): a rank's share of the
@@ -862,7 +871,7 @@ class Far3DEngine:
                 sp = self._bufs[sk] = ops.AggSplit(A, self.agg_split_extra, self.dev)
         self.last_agg_split = ws.split = sp
         srt = None
-        if self.agg_sorted and sp is None and self.agg_variant in (0, 8) and A > 0 and ws.vc_all.shape[1] <= 8 and cfg["num_pts"] * cfg["num_levels"] <= 52:
+        if self._agg_sorted_gate(A, sp, tokens):
             srt = (self._buf(("agg_inv",), (A,), torch.int32), self._buf(("agg_qbase",), (A, 4), torch.float32))
             ws.inv, ws.qbase = srt
         res = ops.aggregation_order(ref, lidar2img, cfg["pc_range"], pad_hw, out=self._buf(("perm",), (A + (sp.extra if sp else 0),), torch.int32),
@@ -1023,7 +1032,7 @@ class Far3DEngine:
             VC[:, b].copy_(ops.cam_embed_chain(lidar2img[b], self.cam_chain))
             ops.linear(X2[b][:A], self.layers[0]["qkv"], out=QKV[b, :A, :3 * E], out_dtype=at)
         # the same table pass as far3d_agg_order's (agg_tables_body): the bits of the one-stream decoder's tables, where its kernel reads them
-        tabs = N <= 8 and cfg["num_pts"] <= 16
+        tabs = ops.aggregate_kernel8_applies(N, cfg["num_pts"], cfg["num_levels"], tok.shape[2], tok.shape[3], tok.element_size())
         if tabs:
             ops.agg_tables(VC.view(nL * B, N, nJ), out=TAB.view(nL * B, 2 + N, nJ))
         flat = lambda t: t.view(B * A, t.shape[2])

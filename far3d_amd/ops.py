@@ -155,6 +155,22 @@ class AggLists:
         self.counts = torch.zeros((slots * 2,), dtype=torch.int32, device=device)
 
 
+def _agg_host_operands(who, Vc, tables, kernel8, tab_shape, tab_name, level_hw, level_start, pc_range):
+    """What aggregate_forward and aggregate_batched hand the library besides tensors: the tables (agg_tables(Vc) when kernel 8 will
+    run and the caller passed none; checked against tab_shape) and the host arrays level_hw / level_start / pc_range.
+    Returns (tables, keep-alive, level_hw pointer, level_start pointer, pc_range pointer)."""
+    if tables is None and kernel8:
+        tables = agg_tables(Vc)
+    if tables is not None:
+        _chk(tables, "tables", torch.float32, len(tab_shape))
+        if tuple(tables.shape) != tab_shape:
+            raise ValueError("%s: tables must be %s = %s, got %s" % (who, tab_name, tab_shape, tuple(tables.shape)))
+    hw_keep, hw_p = _host_i32([list(x) for x in level_hw])
+    st_keep, st_p = _host_i32(list(level_start))
+    pc_keep, pc_p = _host_f32(list(pc_range))
+    return tables, (hw_keep, st_keep, pc_keep), hw_p, st_p, pc_p
+
+
 def aggregate_forward(feat, ref, offsets, lidar2img, U, Vc, level_hw, level_start, pc_range, pad_hw,
                       num_groups=8, out=None, perm=None, out_dtype=torch.float32, variant=0, tables=None, split=None, qbase=None, lists=None):
     """Fused perspective-aware aggregation for ONE sample (B=1).
@@ -200,8 +216,6 @@ def aggregate_forward(feat, ref, offsets, lidar2img, U, Vc, level_hw, level_star
         if perm is None or split.rows < A or variant not in (0, 9):
             raise ValueError("aggregate_forward: split needs the perm of aggregation_order(split=...), a workspace of >= A rows and variant 0 / 9")
         variant = 9
-    if tables is None and variant in (0, 8, 9, 12, 13) and A > 0 and N <= 8 and P <= 16:
-        tables = agg_tables(Vc)
     if qbase is not None:
         _chk(qbase, "qbase", torch.float32, 2)
         if perm is None or split is not None or variant not in (0, 8, 13) or tuple(qbase.shape) != (nperm, 4) or nperm != A:
@@ -211,13 +225,9 @@ def aggregate_forward(feat, ref, offsets, lidar2img, U, Vc, level_hw, level_star
     if variant == 13:
         if qbase is None or lists is None or lists.rows < A:
             raise ValueError("aggregate_forward: variant 13 (two-kernel split) needs the sorted mode's qbase and an AggLists workspace of >= A rows")
-    if tables is not None:
-        _chk(tables, "tables", torch.float32, 2)
-        if tuple(tables.shape) != (2 + N, L * P * G):
-            raise ValueError("aggregate_forward: tables must be (2+N, L*P*G) = %s, got %s" % ((2 + N, L * P * G), tuple(tables.shape)))
-    hw_keep, hw_p = _host_i32([list(x) for x in level_hw])
-    st_keep, st_p = _host_i32(list(level_start))
-    pc_keep, pc_p = _host_f32(list(pc_range))
+    k8 = variant in (0, 8, 9, 12, 13) and A > 0 and aggregate_kernel8_applies(N, P, L, S, C, feat.element_size())
+    tables, _keep, hw_p, st_p, pc_p = _agg_host_operands("aggregate_forward", Vc, tables, k8, (2 + N, L * P * G), "(2+N, L*P*G)",
+                                                         level_hw, level_start, pc_range)
     _lib.check(lib.far3d_aggregate_forward(_ptr(feat), _dt(feat), _ptr(ref), _ptr(offsets), _ptr(lidar2img),
                                            _ptr(U), _ptr(Vc), _ptr(tables) if tables is not None else None,
                                            _ptr(perm) if perm is not None else None, _ptr(out), _dt(out),
@@ -242,6 +252,28 @@ def aggregate_fused_supported(C, G, L, N, P):
     C, G, L, N, P = int(C), int(G), int(L), int(N), int(P)
     return (C == AGG_FUSED_C and G == AGG_FUSED_G and 1 <= L <= AGG_FUSED_MAX_L and 1 <= N <= AGG_FUSED_MAX_N and P >= 1 and
             N * P <= AGG_FUSED_MAX_NP and N * P * L <= AGG_FUSED_MAX_NLP)
+
+
+# Kernel 8 (the default kernel: factored softmax over agg_tables) and its sorted mode (csrc/sampling.hip: agg_kernel8_applies, AGG8_WCAM).
+AGG_K8_MAX_N, AGG_K8_MAX_P, AGG_SORTED_MAX_LP = 8, 16, 52
+
+
+def aggregate_kernel8_applies(N, P, L, S=None, C=256, esz=None):
+    """Does variant 0 of far3d_aggregate_forward / far3d_aggregate_batched run kernel 8 (and read the tables of agg_tables) for N
+    cameras, P points and L levels?  Otherwise it runs kernel 7, which reads Vc.  With the S tokens per camera and the element size
+    esz (bytes) of the value maps the rule includes that one sample's maps stay below 4 GiB (kernel 8 forms 32-bit byte offsets).
+    A host predicate: no device, no library.  The rule is the library's (agg_kernel8_applies, with the tables present), one for one."""
+    N, P, L = int(N), int(P), int(L)
+    ok = N <= AGG_K8_MAX_N and P <= AGG_K8_MAX_P and L <= AGG_FUSED_MAX_L
+    if S is not None and esz is not None:
+        ok = ok and N * int(S) * int(C) * int(esz) < (1 << 32)
+    return ok
+
+
+def aggregate_sorted_applies(N, P, L, S=None, C=256, esz=None):
+    """Does far3d_aggregate_forward take the sorted mode's operands (qbase)?  Kernel 8's rule and L * P <= 52: a camera row of the
+    query's weights has to fit the kernel's LDS slot.  A host predicate like aggregate_kernel8_applies; the library's rule, one for one."""
+    return aggregate_kernel8_applies(N, P, L, S, C, esz) and int(L) * int(P) <= AGG_SORTED_MAX_LP
 
 
 def _batch_rows(t, B, A, name, who):
@@ -304,15 +336,9 @@ def aggregate_batched(feat, ref, offsets, lidar2img, U, Vc, level_hw, level_star
         _chk(out, "out", ndim=3)
         if tuple(out.shape) != (B, A, C):
             raise ValueError("aggregate_batched: out must be (B,A,C) = %s, got %s" % ((B, A, C), tuple(out.shape)))
-    if tables is None and B * A > 0 and N <= 8 and P <= 16:
-        tables = agg_tables(Vc)
-    if tables is not None:
-        _chk(tables, "tables", torch.float32, 3)
-        if tuple(tables.shape) != (B, 2 + N, J):
-            raise ValueError("aggregate_batched: tables must be (B, 2+N, L*P*G) = %s, got %s" % ((B, 2 + N, J), tuple(tables.shape)))
-    hw_keep, hw_p = _host_i32([list(x) for x in level_hw])
-    st_keep, st_p = _host_i32(list(level_start))
-    pc_keep, pc_p = _host_f32(list(pc_range))
+    k8 = B * A > 0 and aggregate_kernel8_applies(N, P, L, S, C, feat.element_size())
+    tables, _keep, hw_p, st_p, pc_p = _agg_host_operands("aggregate_batched", Vc, tables, k8, (B, 2 + N, J), "(B, 2+N, L*P*G)",
+                                                         level_hw, level_start, pc_range)
     _lib.check(lib.far3d_aggregate_batched(_ptr(feat), _dt(feat), _ptr(ref), _ptr(offs), _ptr(l2i), _ptr(U2), _ptr(Vc),
                                            _ptr(tables) if tables is not None else None, _ptr(out), _dt(out), B, A, N, S, C, G, P, L,
                                            hw_p, st_p, pc_p, float(pad_hw[0]), float(pad_hw[1]),

@@ -103,6 +103,7 @@ def test_ordered_and_sorted_mode(hip_lib, geom, shape, dtype):
     Us, Os = torch.full_like(U, float("nan")), torch.full_like(offs, float("nan"))
     Us[inv.long()], Os[inv.long()] = U, offs
     run = lambda: ops.aggregate_forward(feat, ref, Os, l2i, Us, Vc, *geo, num_groups=ec.G, perm=perm, tables=tab, qbase=qbase)
+    assert ops.aggregate_sorted_applies(*shape) == ec.sorted_mode_shape(shape)
     if not ec.sorted_mode_shape(shape):       # L * P * 2 > 104 float4 per hinted camera row: the library refuses the call
         with pytest.raises(Far3dHipError, match="sorted mode"):
             run()
@@ -116,6 +117,20 @@ def test_ordered_and_sorted_mode(hip_lib, geom, shape, dtype):
     if shape[0] >= 3 and "all_cameras" in c["family"]:
         hint = int(qbase.cpu().view(torch.int32)[:, 3][iv][ec.rows_of(c, "all_cameras")[0]])
         assert (hint & 0xff) != ((hint >> 8) & 0xff), "two hinted cameras: the row's other cameras form their weights in the item loop"
+
+
+def test_sorted_gate_at_l4_p14(hip_lib):
+    """N = 2, P = 14, L = 4 (L * P = 56 > 52) is kernel 8's shape but not the sorted mode's: the library refuses a forced qbase, and
+    ops.aggregate_sorted_applies -- the gate the engine asks -- says no for the same shape, so the engine never forces it."""
+    from far3d_amd import ops
+    from far3d_amd.lib import Far3dHipError
+    shape = (2, 14, 4)
+    (feat, ref, offs, l2i, U, Vc), geo = _operands("dyadic", shape, torch.float32)
+    perm, (inv, qbase) = ops.aggregation_order(ref, l2i, geo[2], geo[3], sorted_operands=True)
+    with pytest.raises(Far3dHipError, match="sorted mode"):
+        ops.aggregate_forward(feat, ref, offs, l2i, U, Vc, *geo, num_groups=ec.G, perm=perm, qbase=qbase)
+    assert ops.aggregate_kernel8_applies(*shape) and not ops.aggregate_sorted_applies(*shape)
+    _check(ops.aggregate_forward(feat, ref, offs, l2i, U, Vc, *geo, num_groups=ec.G, perm=perm), "dyadic", shape, torch.float32, "variant 0 unsorted")
 
 
 # ------------------------------------------------------------------------------------------------ variant 9: sibling workgroups

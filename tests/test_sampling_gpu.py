@@ -287,3 +287,44 @@ def test_aggregate_two_kernel_split_is_bit_identical(hip_lib, dtype):
         assert 0 < int(lists.counts.max()) <= 1024
     with pytest.raises(ValueError):
         ops.aggregate_forward(feat, ref, Os, l2i, Us, Vc, c["level_hw"], c["level_start"], c["pc_range"], c["pad_hw"], variant=13, **kw)
+
+
+def _rule_case(N, P, seed):
+    """L = 1, one 4 x 4 map (S = 16), A = 3 queries a few metres in front of camera 0 / behind it (camera N/2), G = 8, C = 256."""
+    from far3d_amd import synth
+    g = torch.Generator().manual_seed(seed)
+    pad_hw, pc = (32, 32), [-20.0, -20.0, -3.0, 20.0, 20.0, 5.0]
+    lo, hi = torch.tensor(pc[:3]), torch.tensor(pc[3:])
+    ref_m = torch.tensor([[10.0, 1.0, 1.5], [-12.0, -2.0, 1.0], [8.0, -3.0, 2.0]])
+    _, _, l2i = synth.ring_cameras(N, pad_hw)
+    return dict(feat=torch.randn(N, 16, 256, generator=g), ref=(ref_m - lo) / (hi - lo), offsets=torch.randn(3, P, 3, generator=g),
+                lidar2img=l2i.contiguous(), U=torch.randn(3, P * 8, generator=g), Vc=torch.randn(N, P * 8, generator=g),
+                level_hw=[(4, 4)], level_start=[0], pc_range=pc, pad_hw=pad_hw, G=8)
+
+
+def test_variant0_is_kernel8_exactly_where_the_rule_says(hip_lib):
+    """ops.aggregate_kernel8_applies on both sides of N = 8 / 9 and P = 16 / 17 and at the smallest shape: where it holds, variant 8 runs
+    and variant 0 returns its bits; where it does not, variant 8 is refused and variant 0 returns kernel 7's bits.  fp32 and bf16 rows;
+    every result within 2e-5 of aggregate_general (the bar of tests/test_agg_edges_gpu.py) on outputs that are not all zero."""
+    from far3d_amd import ops
+    from far3d_amd.lib import Far3dHipError
+    d = lambda t: t.to(DEV).contiguous()
+    for (N, P), want_k8 in (((8, 16), True), ((9, 16), False), ((8, 17), False), ((2, 1), True)):
+        assert ops.aggregate_kernel8_applies(N, P, 1) == want_k8
+        c = _rule_case(N, P, seed=N * 100 + P)
+        for dtype in (torch.float32, torch.bfloat16):
+            ten = [d(c["feat"].to(dtype)), d(c["ref"]), d(c["offsets"]), d(c["lidar2img"]), d(c["U"]), d(c["Vc"])]
+            geo = (c["level_hw"], c["level_start"], c["pc_range"], c["pad_hw"])
+            assert ops.aggregate_kernel8_applies(N, P, 1, 16, 256, ten[0].element_size()) == want_k8
+            run = lambda variant: ops.aggregate_forward(*ten, *geo, num_groups=8, variant=variant)
+            v0 = run(0)
+            if want_k8:
+                assert torch.equal(v0, run(8)), (N, P, dtype)
+            else:
+                with pytest.raises(Far3dHipError):
+                    run(8)
+                assert torch.equal(v0, run(7)), (N, P, dtype)
+            want = ops.aggregate_general(*ten, *geo, 8)[0]
+            err = (v0 - want).abs().max().item()
+            print("N=%d P=%d %s: kernel %d, max |fused - general| %.3e, max |out| %.2f" % (N, P, dtype, 8 if want_k8 else 7, err, want.abs().max().item()))
+            assert want.abs().max().item() > 1e-2 and err < 2e-5, (N, P, dtype, err)
