@@ -5,9 +5,10 @@
 //   far3d_proposal_from_boxes  the counterpart of far3d_proposal_gather / far3d_proposal_gather_md that READS the box instead of
 //                              decoding it from the regression maps: depth cell, best bin(s), LID un-binning, un-projection,
 //                              context row; with topk > 1 the per-primary records far3d_proposal_extra_rows consumes.
-// The arithmetic after the box is written with the expressions of prop_gather_kernel / md_topk_record (frontend.hip), in their order:
+// The arithmetic after the box is the building blocks of prop_core.hpp, the ones prop_gather_kernel / md_topk_record (frontend.hip) use:
 // fed with that kernel's own boxes, scores and selection, the rows and records are the same bit for bit (tests/test_foreign_props_gpu.py).
 #include "common.hpp"
+#include "prop_core.hpp"
 
 // ------------------------------------------------------------------------------------------ ordered mask compaction
 #define COMPACT_THREADS 1024
@@ -100,22 +101,11 @@ struct FromBoxParams {
   const void* feat; int feat_dt, feat_vec;                            // (N,S,C) token maps; feat_vec: 16-byte reads are possible
   float* ref2d; float* ctx;                                           // (rows,3), (rows,C+1)
   int N, S, cap, C, hd, wd, nd, ds, rows, is_prob;
-  float depth_min, bin_size, pc_lo[3], pc_span[3], thr_logodds;
+  PropGeom geo; float thr_logodds;
   int md_k, md_min_bin;
   int* md_flags; int* md_info;                                        // (rows), (rows, 2K): the layout of far3d_proposal_gather_md
   int* mismatch_out;
 };
-
-#define FB_SLOTS 4                            // depth bins per lane: nd <= 256
-// value descending, lower bin first on ties; exact compares only, so every lane ends with the same pair
-__device__ __forceinline__ void fb_wave_argmax(float& v, int& i) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) {
-    const float ov = __shfl_xor(v, o);
-    const int oi = __shfl_xor(i, o);
-    if (ov > v || (ov == v && oi < i)) { v = ov; i = oi; }
-  }
-}
 
 // One wave per (box slot j, camera n).  The j-th box of camera n pairs with token sel_idx[n,j]; its row (input box / score and output)
 // is j + the boxes of the cameras before n.
@@ -139,74 +129,17 @@ __global__ __launch_bounds__(64) void prop_from_boxes_kernel(FromBoxParams g) {
   int u = (int)rintf(bcx / g.ds), v = (int)rintf(bcy / g.ds);
   u = min(max(u, 0), g.wd - 1); v = min(max(v, 0), g.hd - 1);
   const float* dl = g.depth + (long)n * g.d_img + ((long)v * g.wd + u) * g.d_cell;
-  // the K best bins (K = 1: the first maximum, like argmax), bins spread over the lanes (bin = lane + 64 * slot)
-  float lv[FB_SLOTS];
-#pragma unroll
-  for (int q = 0; q < FB_SLOTS; ++q) {
-    const int b = lane + 64 * q;
-    lv[q] = b < g.nd ? dl[(long)b * g.d_bin] : -INFINITY;
-  }
-  const int K = g.md_k > 1 ? g.md_k : 1;
-  unsigned taken = 0u;
+  // the K best bins (K = 1: the first maximum, like argmax)
+  float lv[PROP_SLOTS], lk[8];
   int bins[8];
-  float lk[8];
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    if (k < K) {                               // wave-uniform
-      float bv = -INFINITY; int bi = 0x7fffffff;
-#pragma unroll
-      for (int q = 0; q < FB_SLOTS; ++q) {
-        const int b = lane + 64 * q;
-        if (b < g.nd && !(taken & (1u << q)) && (lv[q] > bv || bi == 0x7fffffff)) { bv = lv[q]; bi = b; }
-      }
-      fb_wave_argmax(bv, bi);
-      if ((bi & 63) == lane) taken |= 1u << (bi >> 6);
-      bins[k] = bi; lk[k] = bv;
-    }
-  }
-  if (g.md_k > 1) {
-    float s_den = 1.f;
-    if (!g.is_prob) {
-      // logits: p_k = e_k / s in fp32 with e_k = exp(l_k - max) and s summed slot by slot, then over the wave -- as md_topk_record does
-      float e = 0.f;
-#pragma unroll
-      for (int q = 0; q < FB_SLOTS; ++q)
-        if (lane + 64 * q < g.nd) e += expf(lv[q] - lk[0]);
-#pragma unroll
-      for (int o = 32; o >= 1; o >>= 1) e += __shfl_down(e, o);
-      s_den = __shfl(e, 0);
-    }
-    if (lane == 0) {
-      int* info = g.md_info + (long)row * 2 * g.md_k;
-      info[0] = n;
-      const float p0 = g.is_prob ? lk[0] : expf(lk[0] - lk[0]) / s_den;
-#pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        if (k < g.md_k) {
-          info[1 + k] = bins[k];
-          if (k > 0) info[g.md_k + k] = __float_as_int((g.is_prob ? lk[k] : expf(lk[k] - lk[0]) / s_den) / p0);
-        }
-      }
-      g.md_flags[row] = bins[0] >= g.md_min_bin ? 1 : 0;
-    }
-  }
-  const int best = bins[0];
-  const float q = (float)best / 0.5f + 1.f;
-  const float d = g.depth_min + g.bin_size / 8.f * (q * q - 1.f);
-  const float dm = fmaxf(d, 1e-5f);
-  const float px = bcx * dm, py = bcy * dm;
-  const float* m = g.img2lidar + n * 16;
+  PROP_TOPK_BINS(dl, g.d_bin, g.nd, g.md_k > 1 ? g.md_k : 1, lane, lv, bins, lk)
+  if (g.md_k > 1) PROP_MD_RECORD(g, lv, bins, lk, lane, n, row, g.is_prob)
   float c3[3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const float w = m[4 * k] * px + m[4 * k + 1] * py + m[4 * k + 2] * d + m[4 * k + 3];
-    c3[k] = (w - g.pc_lo[k]) / g.pc_span[k];
-  }
+  PROP_BIN_TO_REF(g.geo, g.img2lidar + n * 16, bins[0], bcx, bcy, c3, 0)
   float* cr = g.ctx + (long)row * (g.C + 1);
   if (lane == 0) {
     g.ref2d[row * 3 + 0] = c3[0]; g.ref2d[row * 3 + 1] = c3[1]; g.ref2d[row * 3 + 2] = c3[2];
-    const float scc = fmaxf(sc, 1e-6f);
-    cr[g.C] = logf(scc / (1.f - scc)) - g.thr_logodds;
+    cr[g.C] = prop_score_logodds(sc) - g.thr_logodds;
   }
   // the token: 16-byte reads (the token rows are 16-byte aligned when C % 8 == 0); the context rows are C + 1 floats: dword stores
   const long tok = ((long)n * g.S + s) * g.C;
@@ -230,12 +163,7 @@ __global__ __launch_bounds__(64) void prop_from_boxes_kernel(FromBoxParams g) {
       }
     }
   } else {
-    for (int c = lane; c < g.C; c += 64) {
-      float fv;
-      if (g.feat_dt == FAR3D_DT_F32) fv = reinterpret_cast<const float*>(g.feat)[tok + c];
-      else fv = bf16_to_f32(reinterpret_cast<const bf16_t*>(g.feat)[tok + c]);
-      cr[c] = fv;
-    }
+    PROP_CTX_COPY(g.feat, g.feat_dt, tok, cr, 0, g.C, lane)
   }
 }
 
@@ -249,7 +177,7 @@ extern "C" int far3d_proposal_from_boxes(const float* boxes, const int* box_cnt,
                   "far3d_proposal_from_boxes: null argument");
   FAR3D_CHECK_ARG(N >= 1 && S >= 1 && cap >= 1 && rows >= 1 && C >= 1 && hd >= 1 && wd >= 1 && depth_stride >= 1 && depth_bins >= 1,
                   "far3d_proposal_from_boxes: bad sizes");
-  FAR3D_CHECK_ARG(nd >= 1 && nd <= 64 * FB_SLOTS, "far3d_proposal_from_boxes: depth bins nd=%d (1 ... %d)", nd, 64 * FB_SLOTS);
+  FAR3D_CHECK_ARG(nd >= 1 && nd <= 64 * PROP_SLOTS, "far3d_proposal_from_boxes: depth bins nd=%d (1 ... %d)", nd, 64 * PROP_SLOTS);
   FAR3D_CHECK_ARG(depth_layout == 0 || depth_layout == 1, "far3d_proposal_from_boxes: depth_layout 0 (N,hd,wd,nd) or 1 (N,nd,hd,wd)");
   FAR3D_CHECK_ARG(feat_dt == FAR3D_DT_F32 || feat_dt == FAR3D_DT_BF16, "far3d_proposal_from_boxes: tokens must be f32 or bf16");
   FAR3D_CHECK_ARG(topk == 1 || (topk >= 2 && topk <= 8 && topk <= nd && md_flags && md_info),
@@ -267,10 +195,8 @@ extern "C" int far3d_proposal_from_boxes(const float* boxes, const int* box_cnt,
   g.ref2d = ref2d; g.ctx = ctx;
   g.N = N; g.S = S; g.cap = cap; g.C = C; g.hd = hd; g.wd = wd; g.nd = nd; g.ds = depth_stride; g.rows = rows;
   g.is_prob = depth_is_prob ? 1 : 0;
-  g.depth_min = depth_min;
-  g.bin_size = 2.f * (depth_max - depth_min) / ((float)depth_bins * (1.f + depth_bins));
-  for (int k = 0; k < 3; ++k) { g.pc_lo[k] = pc_range[k]; g.pc_span[k] = pc_range[3 + k] - pc_range[k]; }
-  g.thr_logodds = logf(score_thr / (1.f - score_thr));
+  prop_fill_geom(g.geo, depth_min, depth_max, depth_bins, pc_range);
+  g.thr_logodds = prop_thr_logodds(score_thr);
   g.md_k = topk; g.md_min_bin = range_min_bin; g.md_flags = md_flags; g.md_info = md_info;
   g.mismatch_out = mismatch_out;
   hipLaunchKernelGGL(prop_from_boxes_kernel, dim3(cap, N), dim3(64), 0, (hipStream_t)stream, g);

@@ -11,6 +11,7 @@
 //   far3d_row_affine_ln    out = gamma[row] * LN_noaffine(x[row]) + beta[row] (+ add[row]): the MLN(180) modulation of
 //                          queries / memory (ref models/utils/misc.py:153-190; farhead.py:292-303).
 #include "common.hpp"
+#include "prop_core.hpp"
 
 // ------------------------------------------------------------------------------------------ stem im2col
 template <typename T>
@@ -267,7 +268,7 @@ struct GatherParams {
   float* box2d;                               // (Mcap,4) cx,cy,w,h (pixels)
   float* score;                               // (Mcap)
   int cap, C, hd, wd, nd, ds;
-  float depth_min, bin_size, pc_lo[3], pc_span[3], thr_logodds;
+  PropGeom geo; float thr_logodds;
   int N, rows_total;                          // rows_total > 0: fixed-capacity mode (rows past it are dropped, unused ones zero-filled)
   int* m_out; int* overflow_out;              // optional: number of valid rows; 1 if a proposal was (or may have been) dropped
   // multi-depth variant only (prop_gather_kernel<true>): top-`md_k` depth bins per primary, records for far3d_proposal_extra_rows
@@ -276,70 +277,15 @@ struct GatherParams {
 };
 
 // MD = true: the multi-depth variant (far3d_proposal_gather_md).  The primary rows are the same arithmetic as MD = false -- the
-// depth bin is the same first-maximum of the logits, found by a wave arg-max instead of a serial loop -- and every primary also
-// leaves a record of its top-K bins for the extra-row launch.
-#define MD_SLOTS 4                            // depth bins per lane: nd <= 256
-// Wave arg-max over the lanes' (value, bin) pairs: value descending, lower bin first on ties.  Exact compares only, so every lane
-// ends with the same pair.
-__device__ __forceinline__ void wave_argmax(float& v, int& i) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) {
-    const float ov = __shfl_xor(v, o);
-    const int oi = __shfl_xor(i, o);
-    if (ov > v || (ov == v && oi < i)) { v = ov; i = oi; }
-  }
-}
-
-// Multi-depth proposals (ref farhead.py:754-805): the top-K depth bins of one primary's cell, ranked by logit (softmax is monotone;
-// the top-1 is the first maximum, i.e. the K = 1 engine's bin), p_k = e_k / s in fp32 (e_k = exp(l_k - max)), the ratios
-// p_k / p_0 that scale the extra rows' log-odds, and the valid flag (top-1 bin >= the bin of range_min).  Lane 0 writes the record
-// of primary `row`; returns the top-1 bin.  Bins are spread over the lanes (bin = lane + 64 * slot).
+// depth bin is the same first-maximum of the logits, found by PROP_TOPK_BINS' wave arg-max instead of a serial loop -- and every
+// primary also leaves a record of its top-K bins for the extra-row launch: md_topk_record ranks the logits of primary `row`'s cell,
+// writes the record and returns the top-1 bin.
 template <typename P>
 __device__ int md_topk_record(const P& g, const float* __restrict__ dl, int lane, int n, int row) {
-  float lv[MD_SLOTS];
-#pragma unroll
-  for (int q = 0; q < MD_SLOTS; ++q) {
-    const int b = lane + 64 * q;
-    lv[q] = b < g.nd ? dl[b] : -INFINITY;
-  }
-  unsigned taken = 0u;
+  float lv[PROP_SLOTS], lk[8];
   int bins[8];
-  float lk[8];
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    if (k < g.md_k) {                          // wave-uniform
-      float v = -INFINITY; int i = 0x7fffffff;
-#pragma unroll
-      for (int q = 0; q < MD_SLOTS; ++q) {
-        const int b = lane + 64 * q;
-        if (b < g.nd && !(taken & (1u << q)) && (lv[q] > v || i == 0x7fffffff)) { v = lv[q]; i = b; }
-      }
-      wave_argmax(v, i);
-      if ((i & 63) == lane) taken |= 1u << (i >> 6);
-      bins[k] = i; lk[k] = v;
-    }
-  }
-  // softmax denominator: s = sum_b exp(l_b - max), reduced over the wave, lane 0's sum broadcast (one value for all lanes)
-  float e = 0.f;
-#pragma unroll
-  for (int q = 0; q < MD_SLOTS; ++q)
-    if (lane + 64 * q < g.nd) e += expf(lv[q] - lk[0]);
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) e += __shfl_down(e, o);
-  const float s = __shfl(e, 0);
-  if (lane == 0) {
-    const float p0 = expf(lk[0] - lk[0]) / s;
-    int* info = g.md_info + (long)row * 2 * g.md_k;
-    info[0] = n;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      if (k < g.md_k) {
-        info[1 + k] = bins[k];
-        if (k > 0) info[g.md_k + k] = __float_as_int((expf(lk[k] - lk[0]) / s) / p0);
-      }
-    }
-    g.md_flags[row] = bins[0] >= g.md_min_bin ? 1 : 0;
-  }
+  PROP_TOPK_BINS(dl, 1, g.nd, g.md_k, lane, lv, bins, lk)
+  PROP_MD_RECORD(g, lv, bins, lk, lane, n, row, false)
   return bins[0];
 }
 
@@ -356,12 +302,7 @@ __global__ __launch_bounds__(64) void prop_gather_kernel(GatherParams g) {
       if (g.m_out) *g.m_out = Mv;
       if (g.overflow_out) *g.overflow_out = (M > g.rows_total || full) ? 1 : 0;
     }
-    for (int row = Mv + j; row < g.rows_total; row += gridDim.x) {
-      if (lane < 3) g.ref2d[row * 3 + lane] = 0.f;
-      if (lane < 4) g.box2d[row * 4 + lane] = 0.f;
-      if (lane == 0) g.score[row] = 0.f;
-      for (int c = lane; c <= g.C; c += 64) g.ctx[(long)row * (g.C + 1) + c] = 0.f;
-    }
+    for (int row = Mv + j; row < g.rows_total; row += gridDim.x) PROP_ZERO_ROW(g, row, lane)
     return;
   }
   if (j >= g.sel_cnt[n]) return;
@@ -391,32 +332,15 @@ __global__ __launch_bounds__(64) void prop_gather_kernel(GatherParams g) {
   } else {
     for (int k = 1; k < g.nd; ++k) if (dl[k] > bv) { bv = dl[k]; best = k; }   // first maximum, like argmax
   }
-  const float q = (float)best / 0.5f + 1.f;
-  const float d = g.depth_min + g.bin_size / 8.f * (q * q - 1.f);
-  const float dm = fmaxf(d, 1e-5f);
-  const float px = bcx * dm, py = bcy * dm;
-  const float* m = g.img2lidar + n * 16;
   float c3[3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const float w = m[4 * k] * px + m[4 * k + 1] * py + m[4 * k + 2] * d + m[4 * k + 3];
-    c3[k] = (w - g.pc_lo[k]) / g.pc_span[k];
-  }
+  PROP_BIN_TO_REF(g.geo, g.img2lidar + n * 16, best, bcx, bcy, c3, 0)
   if (lane == 0) {
     g.ref2d[row * 3 + 0] = c3[0]; g.ref2d[row * 3 + 1] = c3[1]; g.ref2d[row * 3 + 2] = c3[2];
     g.box2d[row * 4 + 0] = bcx; g.box2d[row * 4 + 1] = bcy; g.box2d[row * 4 + 2] = brx - tlx; g.box2d[row * 4 + 3] = bry - tly;
     g.score[row] = sc;
-    // static top-K mode can pad a camera with zero-weight (non-peak) cells: clamp so their log-odds stay finite (a peak
-    // that passed the reference's `> score_thr` test is never below 1e-6, so threshold mode is unchanged)
-    const float scc = fmaxf(sc, 1e-6f);
-    g.ctx[(long)row * (g.C + 1) + g.C] = logf(scc / (1.f - scc)) - g.thr_logodds;
+    g.ctx[(long)row * (g.C + 1) + g.C] = prop_score_logodds(sc) - g.thr_logodds;
   }
-  for (int c = lane; c < g.C; c += 64) {
-    float fv;
-    if (g.feat_dt == FAR3D_DT_F32) fv = reinterpret_cast<const float*>(g.feat)[((long)n * lv.S + s) * g.C + c];
-    else fv = bf16_to_f32(reinterpret_cast<const bf16_t*>(g.feat)[((long)n * lv.S + s) * g.C + c]);
-    g.ctx[(long)row * (g.C + 1) + c] = fv;
-  }
+  PROP_CTX_COPY(g.feat, g.feat_dt, ((long)n * lv.S + s) * g.C, g.ctx, (long)row * (g.C + 1), g.C, lane)
 }
 
 static int fill_levels(PropLevels& lv, int L, const int32_t* hw, const int32_t* strides, const float* const* cls,
@@ -453,6 +377,24 @@ extern "C" int far3d_proposal_select(const float* const* cls, const float* const
   return FAR3D_OK;
 }
 
+// The part of GatherParams far3d_proposal_gather and far3d_proposal_gather_md share: level table, selection, depth map, tokens, outputs,
+// depth bins and range, threshold log-odds.  rows: rows_total / primary_rows.  The caller has checked its arguments.
+static void gather_fill(GatherParams& g, const float* const* reg, int nreg, int N, int L, const int32_t* level_hw, const int32_t* strides,
+                        const int* sel_idx, const int* sel_cnt, int cap, const float* weights, const float* depth_logit, int hd, int wd,
+                        int nd, int depth_stride, float depth_min, float depth_max, int depth_bins, const float* img2lidar,
+                        const void* feat, int feat_dt, int C, const float* pc_range, float score_thr, float* ref2d, float* ctx,
+                        float* box2d, float* score, int rows) {
+  memset(&g, 0, sizeof(g));
+  const float* none[PROP_MAX_L] = {nullptr, nullptr, nullptr, nullptr};
+  fill_levels(g.lv, L, level_hw, strides, none, reg, 1, nreg);
+  g.sel_idx = sel_idx; g.sel_cnt = sel_cnt; g.wgt = weights; g.depth_logit = depth_logit;
+  g.img2lidar = img2lidar; g.feat = feat; g.feat_dt = feat_dt; g.ref2d = ref2d; g.ctx = ctx; g.box2d = box2d; g.score = score;
+  g.cap = cap; g.C = C; g.hd = hd; g.wd = wd; g.nd = nd; g.ds = depth_stride;
+  prop_fill_geom(g.geo, depth_min, depth_max, depth_bins, pc_range);
+  g.thr_logodds = prop_thr_logodds(score_thr);
+  g.N = N; g.rows_total = rows;
+}
+
 extern "C" int far3d_proposal_gather(const float* const* reg, int nreg, int N, int L, const int32_t* level_hw,
                                      const int32_t* strides, const int* sel_idx, const int* sel_cnt,
                                      int cap, const float* weights, const float* depth_logit, int hd, int wd, int nd,
@@ -465,17 +407,9 @@ extern "C" int far3d_proposal_gather(const float* const* reg, int nreg, int N, i
   FAR3D_CHECK_ARG(L >= 1 && L <= PROP_MAX_L && N > 0 && cap > 0 && rows_total >= 0, "far3d_proposal_gather: bad sizes");
   FAR3D_CHECK_ARG(rows_total > 0 || (!m_out && !overflow_out), "far3d_proposal_gather: m_out / overflow_out need rows_total > 0");
   GatherParams g;
-  memset(&g, 0, sizeof(g));
-  const float* none[PROP_MAX_L] = {nullptr, nullptr, nullptr, nullptr};
-  fill_levels(g.lv, L, level_hw, strides, none, reg, 1, nreg);
-  g.sel_idx = sel_idx; g.sel_cnt = sel_cnt; g.wgt = weights; g.depth_logit = depth_logit;
-  g.img2lidar = img2lidar; g.feat = feat; g.feat_dt = feat_dt; g.ref2d = ref2d; g.ctx = ctx; g.box2d = box2d; g.score = score;
-  g.cap = cap; g.C = C; g.hd = hd; g.wd = wd; g.nd = nd; g.ds = depth_stride;
-  g.depth_min = depth_min;
-  g.bin_size = 2.f * (depth_max - depth_min) / ((float)depth_bins * (1.f + depth_bins));
-  for (int k = 0; k < 3; ++k) { g.pc_lo[k] = pc_range[k]; g.pc_span[k] = pc_range[3 + k] - pc_range[k]; }
-  g.thr_logodds = logf(score_thr / (1.f - score_thr));
-  g.N = N; g.rows_total = rows_total; g.m_out = m_out; g.overflow_out = overflow_out;
+  gather_fill(g, reg, nreg, N, L, level_hw, strides, sel_idx, sel_cnt, cap, weights, depth_logit, hd, wd, nd, depth_stride, depth_min,
+              depth_max, depth_bins, img2lidar, feat, feat_dt, C, pc_range, score_thr, ref2d, ctx, box2d, score, rows_total);
+  g.m_out = m_out; g.overflow_out = overflow_out;
   hipLaunchKernelGGL(prop_gather_kernel<false>, dim3(cap, rows_total > 0 ? N + 1 : N), dim3(64), 0, (hipStream_t)stream, g);
   FAR3D_CHECK_LAUNCH("far3d_proposal_gather");
   return FAR3D_OK;
@@ -495,20 +429,11 @@ extern "C" int far3d_proposal_gather_md(const float* const* reg, int nreg, int N
   FAR3D_CHECK_ARG(reg && level_hw && strides && sel_idx && sel_cnt && weights && depth_logit && img2lidar && feat &&
                   pc_range && ref2d && ctx && box2d && score && md_flags && md_info, "far3d_proposal_gather_md: null argument");
   FAR3D_CHECK_ARG(L >= 1 && L <= PROP_MAX_L && N > 0 && cap > 0 && primary_rows >= 0 && C > 0, "far3d_proposal_gather_md: bad sizes");
-  FAR3D_CHECK_ARG(topk >= 2 && topk <= 8 && topk <= nd && nd <= 64 * MD_SLOTS,
-                  "far3d_proposal_gather_md: need 2 <= topk <= 8, topk <= depth bins, depth bins <= %d", 64 * MD_SLOTS);
+  FAR3D_CHECK_ARG(topk >= 2 && topk <= 8 && topk <= nd && nd <= 64 * PROP_SLOTS,
+                  "far3d_proposal_gather_md: need 2 <= topk <= 8, topk <= depth bins, depth bins <= %d", 64 * PROP_SLOTS);
   GatherParams g;
-  memset(&g, 0, sizeof(g));
-  const float* none[PROP_MAX_L] = {nullptr, nullptr, nullptr, nullptr};
-  fill_levels(g.lv, L, level_hw, strides, none, reg, 1, nreg);
-  g.sel_idx = sel_idx; g.sel_cnt = sel_cnt; g.wgt = weights; g.depth_logit = depth_logit;
-  g.img2lidar = img2lidar; g.feat = feat; g.feat_dt = feat_dt; g.ref2d = ref2d; g.ctx = ctx; g.box2d = box2d; g.score = score;
-  g.cap = cap; g.C = C; g.hd = hd; g.wd = wd; g.nd = nd; g.ds = depth_stride;
-  g.depth_min = depth_min;
-  g.bin_size = 2.f * (depth_max - depth_min) / ((float)depth_bins * (1.f + depth_bins));
-  for (int k = 0; k < 3; ++k) { g.pc_lo[k] = pc_range[k]; g.pc_span[k] = pc_range[3 + k] - pc_range[k]; }
-  g.thr_logodds = logf(score_thr / (1.f - score_thr));
-  g.N = N; g.rows_total = primary_rows;
+  gather_fill(g, reg, nreg, N, L, level_hw, strides, sel_idx, sel_cnt, cap, weights, depth_logit, hd, wd, nd, depth_stride, depth_min,
+              depth_max, depth_bins, img2lidar, feat, feat_dt, C, pc_range, score_thr, ref2d, ctx, box2d, score, primary_rows);
   g.md_k = topk; g.md_min_bin = range_min_bin; g.md_flags = md_flags; g.md_info = md_info;
   hipLaunchKernelGGL(prop_gather_kernel<true>, dim3(cap, N), dim3(64), 0, (hipStream_t)stream, g);
   FAR3D_CHECK_LAUNCH("far3d_proposal_gather_md");
@@ -525,7 +450,7 @@ struct ExtraParams {
   const float* img2lidar;
   float* ref2d; float* ctx; float* box2d; float* score;
   int N, sel_cap, P, K, C, rows_total, fill_hole;
-  float depth_min, bin_size, pc_lo[3], pc_span[3];
+  PropGeom geo;
   int* m_out; int* overflow_out;
 };
 
@@ -592,17 +517,7 @@ __global__ __launch_bounds__(EXTRA_THREADS) void prop_extra_kernel(ExtraParams g
       if (lane == 0) {
         dr[g.C] = sr[g.C] * ratio;
         const float bcx = g.box2d[src * 4 + 0], bcy = g.box2d[src * 4 + 1];
-        // the same operation order as prop_gather_kernel
-        const float q = (float)bin / 0.5f + 1.f;
-        const float d = g.depth_min + g.bin_size / 8.f * (q * q - 1.f);
-        const float dm = fmaxf(d, 1e-5f);
-        const float px = bcx * dm, py = bcy * dm;
-        const float* mm = g.img2lidar + n * 16;
-#pragma unroll
-        for (int r = 0; r < 3; ++r) {
-          const float wv3 = mm[4 * r] * px + mm[4 * r + 1] * py + mm[4 * r + 2] * d + mm[4 * r + 3];
-          g.ref2d[dst * 3 + r] = (wv3 - g.pc_lo[r]) / g.pc_span[r];
-        }
+        PROP_BIN_TO_REF(g.geo, g.img2lidar + n * 16, bin, bcx, bcy, g.ref2d, dst * 3)   // what prop_gather_kernel expands
 #pragma unroll
         for (int r = 0; r < 4; ++r) g.box2d[dst * 4 + r] = g.box2d[src * 4 + r];
         g.score[dst] = g.score[src];
@@ -612,12 +527,7 @@ __global__ __launch_bounds__(EXTRA_THREADS) void prop_extra_kernel(ExtraParams g
   }
   if (!g.fill_hole) return;
   // the hole [M', rows_total): zeros, so that everything computed from it downstream stays finite (masked, not removed)
-  for (int row = Mq + w * (EXTRA_THREADS / 64) + wv; row < g.rows_total; row += G * (EXTRA_THREADS / 64)) {
-    if (lane < 3) g.ref2d[row * 3 + lane] = 0.f;
-    if (lane < 4) g.box2d[row * 4 + lane] = 0.f;
-    if (lane == 0) g.score[row] = 0.f;
-    for (int cc = lane; cc <= g.C; cc += 64) g.ctx[(long)row * (g.C + 1) + cc] = 0.f;
-  }
+  for (int row = Mq + w * (EXTRA_THREADS / 64) + wv; row < g.rows_total; row += G * (EXTRA_THREADS / 64)) PROP_ZERO_ROW(g, row, lane)
 }
 
 extern "C" int far3d_proposal_extra_rows(const int* sel_cnt, int N, int sel_cap, int primary_rows, int topk, const int32_t* md_flags,
@@ -635,9 +545,7 @@ extern "C" int far3d_proposal_extra_rows(const int* sel_cnt, int N, int sel_cap,
   g.sel_cnt = sel_cnt; g.flags = md_flags; g.info = md_info; g.img2lidar = img2lidar;
   g.ref2d = ref2d; g.ctx = ctx; g.box2d = box2d; g.score = score;
   g.N = N; g.sel_cap = sel_cap; g.P = primary_rows; g.K = topk; g.C = C; g.rows_total = rows_total; g.fill_hole = fill_hole;
-  g.depth_min = depth_min;
-  g.bin_size = 2.f * (depth_max - depth_min) / ((float)depth_bins * (1.f + depth_bins));
-  for (int k = 0; k < 3; ++k) { g.pc_lo[k] = pc_range[k]; g.pc_span[k] = pc_range[3 + k] - pc_range[k]; }
+  prop_fill_geom(g.geo, depth_min, depth_max, depth_bins, pc_range);
   g.m_out = m_out; g.overflow_out = overflow_out;
   // a workgroup per 16 primary rows, at most 256: each scans the flags (<= a few thousand) twice and writes 1/G of the extras
   const int G = max(1, min((primary_rows + 15) / 16, 256));

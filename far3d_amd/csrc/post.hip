@@ -14,6 +14,7 @@
 //   far3d_nan_to_num      torch.nan_to_num on the stacked decoder outputs (ref farhead.py:646) (+ optional bf16 copy).
 #include "common.hpp"
 #include "agg_tables.hpp"
+#include <type_traits>
 
 #ifdef FAR3D_PROFILING
 // tools/topk_phase_times.py: stage stamps (s_memtime) of block_topk_sorted, written by thread 0 of workgroup 0: 8 x uint64
@@ -441,16 +442,21 @@ __global__ __launch_bounds__(TOPK_THREADS) void topk_kernel(const float* __restr
   }
 }
 
+// The values a thread of block_topk_sorted holds in registers, chosen by the input's size n <= TOPK_THREADS * TOPK_MAXV and handed to f
+// as a constant: 4 (the memory update ranks A ~ 1.5k scores: 4 registers per thread instead of 40), 16 (the benchmarked frame's decode:
+// 1544 queries x 10 classes) or TOPK_MAXV.
+template <typename F>
+static inline void topk_for_maxv(long n, F f) {
+  if (n <= TOPK_THREADS * 4) f(std::integral_constant<int, 4>{});
+  else if (n <= TOPK_THREADS * 16) f(std::integral_constant<int, 16>{});
+  else f(std::integral_constant<int, TOPK_MAXV>{});
+}
+
 extern "C" int far3d_topk(const float* vals, int n, int K, int64_t* idx_out, float* val_out, void* stream) {
   FAR3D_CHECK_ARG(vals && idx_out, "far3d_topk: null pointer argument");
   FAR3D_CHECK_ARG(n > 0 && n <= TOPK_THREADS * TOPK_MAXV && K > 0 && K <= n && K <= TOPK_MAXK,
                   "far3d_topk: need 0 < K <= min(n, %d), n <= %d (got n=%d K=%d)", TOPK_MAXK, TOPK_THREADS * TOPK_MAXV, n, K);
-  if (n <= TOPK_THREADS * 4)      // the memory update ranks A ~ 1.5k scores: 4 registers per thread instead of 40
-    hipLaunchKernelGGL(topk_kernel<4>, dim3(1), dim3(TOPK_THREADS), 0, (hipStream_t)stream, vals, n, K, (long*)idx_out, val_out);
-  else if (n <= TOPK_THREADS * 16)
-    hipLaunchKernelGGL(topk_kernel<16>, dim3(1), dim3(TOPK_THREADS), 0, (hipStream_t)stream, vals, n, K, (long*)idx_out, val_out);
-  else
-    hipLaunchKernelGGL(topk_kernel<TOPK_MAXV>, dim3(1), dim3(TOPK_THREADS), 0, (hipStream_t)stream, vals, n, K, (long*)idx_out, val_out);
+  topk_for_maxv(n, [&](auto mv) { hipLaunchKernelGGL(topk_kernel<decltype(mv)::value>, dim3(1), dim3(TOPK_THREADS), 0, (hipStream_t)stream, vals, n, K, (long*)idx_out, val_out); });
   FAR3D_CHECK_LAUNCH("far3d_topk");
   return FAR3D_OK;
 }
@@ -467,6 +473,29 @@ struct DecodeParams {
   float lo[3], hi[3];
 };
 
+// Output row i of the decode from winner e = (ordered logit key << 32 | ~position) of the ranking: label, sigmoid score, the box
+// un-coded from its normalised code (ref nms_free_coder.py:58-88), the keep flag.  box / boxes / scores / labels / keep: the operand
+// bases (p's, or a stream's); cand_idx: a null constant, or the map from a candidate position to the original index.  A function-like
+// macro with every name passed in: behind a call the nine decode kernels came out in another instruction order (profiles/prop_host).
+#define DECODE_ROW(p, box, boxes, scores, labels, keep, e, i, cand_idx)                               \
+  {                                                                                                   \
+    int idx_ = (int)(0xffffffffu - (unsigned)((e) & 0xffffffffull));                                  \
+    if (cand_idx) idx_ = (cand_idx)[idx_];                                                            \
+    const float logit_ = ord_val((unsigned)((e) >> 32));                                              \
+    const int q_ = idx_ / (p).ncls;                                                                   \
+    (labels)[i] = (long)(idx_ - q_ * (p).ncls);                                                       \
+    (scores)[i] = 1.f / (1.f + expf(-logit_));                                                        \
+    const float* b_ = (box) + (long)q_ * (p).code;                                                    \
+    float* o_ = (boxes) + (long)(i) * ((p).code - 1);                                                 \
+    const float cx_ = b_[0], cy_ = b_[1], cz_ = b_[2];                                                \
+    const float w_ = expf(b_[3]), l_ = expf(b_[4]), h_ = expf(b_[5]);                                 \
+    o_[0] = cx_; o_[1] = cy_; o_[2] = cz_ - h_ * 0.5f;                                                \
+    o_[3] = w_; o_[4] = l_; o_[5] = h_;                                                               \
+    o_[6] = atan2f(b_[6], b_[7]);                                                                     \
+    for (int k_ = 8; k_ < (p).code; ++k_) o_[k_ - 1] = b_[k_];                                        \
+    (keep)[i] = (cx_ >= (p).lo[0] && cy_ >= (p).lo[1] && cz_ >= (p).lo[2] && cx_ <= (p).hi[0] && cy_ <= (p).hi[1] && cz_ <= (p).hi[2]) ? 1 : 0; \
+  }
+
 // cand_idx: null = the K winners' positions are indices into cls (A * ncls <= TOPK_THREADS * TOPK_MAXV, one launch);
 // otherwise cls points at candidate logits (the per-chunk winners of decode_chunk_kernel, chunk-major, each chunk sorted) and
 // cand_idx maps a position to the original index.  Equal logits keep their original index order in that layout, so the tie rule
@@ -478,21 +507,7 @@ __global__ __launch_bounds__(TOPK_THREADS) void decode_topk_kernel(DecodeParams 
   block_topk_sorted<MAXV>(p.cls, n, p.K, sel);
   for (int i = threadIdx.x; i < p.K; i += TOPK_THREADS) {
     const unsigned long long e = sel[i];
-    int idx = (int)(0xffffffffu - (unsigned)(e & 0xffffffffull));
-    if (cand_idx) idx = cand_idx[idx];
-    const float logit = ord_val((unsigned)(e >> 32));
-    const int q = idx / p.ncls;
-    p.labels[i] = (long)(idx - q * p.ncls);
-    p.scores[i] = 1.f / (1.f + expf(-logit));
-    const float* b = p.box + (long)q * p.code;
-    float* o = p.boxes + (long)i * (p.code - 1);
-    const float cx = b[0], cy = b[1], cz = b[2];
-    const float w = expf(b[3]), l = expf(b[4]), h = expf(b[5]);
-    o[0] = cx; o[1] = cy; o[2] = cz - h * 0.5f;
-    o[3] = w; o[4] = l; o[5] = h;
-    o[6] = atan2f(b[6], b[7]);
-    for (int k = 8; k < p.code; ++k) o[k - 1] = b[k];
-    p.keep[i] = (cx >= p.lo[0] && cy >= p.lo[1] && cz >= p.lo[2] && cx <= p.hi[0] && cy <= p.hi[1] && cz <= p.hi[2]) ? 1 : 0;
+    DECODE_ROW(p, p.box, p.boxes, p.scores, p.labels, p.keep, e, i, cand_idx)
   }
 }
 
@@ -533,20 +548,7 @@ __global__ __launch_bounds__(TOPK_THREADS) void decode_topk_mem_kernel(DecodePar
   block_topk_sorted<MAXV>(cls, n, p.K, sel);
   for (int i = threadIdx.x; i < p.K; i += TOPK_THREADS) {
     const unsigned long long e = sel[i];
-    const int idx = (int)(0xffffffffu - (unsigned)(e & 0xffffffffull));
-    const float logit = ord_val((unsigned)(e >> 32));
-    const int q = idx / p.ncls;
-    labels[i] = (long)(idx - q * p.ncls);
-    scores[i] = 1.f / (1.f + expf(-logit));
-    const float* b = box + (long)q * p.code;
-    float* o = boxes + (long)i * (p.code - 1);
-    const float cx = b[0], cy = b[1], cz = b[2];
-    const float w = expf(b[3]), l = expf(b[4]), h = expf(b[5]);
-    o[0] = cx; o[1] = cy; o[2] = cz - h * 0.5f;
-    o[3] = w; o[4] = l; o[5] = h;
-    o[6] = atan2f(b[6], b[7]);
-    for (int k = 8; k < p.code; ++k) o[k - 1] = b[k];
-    keep[i] = (cx >= p.lo[0] && cy >= p.lo[1] && cz >= p.lo[2] && cx <= p.hi[0] && cy <= p.hi[1] && cz <= p.hi[2]) ? 1 : 0;
+    DECODE_ROW(p, box, boxes, scores, labels, keep, e, i, (const int*)nullptr)
   }
 }
 
@@ -573,28 +575,45 @@ __global__ __launch_bounds__(TOPK_THREADS) void decode_chunk_kernel(const float*
   }
 }
 
+static DecodeParams decode_fill_params(const float* cls_last, const float* box_last, int A, int num_classes, int code_size, int K,
+                                       const float* post_center_range, float* boxes, float* scores, int64_t* labels, unsigned char* keep) {
+  DecodeParams p;
+  p.cls = cls_last; p.box = box_last; p.boxes = boxes; p.scores = scores; p.labels = (long*)labels; p.keep = keep;
+  p.A = A; p.ncls = num_classes; p.code = code_size; p.K = K;
+  for (int k = 0; k < 3; ++k) { p.lo[k] = post_center_range[k]; p.hi[k] = post_center_range[3 + k]; }
+  return p;
+}
+
+// The size rule far3d_decode_topk and far3d_decode_topk_mem state in the same words (the streams entry names the arguments in full:
+// its text is its own).
+static int decode_check_sizes(const char* who, int A, int num_classes, int code_size, int K) {
+  const long n = (long)A * num_classes;
+  FAR3D_CHECK_ARG(A > 0 && num_classes > 0 && code_size >= 8 && K > 0 && K <= TOPK_MAXK && n < (1L << 30) && K <= n,
+                  "%s: bad sizes A=%d ncls=%d code=%d K=%d (K <= %d)", who, A, num_classes, code_size, K, TOPK_MAXK);
+  return FAR3D_OK;
+}
+
+// n > DECODE_CHUNK logits: the chunks and their K winners each, which must fit one workgroup's ranking
+static int decode_chunks(const char* who, long n, int K, int& nchunks, long& ncand) {
+  nchunks = (int)((n + DECODE_CHUNK - 1) / DECODE_CHUNK);
+  ncand = (long)nchunks * K;
+  FAR3D_CHECK_ARG(ncand <= DECODE_CHUNK, "%s: A*num_classes=%ld needs %d chunks x K=%d candidates > %d", who, n, nchunks, K, DECODE_CHUNK);
+  return FAR3D_OK;
+}
+
 extern "C" int far3d_decode_topk(const float* cls_last, const float* box_last, int A, int num_classes, int code_size, int K,
                                  const float* post_center_range, float* boxes, float* scores, int64_t* labels,
                                  unsigned char* keep, void* workspace, long workspace_bytes, void* stream) {
   FAR3D_CHECK_ARG(cls_last && box_last && post_center_range && boxes && scores && labels && keep, "far3d_decode_topk: null pointer argument");
   const long n = (long)A * num_classes;
-  FAR3D_CHECK_ARG(A > 0 && num_classes > 0 && code_size >= 8 && K > 0 && K <= TOPK_MAXK && n < (1L << 30) && K <= n,
-                  "far3d_decode_topk: bad sizes A=%d ncls=%d code=%d K=%d (K <= %d)", A, num_classes, code_size, K, TOPK_MAXK);
-  DecodeParams p;
-  p.cls = cls_last; p.box = box_last; p.boxes = boxes; p.scores = scores; p.labels = (long*)labels; p.keep = keep;
-  p.A = A; p.ncls = num_classes; p.code = code_size; p.K = K;
-  for (int k = 0; k < 3; ++k) { p.lo[k] = post_center_range[k]; p.hi[k] = post_center_range[3 + k]; }
+  if (const int rc = decode_check_sizes("far3d_decode_topk", A, num_classes, code_size, K)) return rc;
+  DecodeParams p = decode_fill_params(cls_last, box_last, A, num_classes, code_size, K, post_center_range, boxes, scores, labels, keep);
   hipStream_t st = (hipStream_t)stream;
-  if (n <= TOPK_THREADS * 4) {
-    hipLaunchKernelGGL(decode_topk_kernel<4>, dim3(1), dim3(TOPK_THREADS), 0, st, p, (int)n, (const int*)nullptr);
-  } else if (n <= TOPK_THREADS * 16) {      // the benchmarked frame: 1544 queries x 10 classes
-    hipLaunchKernelGGL(decode_topk_kernel<16>, dim3(1), dim3(TOPK_THREADS), 0, st, p, (int)n, (const int*)nullptr);
-  } else if (n <= DECODE_CHUNK) {
-    hipLaunchKernelGGL(decode_topk_kernel<TOPK_MAXV>, dim3(1), dim3(TOPK_THREADS), 0, st, p, (int)n, (const int*)nullptr);
+  if (n <= DECODE_CHUNK) {
+    topk_for_maxv(n, [&](auto mv) { hipLaunchKernelGGL(decode_topk_kernel<decltype(mv)::value>, dim3(1), dim3(TOPK_THREADS), 0, st, p, (int)n, (const int*)nullptr); });
   } else {
-    const int nchunks = (int)((n + DECODE_CHUNK - 1) / DECODE_CHUNK);
-    const long ncand = (long)nchunks * K;
-    FAR3D_CHECK_ARG(ncand <= DECODE_CHUNK, "far3d_decode_topk: A*num_classes=%ld needs %d chunks x K=%d candidates > %d", n, nchunks, K, DECODE_CHUNK);
+    int nchunks; long ncand;
+    if (const int rc = decode_chunks("far3d_decode_topk", n, K, nchunks, ncand)) return rc;
     FAR3D_CHECK_ARG(workspace && workspace_bytes >= ncand * 8 && ((uintptr_t)workspace % 8) == 0,
                     "far3d_decode_topk: A*num_classes=%ld > %d needs a workspace of FAR3D_DECODE_WS_BYTES = %ld bytes (got %ld)", n, DECODE_CHUNK,
                     ncand * 8, workspace ? workspace_bytes : 0L);
@@ -625,19 +644,10 @@ extern "C" int far3d_decode_topk_mem(const float* cls_last, const float* box_las
                              workspace_bytes, stream);
   }
   FAR3D_CHECK_ARG(cls_last && box_last && post_center_range && boxes && scores && labels && keep, "far3d_decode_topk_mem: null pointer argument");
-  FAR3D_CHECK_ARG(A > 0 && num_classes > 0 && code_size >= 8 && K > 0 && K <= TOPK_MAXK && K <= n,
-                  "far3d_decode_topk_mem: bad sizes A=%d ncls=%d code=%d K=%d (K <= %d)", A, num_classes, code_size, K, TOPK_MAXK);
-  DecodeParams p;
-  p.cls = cls_last; p.box = box_last; p.boxes = boxes; p.scores = scores; p.labels = (long*)labels; p.keep = keep;
-  p.A = A; p.ncls = num_classes; p.code = code_size; p.K = K;
-  for (int k = 0; k < 3; ++k) { p.lo[k] = post_center_range[k]; p.hi[k] = post_center_range[3 + k]; }
+  if (const int rc = decode_check_sizes("far3d_decode_topk_mem", A, num_classes, code_size, K)) return rc;
+  const DecodeParams p = decode_fill_params(cls_last, box_last, A, num_classes, code_size, K, post_center_range, boxes, scores, labels, keep);
   hipStream_t st = (hipStream_t)stream;
-  if (n <= TOPK_THREADS * 4)
-    hipLaunchKernelGGL(decode_topk_mem_kernel<4>, dim3(2), dim3(TOPK_THREADS), 0, st, p, (int)n, mem_scores, mem_n, mem_K, (long*)mem_idx_out);
-  else if (n <= TOPK_THREADS * 16)
-    hipLaunchKernelGGL(decode_topk_mem_kernel<16>, dim3(2), dim3(TOPK_THREADS), 0, st, p, (int)n, mem_scores, mem_n, mem_K, (long*)mem_idx_out);
-  else
-    hipLaunchKernelGGL(decode_topk_mem_kernel<TOPK_MAXV>, dim3(2), dim3(TOPK_THREADS), 0, st, p, (int)n, mem_scores, mem_n, mem_K, (long*)mem_idx_out);
+  topk_for_maxv(n, [&](auto mv) { hipLaunchKernelGGL(decode_topk_mem_kernel<decltype(mv)::value>, dim3(2), dim3(TOPK_THREADS), 0, st, p, (int)n, mem_scores, mem_n, mem_K, (long*)mem_idx_out); });
   FAR3D_CHECK_LAUNCH("far3d_decode_topk_mem");
   return FAR3D_OK;
 }
@@ -667,9 +677,8 @@ extern "C" int far3d_decode_topk_mem_streams(const float* cls_last, const float*
   FAR3D_CHECK_ARG(A > 0 && num_classes > 0 && code_size >= 8 && K > 0 && K <= TOPK_MAXK && n < (1L << 30) && K <= n,
                   "%s: bad sizes A=%d num_classes=%d code_size=%d K=%d (K <= %d)", who, A, num_classes, code_size, K, TOPK_MAXK);
   if (n > DECODE_CHUNK) {
-    const int nchunks = (int)((n + DECODE_CHUNK - 1) / DECODE_CHUNK);
-    const long ncand = (long)nchunks * K;
-    FAR3D_CHECK_ARG(ncand <= DECODE_CHUNK, "%s: A*num_classes=%ld needs %d chunks x K=%d candidates > %d", who, n, nchunks, K, DECODE_CHUNK);
+    int nchunks; long ncand;
+    if (const int rc = decode_chunks(who, n, K, nchunks, ncand)) return rc;
     FAR3D_CHECK_ARG(workspace && workspace_bytes >= ncand * 8 && ((uintptr_t)workspace % 8) == 0 && workspace_bytes % 8 == 0,
                     "%s: A*num_classes=%ld > %d needs a workspace of B x workspace_bytes, workspace_bytes >= FAR3D_DECODE_WS_BYTES = %ld per "
                     "stream and a multiple of 8, 8-byte aligned (got %ld)", who, n, DECODE_CHUNK, ncand * 8, workspace ? workspace_bytes : 0L);
@@ -692,22 +701,11 @@ extern "C" int far3d_decode_topk_mem_streams(const float* cls_last, const float*
     }
     return FAR3D_OK;
   }
-  DecodeParams p;
-  p.cls = cls_last; p.box = box_last; p.boxes = boxes; p.scores = scores; p.labels = (long*)labels; p.keep = keep;
-  p.A = A; p.ncls = num_classes; p.code = code_size; p.K = K;
-  for (int k = 0; k < 3; ++k) { p.lo[k] = post_center_range[k]; p.hi[k] = post_center_range[3 + k]; }
+  const DecodeParams p = decode_fill_params(cls_last, box_last, A, num_classes, code_size, K, post_center_range, boxes, scores, labels, keep);
   const DecodeStreams ds{bs[0], bs[1], bs[2], bs[3], bs[4], bs[5], bs[6], bs[7]};
   hipStream_t st = (hipStream_t)stream;
   const dim3 grid(2, B);
-  if (n <= TOPK_THREADS * 4)
-    hipLaunchKernelGGL((decode_topk_mem_kernel<4, DecodeStreams>), grid, dim3(TOPK_THREADS), 0, st, p, (int)n, mem_scores, mem_n, mem_K,
-                       (long*)mem_idx_out, ds);
-  else if (n <= TOPK_THREADS * 16)
-    hipLaunchKernelGGL((decode_topk_mem_kernel<16, DecodeStreams>), grid, dim3(TOPK_THREADS), 0, st, p, (int)n, mem_scores, mem_n, mem_K,
-                       (long*)mem_idx_out, ds);
-  else
-    hipLaunchKernelGGL((decode_topk_mem_kernel<TOPK_MAXV, DecodeStreams>), grid, dim3(TOPK_THREADS), 0, st, p, (int)n, mem_scores, mem_n, mem_K,
-                       (long*)mem_idx_out, ds);
+  topk_for_maxv(n, [&](auto mv) { hipLaunchKernelGGL((decode_topk_mem_kernel<decltype(mv)::value, DecodeStreams>), grid, dim3(TOPK_THREADS), 0, st, p, (int)n, mem_scores, mem_n, mem_K, (long*)mem_idx_out, ds); });
   FAR3D_CHECK_LAUNCH(who);
   return FAR3D_OK;
 }

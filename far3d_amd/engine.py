@@ -1319,12 +1319,9 @@ class Far3DEngine:
     def decode_streams(self, cls_last, box_last, mem_scores, mem_K):
         """`decode` of B scene streams in one launch: cls_last (B, A, num_classes) / box_last (B, A, code_size) the last layer's logits
         and boxes, mem_scores (B, A) -- views with contiguous streams.  -> (dict of (B, .) results, idx (B, mem_K))."""
-        cfg = self.cfg
         B, A, ncls = cls_last.shape
-        K = min(cfg["max_num"], A * ncls)
-        need = ops.decode_ws_bytes(A * ncls, K)
-        ws = self._buf(("decode_ws_streams", B), (B * need,), torch.uint8) if need else None
-        return ops.decode_topk_mem_streams(cls_last, box_last, K, cfg.get("post_center_range", cfg["pc_range"]), mem_scores, mem_K, workspace=ws)
+        K, ws, rng = self._decode_args(A * ncls, B)
+        return ops.decode_topk_mem_streams(cls_last, box_last, K, rng, mem_scores, mem_K, workspace=ws)
 
     def _stage_inputs(self, data):
         """Copy the frame's inputs into static device buffers (so that a captured graph can be replayed on them)."""
@@ -1524,10 +1521,13 @@ class Far3DEngine:
         return outs
 
     # ------------------------------------------------------------------------------------------ a12: NMS-free decode
+    def _decode_args(self, n, B=None):
+        """K, the workspace and the centre range of the decode of n = A * num_classes logits, for one stream (B None) or B streams."""
+        K = min(self.cfg["max_num"], n)
+        need = ops.decode_ws_bytes(n, K)      # > 0 beyond 40960 logits (many adaptive queries): chunked two-launch decode
+        key, size = (("decode_ws",), need) if B is None else (("decode_ws_streams", B), B * need)
+        return K, (self._buf(key, (size,), torch.uint8) if need else None), self.cfg.get("post_center_range", self.cfg["pc_range"])
+
     def decode(self, all_cls, all_box, mem_scores=None, mem_K=None):   # core/bbox/coders/nms_free_coder.py:39-112; farhead.py:1224-1245
-        cfg = self.cfg
-        cls, box = all_cls[-1][0], all_box[-1][0]
-        K = min(cfg["max_num"], cls.numel())
-        need = ops.decode_ws_bytes(cls.numel(), K)      # > 0 beyond 40960 logits (many adaptive queries): chunked two-launch decode
-        ws = self._buf(("decode_ws",), (need,), torch.uint8) if need else None
-        return ops.decode_topk(cls, box, K, cfg.get("post_center_range", cfg["pc_range"]), workspace=ws, mem_scores=mem_scores, mem_K=mem_K)
+        K, ws, rng = self._decode_args(all_cls[-1][0].numel())
+        return ops.decode_topk(all_cls[-1][0], all_box[-1][0], K, rng, workspace=ws, mem_scores=mem_scores, mem_K=mem_K)

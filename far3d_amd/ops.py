@@ -1567,6 +1567,48 @@ def proposal_select(cls_maps, reg_maps, strides, cap, thr=0.1, topk=False):
     return wgt, sel_idx, sel_cnt
 
 
+def _opt_ptr(t):
+    return _ptr(t) if t is not None else None
+
+
+def _chk_i32_scalars(*ts):
+    for t in (t for t in ts if t is not None):
+        _chk(t, "m_out / overflow_out", torch.int32)
+
+
+class _PropOperands:
+    """The common part of proposal_gather / proposal_gather_md / proposal_extra_rows / proposal_from_boxes: the tensor checks (depth map,
+    img2lidar, tokens, records = (flags, info)) and the C arguments every entry takes in the same form: the level table (reg-map
+    pointers, nreg, L, sizes, strides), the depth-config triple and pc_range.  The host arrays live as long as the object."""
+
+    def __init__(self, depth_cfg, pc_range, img2lidar, depth=None, depth_name="depth_logit", feat=None, reg_maps=None, strides=None, records=None):
+        if depth is not None:
+            _chk(depth, depth_name, torch.float32, 4)
+        _chk(img2lidar, "img2lidar", torch.float32, 3)
+        if feat is not None:
+            _chk(feat, "feat", ndim=3)
+        if records is not None:
+            _chk(records[0], "md_flags", torch.int32, 1)
+            _chk(records[1], "md_info", torch.int32, 2)
+        if reg_maps is not None:
+            self._hw, hp = _host_i32([[int(c.shape[1]), int(c.shape[2])] for c in reg_maps])
+            self._st, sp = _host_i32(list(strides))
+            self._ra = _ptr_array(reg_maps)
+            self.levels = (self._ra, reg_maps[0].shape[3], len(reg_maps), hp, sp)     # reg, nreg, L, level_hw, strides
+        self._pc, self.pc_range = _host_f32(list(pc_range))
+        self.depth_cfg = (float(depth_cfg["depth_min"]), float(depth_cfg["depth_max"]), int(depth_cfg["num_depth_bins"]))
+
+
+def _proposal_gather(fn, name, p, N, cap, sel_idx, sel_cnt, weights, depth_logit, depth_stride, img2lidar, feat, score_thr, out, tail):
+    """The call far3d_proposal_gather and far3d_proposal_gather_md share up to the four outputs; tail: the entry's own arguments."""
+    reg, nreg, L, hp, sp = p.levels
+    _, hd, wd, nd = depth_logit.shape
+    _lib.check(fn(reg, nreg, N, L, hp, sp, _ptr(sel_idx), _ptr(sel_cnt), cap, _ptr(weights), _ptr(depth_logit), hd, wd, nd,
+                  int(depth_stride), *p.depth_cfg, _ptr(img2lidar), _ptr(feat), _dt(feat), feat.shape[2], p.pc_range, float(score_thr),
+                  *[_ptr(t) for t in out], *tail, _stream(feat)), name)
+    return tuple(out)
+
+
 def proposal_gather(reg_maps, strides, sel_idx, sel_cnt, weights, depth_logit, depth_stride, depth_cfg, img2lidar,
                     feat, pc_range, score_thr=0.1, out=None, rows_total=0, m_out=None, overflow_out=None):
     """Returns ref2d (N*cap,3), ctx (N*cap,C+1), box2d (N*cap,4), score (N*cap); rows >= sum(sel_cnt) are NOT written
@@ -1574,12 +1616,8 @@ def proposal_gather(reg_maps, strides, sel_idx, sel_cnt, weights, depth_logit, d
     rows_total > 0: fixed-capacity mode -- the buffers have rows_total rows, rows past M = sum(sel_cnt) are zero-filled, m_out /
     overflow_out (int32 device tensors of one element) receive min(M, rows_total) and the dropped-proposal flag."""
     lib = _lib.require_device()
-    L = len(reg_maps)
     N, cap = sel_idx.shape
-    hw = [(int(c.shape[1]), int(c.shape[2])) for c in reg_maps]
-    _chk(depth_logit, "depth_logit", torch.float32, 4)
-    _chk(img2lidar, "img2lidar", torch.float32, 3)
-    _chk(feat, "feat", ndim=3)
+    p = _PropOperands(depth_cfg, pc_range, img2lidar, depth=depth_logit, feat=feat, reg_maps=reg_maps, strides=strides)
     C = feat.shape[2]
     dev = feat.device
     M = N * cap if not rows_total else int(rows_total)
@@ -1594,23 +1632,10 @@ def proposal_gather(reg_maps, strides, sel_idx, sel_cnt, weights, depth_logit, d
         raise ValueError("proposal_gather: ref2d / ctx must be dense rows")
     if rows_total and min(ref2d.shape[0], ctx.shape[0], box2d.shape[0], score.shape[0]) < rows_total:
         raise ValueError("proposal_gather: the output buffers need rows_total=%d rows" % rows_total)
-    for t in (m_out, overflow_out):
-        if t is not None:
-            _chk(t, "m_out / overflow_out", torch.int32)
-    hk, hp = _host_i32([list(x) for x in hw])
-    sk, sp = _host_i32(list(strides))
-    pk, pp = _host_f32(list(pc_range))
-    ra = _ptr_array(reg_maps)
-    _, hd, wd, nd = depth_logit.shape
-    _lib.check(lib.far3d_proposal_gather(ra, reg_maps[0].shape[3], N, L, hp, sp, _ptr(sel_idx), _ptr(sel_cnt), cap,
-                                         _ptr(weights), _ptr(depth_logit), hd, wd, nd, int(depth_stride),
-                                         float(depth_cfg["depth_min"]), float(depth_cfg["depth_max"]),
-                                         int(depth_cfg["num_depth_bins"]), _ptr(img2lidar), _ptr(feat), _dt(feat), C, pp,
-                                         float(score_thr), _ptr(ref2d), _ptr(ctx), _ptr(box2d), _ptr(score), int(rows_total),
-                                         _ptr(m_out) if m_out is not None else None,
-                                         _ptr(overflow_out) if overflow_out is not None else None, _stream(feat)),
-               "far3d_proposal_gather")
-    return ref2d, ctx, box2d, score
+    _chk_i32_scalars(m_out, overflow_out)
+    return _proposal_gather(lib.far3d_proposal_gather, "far3d_proposal_gather", p, N, cap, sel_idx, sel_cnt, weights, depth_logit,
+                            depth_stride, img2lidar, feat, score_thr, (ref2d, ctx, box2d, score),
+                            (int(rows_total), _opt_ptr(m_out), _opt_ptr(overflow_out)))
 
 
 def depth_range_min_bin(depth_cfg, range_min):
@@ -1628,35 +1653,18 @@ def proposal_gather_md(reg_maps, strides, sel_idx, sel_cnt, weights, depth_logit
     box2d, score) (rows [0, N*cap), or [0, primary_rows) in fixed-capacity mode), and a record per primary into records = (flags
     (rows,) int32, info (rows, 2*topk) int32) for proposal_extra_rows.  2 <= topk <= 8."""
     lib = _lib.require_device()
-    L = len(reg_maps)
     N, cap = sel_idx.shape
-    hw = [(int(c.shape[1]), int(c.shape[2])) for c in reg_maps]
-    _chk(depth_logit, "depth_logit", torch.float32, 4)
-    _chk(img2lidar, "img2lidar", torch.float32, 3)
-    _chk(feat, "feat", ndim=3)
-    C = feat.shape[2]
     ref2d, ctx, box2d, score = out
     flags, info = records
-    _chk(flags, "md_flags", torch.int32, 1)
-    _chk(info, "md_info", torch.int32, 2)
+    p = _PropOperands(depth_cfg, pc_range, img2lidar, depth=depth_logit, feat=feat, reg_maps=reg_maps, strides=strides, records=records)
     rows = int(primary_rows) if primary_rows else N * cap
-    if ref2d.stride(0) != 3 or ctx.stride(0) != C + 1:
+    if ref2d.stride(0) != 3 or ctx.stride(0) != feat.shape[2] + 1:
         raise ValueError("proposal_gather_md: ref2d / ctx must be dense rows")
     if min(ref2d.shape[0], ctx.shape[0], box2d.shape[0], score.shape[0], flags.shape[0], info.shape[0]) < rows or info.shape[1] != 2 * topk:
         raise ValueError("proposal_gather_md: the output buffers and records need %d rows (info: %d columns)" % (rows, 2 * topk))
-    hk, hp = _host_i32([list(x) for x in hw])
-    sk, sp = _host_i32(list(strides))
-    pk, pp = _host_f32(list(pc_range))
-    ra = _ptr_array(reg_maps)
-    _, hd, wd, nd = depth_logit.shape
-    _lib.check(lib.far3d_proposal_gather_md(ra, reg_maps[0].shape[3], N, L, hp, sp, _ptr(sel_idx), _ptr(sel_cnt), cap,
-                                            _ptr(weights), _ptr(depth_logit), hd, wd, nd, int(depth_stride),
-                                            float(depth_cfg["depth_min"]), float(depth_cfg["depth_max"]),
-                                            int(depth_cfg["num_depth_bins"]), _ptr(img2lidar), _ptr(feat), _dt(feat), C, pp,
-                                            float(score_thr), _ptr(ref2d), _ptr(ctx), _ptr(box2d), _ptr(score), int(primary_rows),
-                                            int(topk), int(range_min_bin), _ptr(flags), _ptr(info), _stream(feat)),
-               "far3d_proposal_gather_md")
-    return ref2d, ctx, box2d, score
+    return _proposal_gather(lib.far3d_proposal_gather_md, "far3d_proposal_gather_md", p, N, cap, sel_idx, sel_cnt, weights, depth_logit,
+                            depth_stride, img2lidar, feat, score_thr, (ref2d, ctx, box2d, score),
+                            (int(primary_rows), int(topk), int(range_min_bin), _ptr(flags), _ptr(info)))
 
 
 def proposal_extra_rows(sel_cnt, sel_cap, primary_rows, topk, records, img2lidar, depth_cfg, pc_range, out, fill_hole=True,
@@ -1667,10 +1675,8 @@ def proposal_extra_rows(sel_cnt, sel_cap, primary_rows, topk, records, img2lidar
     that filled its selection).  One launch, no sync."""
     lib = _lib.require_device()
     _chk(sel_cnt, "sel_cnt", torch.int32, 1)
-    _chk(img2lidar, "img2lidar", torch.float32, 3)
+    p = _PropOperands(depth_cfg, pc_range, img2lidar, records=records)
     flags, info = records
-    _chk(flags, "md_flags", torch.int32, 1)
-    _chk(info, "md_info", torch.int32, 2)
     ref2d, ctx, box2d, score = out
     rows_total = ref2d.shape[0]
     C = ctx.shape[1] - 1
@@ -1678,16 +1684,11 @@ def proposal_extra_rows(sel_cnt, sel_cap, primary_rows, topk, records, img2lidar
         raise ValueError("proposal_extra_rows: ref2d / ctx / box2d / score must be dense rows, as many as ref2d's")
     if min(flags.shape[0], info.shape[0]) < primary_rows or info.shape[1] != 2 * topk or img2lidar.shape[0] < sel_cnt.shape[0]:
         raise ValueError("proposal_extra_rows: records need %d rows and %d columns, img2lidar one matrix per camera" % (primary_rows, 2 * topk))
-    for t in (m_out, overflow_out):
-        if t is not None:
-            _chk(t, "m_out / overflow_out", torch.int32)
-    pk, pp = _host_f32(list(pc_range))
+    _chk_i32_scalars(m_out, overflow_out)
     _lib.check(lib.far3d_proposal_extra_rows(_ptr(sel_cnt), sel_cnt.shape[0], int(sel_cap), int(primary_rows), int(topk), _ptr(flags),
-                                             _ptr(info), _ptr(img2lidar), float(depth_cfg["depth_min"]), float(depth_cfg["depth_max"]),
-                                             int(depth_cfg["num_depth_bins"]), pp, C, _ptr(ref2d), _ptr(ctx), _ptr(box2d), _ptr(score),
-                                             int(rows_total), 1 if fill_hole else 0,
-                                             _ptr(m_out) if m_out is not None else None,
-                                             _ptr(overflow_out) if overflow_out is not None else None, _stream(ctx)),
+                                             _ptr(info), _ptr(img2lidar), *p.depth_cfg, p.pc_range, C, _ptr(ref2d), _ptr(ctx), _ptr(box2d),
+                                             _ptr(score), int(rows_total), 1 if fill_hole else 0, _opt_ptr(m_out), _opt_ptr(overflow_out),
+                                             _stream(ctx)),
                "far3d_proposal_extra_rows")
     return ref2d, ctx, box2d, score
 
@@ -1729,9 +1730,7 @@ def proposal_from_boxes(boxes, box_cnt, scores, sel_idx, sel_cnt, depth, depth_s
     _chk(box_cnt, "box_cnt", torch.int32, 1)
     _chk(sel_idx, "sel_idx", torch.int32, 2)
     _chk(sel_cnt, "sel_cnt", torch.int32, 1)
-    _chk(depth, "depth", torch.float32, 4)
-    _chk(img2lidar, "img2lidar", torch.float32, 3)
-    _chk(feat, "feat", ndim=3)
+    p = _PropOperands(depth_cfg, pc_range, img2lidar, depth=depth, depth_name="depth", feat=feat)
     if depth_layout not in ("nhwc", "nchw"):
         raise ValueError("proposal_from_boxes: depth_layout %r (nhwc or nchw)" % (depth_layout,))
     N, cap = sel_idx.shape
@@ -1767,14 +1766,11 @@ def proposal_from_boxes(boxes, box_cnt, scores, sel_idx, sel_cnt, depth, depth_s
             raise ValueError("proposal_from_boxes: the records need %d rows (info: %d columns)" % (rows, 2 * topk))
     if mismatch_out is not None:
         _chk(mismatch_out, "mismatch_out", torch.int32)
-    pk, pp = _host_f32(list(pc_range))
     _lib.check(lib.far3d_proposal_from_boxes(_ptr(boxes), _ptr(box_cnt), _ptr(scores), rows, _ptr(sel_idx), _ptr(sel_cnt), cap, N, S,
                                              _ptr(depth), 0 if depth_layout == "nhwc" else 1, 1 if depth_is_prob else 0, hd, wd, nd,
-                                             int(depth_stride), float(depth_cfg["depth_min"]), float(depth_cfg["depth_max"]),
-                                             int(depth_cfg["num_depth_bins"]), _ptr(img2lidar), _ptr(feat), _dt(feat), C, pp,
-                                             float(score_thr), _ptr(ref2d), _ptr(ctx), topk, int(range_min_bin),
-                                             _ptr(flags) if flags is not None else None, _ptr(info) if info is not None else None,
-                                             _ptr(mismatch_out) if mismatch_out is not None else None, _stream(feat)),
+                                             int(depth_stride), *p.depth_cfg, _ptr(img2lidar), _ptr(feat), _dt(feat), C, p.pc_range,
+                                             float(score_thr), _ptr(ref2d), _ptr(ctx), topk, int(range_min_bin), _opt_ptr(flags),
+                                             _opt_ptr(info), _opt_ptr(mismatch_out), _stream(feat)),
                "far3d_proposal_from_boxes")
     return ref2d, ctx
 
@@ -2197,6 +2193,21 @@ def decode_ws_bytes(n, K):
     return 0 if n <= DECODE_CHUNK else -(-n // DECODE_CHUNK) * K * 8
 
 
+def _decode_outputs(dev, n, code, K, workspace, B=None):
+    """The decode's outputs for n = A * ncls logits per stream (each with a leading B for B streams) and its workspace, allocated here when
+    the chunked decode needs one and none, or too small a one, is given: (dict, workspace | None, workspace bytes per stream)."""
+    lead = () if B is None else (B,)
+    res = dict(boxes_3d=torch.empty(lead + (K, code - 1), dtype=torch.float32, device=dev),
+               scores_3d=torch.empty(lead + (K,), dtype=torch.float32, device=dev),
+               labels_3d=torch.empty(lead + (K,), dtype=torch.int64, device=dev),
+               keep=torch.empty(lead + (K,), dtype=torch.bool, device=dev))
+    need = decode_ws_bytes(n, K)
+    total = need * (1 if B is None else B)
+    if need and (workspace is None or workspace.numel() * workspace.element_size() < total):
+        workspace = torch.empty((total,), dtype=torch.uint8, device=dev)
+    return res, (workspace if need else None), need
+
+
 def decode_topk(cls_last, box_last, K, post_center_range, workspace=None, mem_scores=None, mem_K=None):
     """NMS-free decode of the last layer: returns dict(boxes_3d (K,code-1), scores_3d (K), labels_3d (K) i64, keep (K) bool).
     workspace: optional uint8 device buffer of decode_ws_bytes(A * ncls, K) bytes (allocated here when needed and not given).
@@ -2208,24 +2219,17 @@ def decode_topk(cls_last, box_last, K, post_center_range, workspace=None, mem_sc
     A, ncls = cls_last.shape
     code = box_last.shape[1]
     dev = cls_last.device
-    boxes = torch.empty((K, code - 1), dtype=torch.float32, device=dev)
-    scores = torch.empty((K,), dtype=torch.float32, device=dev)
-    labels = torch.empty((K,), dtype=torch.int64, device=dev)
-    keep = torch.empty((K,), dtype=torch.bool, device=dev)
+    res, workspace, need = _decode_outputs(dev, A * ncls, code, int(K), workspace)
     rk, rp = _host_f32(list(post_center_range))
-    need = decode_ws_bytes(A * ncls, int(K))
-    if need and (workspace is None or workspace.numel() * workspace.element_size() < need):
-        workspace = torch.empty((need,), dtype=torch.uint8, device=dev)
-    res = dict(boxes_3d=boxes, scores_3d=scores, labels_3d=labels, keep=keep)
+    args = (_ptr(cls_last), _ptr(box_last), A, ncls, code, int(K), rp, _ptr(res["boxes_3d"]), _ptr(res["scores_3d"]), _ptr(res["labels_3d"]),
+            _ptr(res["keep"]), _opt_ptr(workspace), need)
     if mem_scores is not None:
         _chk(mem_scores, "mem_scores", torch.float32, 1)
         idx = torch.empty((int(mem_K),), dtype=torch.int64, device=dev)
-        _lib.check(lib.far3d_decode_topk_mem(_ptr(cls_last), _ptr(box_last), A, ncls, code, int(K), rp, _ptr(boxes), _ptr(scores), _ptr(labels),
-                                             _ptr(keep), _ptr(workspace) if need else None, need, _ptr(mem_scores), mem_scores.numel(), int(mem_K),
-                                             _ptr(idx), _stream(cls_last)), "far3d_decode_topk_mem")
+        _lib.check(lib.far3d_decode_topk_mem(*args, _ptr(mem_scores), mem_scores.numel(), int(mem_K), _ptr(idx), _stream(cls_last)),
+                   "far3d_decode_topk_mem")
         return res, idx
-    _lib.check(lib.far3d_decode_topk(_ptr(cls_last), _ptr(box_last), A, ncls, code, int(K), rp, _ptr(boxes), _ptr(scores), _ptr(labels),
-                                     _ptr(keep), _ptr(workspace) if need else None, need, _stream(cls_last)), "far3d_decode_topk")
+    _lib.check(lib.far3d_decode_topk(*args, _stream(cls_last)), "far3d_decode_topk")
     return res
 
 
@@ -2248,22 +2252,16 @@ def decode_topk_mem_streams(cls_last, box_last, K, post_center_range, mem_scores
         raise ValueError("decode_topk_mem_streams: cls_last %s, box_last %s and mem_scores %s disagree on (B, A)" %
                          (tuple(cls_last.shape), tuple(box_last.shape), tuple(mem_scores.shape)))
     K, mem_K, dev = int(K), int(mem_K), cls_last.device
-    boxes = torch.empty((B, K, code - 1), dtype=torch.float32, device=dev)
-    scores = torch.empty((B, K), dtype=torch.float32, device=dev)
-    labels = torch.empty((B, K), dtype=torch.int64, device=dev)
-    keep = torch.empty((B, K), dtype=torch.bool, device=dev)
+    res, workspace, need = _decode_outputs(dev, A * ncls, code, K, workspace, B)
+    outs = [res[k] for k in ("boxes_3d", "scores_3d", "labels_3d", "keep")]
     idx = torch.empty((B, mem_K), dtype=torch.int64, device=dev)
     rk, rp = _host_f32(list(post_center_range))
-    need = decode_ws_bytes(A * ncls, K)
-    if need and (workspace is None or workspace.numel() * workspace.element_size() < B * need):
-        workspace = torch.empty((B * need,), dtype=torch.uint8, device=dev)
-    strides = (ctypes.c_long * 8)(cls_last.stride(0), box_last.stride(0), boxes.stride(0), scores.stride(0), labels.stride(0), keep.stride(0),
-                                  mem_scores.stride(0), idx.stride(0))
-    _lib.check(lib.far3d_decode_topk_mem_streams(_ptr(cls_last), _ptr(box_last), B, A, ncls, code, K, rp, _ptr(boxes), _ptr(scores), _ptr(labels),
-                                                 _ptr(keep), _ptr(workspace) if need else None, need, _ptr(mem_scores), mem_scores.shape[1],
-                                                 mem_K, _ptr(idx), ctypes.cast(strides, ctypes.c_void_p), _stream(cls_last)),
+    strides = (ctypes.c_long * 8)(cls_last.stride(0), box_last.stride(0), *[t.stride(0) for t in outs], mem_scores.stride(0), idx.stride(0))
+    _lib.check(lib.far3d_decode_topk_mem_streams(_ptr(cls_last), _ptr(box_last), B, A, ncls, code, K, rp, *[_ptr(t) for t in outs],
+                                                 _opt_ptr(workspace), need, _ptr(mem_scores), mem_scores.shape[1], mem_K, _ptr(idx),
+                                                 ctypes.cast(strides, ctypes.c_void_p), _stream(cls_last)),
                "far3d_decode_topk_mem_streams")
-    return dict(boxes_3d=boxes, scores_3d=scores, labels_3d=labels, keep=keep), idx
+    return res, idx
 
 
 def camera_prep(lidar2img, intrinsics=None, extrinsics=None):

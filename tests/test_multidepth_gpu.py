@@ -156,6 +156,37 @@ def test_md_kernels_full_size(hip_lib):
 
 
 # ------------------------------------------------------------------------------------------ engine level
+def test_extra_row_is_a_primary_of_the_swapped_depth_map(hip_lib):
+    """The extra rows' reference points come from the code the primaries' come from: with the best and the second-best bin of every
+    cell exchanged, plain proposal_gather makes each primary's point from the bin the K = 2 extra row of the same primary used -- the
+    same bits, with the same box and context features.  One camera, one 4 x 4 level, 3 proposals, 8 depth bins, C = 8."""
+    from far3d_amd import ops
+    g = torch.Generator().manual_seed(5)
+    N, cap, nd, C, K = 1, 3, 8, 8, 2
+    depth = dict(num_depth_bins=nd, depth_min=0.1, depth_max=60.0, stride=8)
+    cls = [torch.randn((N, 4, 4, 26), generator=g).to(DEV)]
+    reg = [(torch.randn((N, 4, 4, 5), generator=g) * 0.5).to(DEV)]
+    wgt, sel_idx, sel_cnt = ops.proposal_select(cls, reg, (8,), cap, thr=0.1, topk=True)
+    dl = torch.randn((N, 4, 4, nd), generator=g) * 2
+    top2 = torch.topk(dl, 2, dim=-1)
+    assert bool((top2.values[..., 0] > top2.values[..., 1]).all())          # no ties: best and second-best are defined
+    swapped = dl.scatter(-1, top2.indices, top2.values.flip(-1))
+    assert torch.equal(torch.topk(swapped, 2, dim=-1).indices, top2.indices.flip(-1))
+    feat = torch.randn((N, 16, C), generator=g).to(DEV)
+    data, _ = synth.make_frame(N, (32, 32), seed=5, frame_index=0)
+    i2l = data["lidar2img"][0].inverse().float().contiguous().to(DEV)
+    x = dict(reg=reg, strides=(8,), wgt=wgt, sel_idx=sel_idx, sel_cnt=sel_cnt, dl=dl.to(DEV), feat=feat, i2l=i2l, C=C)
+    out, rec = _bufs(K * cap, C), (torch.zeros((cap,), dtype=torch.int32, device=DEV), torch.zeros((cap, 2 * K), dtype=torch.int32, device=DEV))
+    m = torch.full((1,), -1, dtype=torch.int32, device=DEV)
+    ops.proposal_gather_md(reg, (8,), sel_idx, sel_cnt, wgt, x["dl"], 8, depth, i2l, feat, PC, K, 0, rec, out)
+    ops.proposal_extra_rows(sel_cnt, 0, cap, K, rec, i2l, depth, PC, out, m_out=m)
+    prim = ops.proposal_gather(reg, (8,), sel_idx, sel_cnt, wgt, swapped.to(DEV), 8, depth, i2l, feat, PC)
+    torch.cuda.synchronize()
+    assert int(sel_cnt.item()) == cap and int(m.item()) == K * cap and bool((rec[0] == 1).all())    # every primary valid: extra row cap + r
+    assert torch.equal(out[0][cap:], prim[0][:cap]) and not torch.equal(out[0][:cap], prim[0][:cap])    # ref2d, bit for bit
+    assert torch.equal(out[2][cap:], prim[2][:cap]) and torch.equal(out[1][cap:, :C], prim[1][:cap, :C])
+
+
 def _md_engine(name, precision="fp32", **over):
     from far3d_amd import engine
     z = np.load(os.path.join(GOLD, name + ".npz"))

@@ -139,6 +139,34 @@ def test_decode_with_the_memory_topk_in_one_launch(hip_lib, A, ncls, K, mK):
     assert torch.equal(i2, widx) and torch.equal(r2["labels_3d"], want["labels_3d"]) and torch.equal(r2["boxes_3d"], want["boxes_3d"])
 
 
+@pytest.mark.parametrize("A,ncls", [(4096, 1), (4097, 1), (8192, 2), (16385, 1), (40960, 1)])
+def test_decode_entries_agree_on_both_sides_of_every_register_rung(hip_lib, A, ncls):
+    """The three decode entries choose among the same instantiations (4 / 16 / 40 values per thread) by n = A * num_classes: n = 4096,
+    16384 and 40960 are the last sizes of their rungs, 4097 and 16385 the first of the next.  decode_topk, decode_topk with the memory
+    ranking and decode_topk_mem_streams on two different streams give the same bits per stream; labels and scores are torch.topk's over
+    distinct logits (scores: the kernel's 1 / (1 + expf(-x)) against torch.sigmoid, both a few ulp of values below 1: 1e-6 as above)."""
+    from far3d_amd import ops
+    g = torch.Generator().manual_seed(A + ncls)
+    n, K, mK, B = A * ncls, 64, 16, 2
+    cls = ((torch.stack([torch.randperm(n, generator=g) for _ in range(B)]).float() - n / 2) * (8.0 / n)).view(B, A, ncls)   # distinct
+    box = torch.randn(B, A, 10, generator=g)
+    mem = torch.stack([torch.randperm(min(A, 4096), generator=g) for _ in range(B)]).float()
+    rng = [-1.0, -1.0, -1.0, 1.0, 1.0, 1.0]
+    cd, bd, md = cls.to(DEV), box.to(DEV), mem.to(DEV)
+    sres, sidx = ops.decode_topk_mem_streams(cd, bd, K, rng, md, mK)
+    for b in range(B):
+        plain = ops.decode_topk(cd[b], bd[b], K, rng)
+        fused, fidx = ops.decode_topk(cd[b], bd[b], K, rng, mem_scores=md[b], mem_K=mK)
+        for k in ("boxes_3d", "scores_3d", "labels_3d", "keep"):
+            assert torch.equal(fused[k], plain[k]) and torch.equal(sres[k][b], plain[k]), (k, b)
+        assert plain["boxes_3d"].shape == (K, 9) and 0 < int(plain["keep"].sum()) < K
+        assert torch.equal(fidx, sidx[b]) and torch.equal(fidx.cpu(), torch.topk(mem[b], mK).indices)
+        want = torch.topk(cls[b].flatten(), K)
+        assert torch.equal(plain["labels_3d"].cpu(), want.indices % ncls)
+        assert (plain["scores_3d"].cpu() - torch.sigmoid(want.values)).abs().max().item() < 1e-6
+        assert torch.equal(plain["boxes_3d"].cpu()[:, :2], box[b][torch.div(want.indices, ncls, rounding_mode="floor")][:, :2])
+
+
 def test_decode_topk_keeps_velocity_channels(hip_lib):
     """code_size 10 (the reference nuScenes layout): vx, vy are appended like denormalize_bbox does (core/bbox/util.py:45-50)."""
     from far3d_amd import ops
