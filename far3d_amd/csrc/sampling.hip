@@ -130,6 +130,14 @@ struct AggParams {
   int* split_tick;                      // [rows] arrival tickets, zero at rest
   int split_extra;
 };
+// What the BATCHED instantiations of kernels 7 and 8 take in AggParams' place (far3d_aggregate_batched_holes): the same fields, then the
+// hole of unused query rows.  hole_count: a DEVICE array of one count per sample, never NULL (AGG_SAMPLE_HOLE_COUNT below); sample b's
+// rows [hole_start + hole_count[b], hole_end) hold no query.  The one-sample instantiations keep AggParams: their arguments and code do not change.
+struct AggParamsBatched : AggParams {
+  const int* hole_count;
+  int hole_start, hole_end;
+};
+template <bool BATCHED> using AggParamsOf = std::conditional_t<BATCHED, AggParamsBatched, AggParams>;
 #define AGG_SPLIT_FLAG (1 << 29)        // perm entry: this query is handled by two workgroups (set on both of its entries)
 #define AGG_SIBLING_FLAG (1 << 30)      // perm entry of the second workgroup (part 1)
 #define AGG_ROW_MASK 0x1fffffff
@@ -613,12 +621,25 @@ extern "C" int far3d_prof_set_agg_timestamps(long long* buf) {
 // (flattening B * A through q_per_xcd needs a division per workgroup to find the sample and makes the placement a function of B; it
 // was not measured).  Placement is a speed heuristic only; no result depends on it.  The per-sample extents are formed in 64 bits
 // (B * N * S * C may pass 2^31); inside a sample the 32-bit offsets stay.  No kernel argument is added: the extents come from AggParams,
-// and the one-sample instantiations (BATCHED = false) never look at blockIdx.y.
+// and the one-sample instantiations (BATCHED = false) never look at blockIdx.y.  The batched instantiations take AggParamsBatched in
+// AggParams' place: the same fields, then the hole of unused query rows per sample (far3d_aggregate_batched_holes, below).
 #define AGG_SAMPLE_BASES(b)                                                                                                       \
   do {                                                                                                                            \
     feat += (b) * prm.N * prm.S * 256; ref += (b) * prm.A * 3; offs += (b) * prm.A * prm.ldO; U += (b) * prm.A * prm.ldU;          \
     l2i += (b) * prm.N * 16;                                                                                                      \
     out = reinterpret_cast<char*>(out) + (b) * prm.A * 256 * (prm.out_dt == FAR3D_DT_F32 ? 4 : 2);                                \
+  } while (0)
+// The hole of a batched launch (AggParamsBatched).  AGG_SAMPLE_HOLE_COUNT fetches the sample's count: one scalar load, uniform per
+// workgroup, issued with the query-independent loads at the top of the kernel.  It stands under no branch and behind no select -- a value
+// loaded inside a branch is waited for inside it, a round trip in front of the whole load burst -- so the host never passes NULL: without
+// a hole the pointer names B readable words of an operand the kernel reads anyway and the hole is the empty [0, 0).  AGG_SAMPLE_HOLE,
+// where the slot's row is decided, clamps the count into [0, hole_end - hole_start] and turns slot a0 into ~a0 when it lies in
+// [hole_start + count, hole_end); the kernel's own hole exit (the one a perm entry ~a takes) does the rest.
+#define AGG_SAMPLE_HOLE_COUNT(b) (prm.hole_count[b])
+#define AGG_SAMPLE_HOLE(a, a0, cnt)                                                                                               \
+  do {                                                                                                                            \
+    const int lo_ = prm.hole_start + min(max(cnt, 0), prm.hole_end - prm.hole_start);                                             \
+    if ((a0) >= lo_ && (a0) < prm.hole_end) a = ~(a0);                                                                            \
   } while (0)
 // The ends of the two-wave kernels (7, 8, the gather half of variant 13), one definition each.  They are function-like macros with every
 // name passed in, not functions: the text reaches the compiler as if written out in the kernel, so the kernels' machine code is what it
@@ -656,7 +677,7 @@ template <typename TV, int PT, int OPT = 0, int CAPW = AGG7_CAPW, bool BATCHED =
 __global__ __launch_bounds__(128) void aggregate_v7_kernel(const TV* __restrict__ feat, const float* __restrict__ ref,
                                                            const float* __restrict__ offs, const float* __restrict__ l2i,
                                                            const float* __restrict__ U, const float* __restrict__ Vc,
-                                                           const int* __restrict__ perm, void* __restrict__ out, AggParams prm) {
+                                                           const int* __restrict__ perm, void* __restrict__ out, AggParamsOf<BATCHED> prm) {
   const int a0 = (blockIdx.x & 7) * prm.q_per_xcd + (blockIdx.x >> 3);
   if (a0 >= prm.A) return;
   int a = a0;
@@ -664,8 +685,10 @@ __global__ __launch_bounds__(128) void aggregate_v7_kernel(const TV* __restrict_
   const int t = threadIdx.x, lane = t & 63, wv = __builtin_amdgcn_readfirstlane(t >> 6);   // wave index: scalar
   const int P = PT ? PT : prm.P, L = prm.L, N = prm.N;
   const int NP = N * P, J = L * P, NLP = NP * L;
+  [[maybe_unused]] int hole_cnt = 0;
   if constexpr (BATCHED) {
     const long b = blockIdx.y;
+    hole_cnt = AGG_SAMPLE_HOLE_COUNT(b);      // first: its pointer comes with the kernel's first argument loads, its value with the burst
     AGG_SAMPLE_BASES(b);
     Vc += b * N * (J * 8);
   }
@@ -702,6 +725,7 @@ __global__ __launch_bounds__(128) void aggregate_v7_kernel(const TV* __restrict_
     }
   }
   if (perm) a = perm[a0];
+  if constexpr (BATCHED) AGG_SAMPLE_HOLE(a, a0, hole_cnt);
   if (a < 0) {      // ~a: row a holds no query (far3d_agg_order marks the hole of the fixed-capacity proposal mode): zero row, no work
     a = ~a;
     const int c = t * 2;
@@ -1102,13 +1126,14 @@ __device__ __forceinline__ void agg8_gather(const TV* __restrict__ feat, const u
 // global workspace (per wave: AGG_GCAP entries of offset + 8 weights, count; per slot: the 8 softmax denominators) instead of being
 // gathered; aggregate_gather_kernel below is the other half.  VERDICT r5 item 3 (c) asked for the split to be measured.
 #define AGG_GCAP 1024
-// BATCHED: far3d_aggregate_batched's instantiations, blockIdx.y = sample (AGG_SAMPLE_BASES above kernel 7); without perm, SPLIT, SORTED.
+// BATCHED: far3d_aggregate_batched's instantiations, blockIdx.y = sample (AGG_SAMPLE_BASES above kernel 7); without perm, SPLIT, SORTED;
+// a sample's hole of unused query rows comes from AggParamsBatched (AGG_SAMPLE_HOLE) and leaves through hole_row like a perm entry ~a.
 template <typename TV, int PT, int PRIO = 1, int LOOPNB = 4, int CAP = AGG8_CAPW, bool SPLIT = false, bool SORTED = false, int DEAL_ = -1, int PHASE = 0,
           bool BATCHED = false>
 __global__ __launch_bounds__(128, 4) void aggregate_v8_kernel(const TV* __restrict__ feat, const float* __restrict__ ref,
                                                            const float* __restrict__ offs, const float* __restrict__ l2i,
                                                            const float* __restrict__ U, const float* __restrict__ tab,
-                                                           const int* __restrict__ perm, void* __restrict__ out, AggParams prm,
+                                                           const int* __restrict__ perm, void* __restrict__ out, AggParamsOf<BATCHED> prm,
                                                            const float4* __restrict__ qbase) {
   // default dealing: snake on bf16 rows; greedy on fp32 rows, where the snake measured no gain (the gathers, twice the bytes, dominate)
   // and the in-tolerance engine keeps the summation order its parity evidence was taken with
@@ -1124,9 +1149,11 @@ __global__ __launch_bounds__(128, 4) void aggregate_v8_kernel(const TV* __restri
   const int t = threadIdx.x, lane = t & 63, wv = __builtin_amdgcn_readfirstlane(t >> 6);
   const int P = PT ? PT : prm.P, L = prm.L, N = prm.N;
   const int n4 = L * P * 2;                                               // float4 per camera row of the tables (<= 128)
+  [[maybe_unused]] int hole_cnt = 0;
   if constexpr (BATCHED) {
     static_assert(!SPLIT && !SORTED && PHASE == 0, "the batched launch has no sibling split, sorted mode or list-build phase");
     const long b = blockIdx.y;
+    hole_cnt = AGG_SAMPLE_HOLE_COUNT(b);      // first: its pointer comes with the kernel's first argument loads, its value with the burst
     AGG_SAMPLE_BASES(b);
     tab += b * (2 + N) * (n4 * 4);
   }
@@ -1178,6 +1205,7 @@ __global__ __launch_bounds__(128, 4) void aggregate_v8_kernel(const TV* __restri
     mv0 = ld0; mv1 = ld1;                                                    // wave 1's
     es0 = ld2; es1 = ld3;
     a = perm ? perm[a0] : a0;
+    if constexpr (BATCHED) AGG_SAMPLE_HOLE(a, a0, hole_cnt);
   }
   bool split = false;
   if constexpr (SPLIT) {
@@ -1779,7 +1807,7 @@ extern "C" int far3d_agg_tables(const float* Vc, float* tables, int layers, int 
 }
 
 // ------------------------------------------------------------------------------------------
-// Host side of the fused aggregation: far3d_aggregate_forward and far3d_aggregate_batched share ONE copy of the argument checks, the
+// Host side of the fused aggregation: far3d_aggregate_forward and far3d_aggregate_batched (with far3d_aggregate_batched_holes) share ONE copy of the argument checks, the
 // AggParams fill, the "kernel 8 applies" rule and the dispatch over row type and point count; the dynamic-LDS sizes stand beside the
 // carve-ups they mirror (agg3_lds_bytes, agg7_lds_bytes, AGG8_LDS).  The checks are several functions that take the entry's name (as in
 // csrc/attn_core.hpp) because each entry runs them in an order of its own, and the order decides which message a call with two faults
@@ -1855,14 +1883,14 @@ static inline void agg_for_row_and_points(int feat_dtype, int P, F f) {
   rows(std::integral_constant<int, 13>{});
 }
 template <bool SPLIT, bool SORTED, int DEAL, int PHASE = 0, bool BATCHED = false>
-static inline void agg_launch_v8(const AggLaunch& k, const float* cam_tables, const AggParams& prm, const float4* qbase) {
+static inline void agg_launch_v8(const AggLaunch& k, const float* cam_tables, const AggParamsOf<BATCHED>& prm, const float4* qbase) {
   agg_for_row_and_points<PHASE == 0>(k.feat_dtype, prm.P, [&](auto row, auto pt) {
     using TV = decltype(row);
     hipLaunchKernelGGL((aggregate_v8_kernel<TV, decltype(pt)::value, 1, 4, AGG8_CAPW, SPLIT, SORTED, DEAL, PHASE, BATCHED>), k.grid, dim3(128), AGG8_LDS, k.st, (const TV*)k.feat, k.ref, k.offs, k.l2i, k.U, cam_tables, k.perm, k.out, prm, qbase);
   });
 }
 template <int OPT, bool BATCHED = false>
-static inline void agg_launch_v7(const AggLaunch& k, const float* Vc, const AggParams& prm) {
+static inline void agg_launch_v7(const AggLaunch& k, const float* Vc, const AggParamsOf<BATCHED>& prm) {
   agg_for_row_and_points(k.feat_dtype, prm.P, [&](auto row, auto pt) {
     using TV = decltype(row);
     hipLaunchKernelGGL((aggregate_v7_kernel<TV, decltype(pt)::value, OPT, AGG7_CAPW, BATCHED>), k.grid, dim3(128), agg7_lds_bytes(prm.N, prm.P, prm.L), k.st, (const TV*)k.feat, k.ref, k.offs, k.l2i, k.U, Vc, k.perm, k.out, prm);
@@ -1921,28 +1949,51 @@ extern "C" int far3d_aggregate_forward(const void* feat, int feat_dtype, const f
 }
 
 // A batch of samples through kernel 8 / kernel 7 in one launch (include/far3d_hip.h).  The checks are far3d_aggregate_forward's, per
-// sample; what belongs to the engine's one-sample call (perm, sorted mode, sibling split, A/B variants) has no batched form.
+// sample; what belongs to the engine's one-sample call (perm, sorted mode, sibling split, A/B variants) has no batched form.  The one
+// host path of far3d_aggregate_batched (no hole) and far3d_aggregate_batched_holes; `who` is the entry's name in the messages.
+static int agg_batched(const char* who, const void* feat, int feat_dtype, const float* ref, const float* offsets,
+                       const float* lidar2img, const float* U, const float* Vc, const float* cam_tables,
+                       void* out, int out_dt, int B, int A, int N, int S, int C, int G, int P, int L,
+                       const int32_t* level_hw, const int32_t* level_start, const float* pc_range,
+                       float pad_h, float pad_w, int ldU, int ldOffs, const int32_t* hole_count, int hole_start, int hole_end,
+                       void* stream) {
+  if (const int rc = agg_check_shape(who, C, G, L, N, P, feat_dtype)) return rc;
+  if (const int rc = agg_check_out_dtype(who, out_dt)) return rc;
+  FAR3D_CHECK_ARG(B >= 0 && B <= 65535, "%s: B=%d out of range [0,65535] (the sample is the grid's y index)", who, B);
+  if (const int rc = agg_check_extent(who, A, N, S, C, "N*S*C of one sample")) return rc;
+  if (B == 0 || A == 0) return FAR3D_OK;
+  if (const int rc = agg_check_pointers(who, feat, ref, offsets, lidar2img, U, Vc, cam_tables, out, level_hw, level_start, pc_range)) return rc;
+  const bool v8 = agg_kernel8_applies(cam_tables, N, P, L, S, C, feat_dtype == FAR3D_DT_F32 ? 4 : 2);     // far3d_aggregate_forward's variant 0
+  FAR3D_CHECK_ARG(v8 || Vc, "%s: kernel 7 (no cam_tables, N=%d > 8, P=%d > 16 or a sample's value maps >= 4 GiB) needs Vc", who, N, P);
+  FAR3D_CHECK_ARG(!hole_count || (hole_start >= 0 && hole_start <= hole_end && hole_end <= A),
+                  "%s: hole rows [%d + count, %d) must lie in the A=%d query rows (0 <= hole_start <= hole_end <= A)", who, hole_start, hole_end, A);
+  AggParamsBatched prm;
+  if (const int rc = agg_fill_params(who, prm, A, N, S, G, P, L, level_hw, level_start, pc_range, pad_h, pad_w, U, ldU, ldOffs, out_dt)) return rc;
+  // no hole: the empty [0, 0), and as the count's address B words the kernel may read (the tables / Vc hold at least N * J floats per sample)
+  prm.hole_count = hole_count ? hole_count : reinterpret_cast<const int*>(v8 ? cam_tables : Vc);
+  prm.hole_start = hole_count ? hole_start : 0; prm.hole_end = hole_count ? hole_end : 0;
+  // grid x: a multiple of 8 (blockIdx.x & 7 = XCD), y: the sample; no perm
+  const AggLaunch k = {dim3(8 * prm.q_per_xcd, B), (hipStream_t)stream, feat, feat_dtype, ref, offsets, lidar2img, U, nullptr, out};
+  if (v8) agg_launch_v8<false, false, -1, 0, true>(k, cam_tables, prm, nullptr);
+  else agg_launch_v7<0, true>(k, Vc, prm);
+  FAR3D_CHECK_LAUNCH(who);
+  return FAR3D_OK;
+}
 extern "C" int far3d_aggregate_batched(const void* feat, int feat_dtype, const float* ref, const float* offsets,
                                        const float* lidar2img, const float* U, const float* Vc, const float* cam_tables,
                                        void* out, int out_dt, int B, int A, int N, int S, int C, int G, int P, int L,
                                        const int32_t* level_hw, const int32_t* level_start, const float* pc_range,
                                        float pad_h, float pad_w, int ldU, int ldOffs, void* stream) {
-  const char* who = "far3d_aggregate_batched";
-  if (const int rc = agg_check_shape(who, C, G, L, N, P, feat_dtype)) return rc;
-  if (const int rc = agg_check_out_dtype(who, out_dt)) return rc;
-  FAR3D_CHECK_ARG(B >= 0 && B <= 65535, "far3d_aggregate_batched: B=%d out of range [0,65535] (the sample is the grid's y index)", B);
-  if (const int rc = agg_check_extent(who, A, N, S, C, "N*S*C of one sample")) return rc;
-  if (B == 0 || A == 0) return FAR3D_OK;
-  if (const int rc = agg_check_pointers(who, feat, ref, offsets, lidar2img, U, Vc, cam_tables, out, level_hw, level_start, pc_range)) return rc;
-  const bool v8 = agg_kernel8_applies(cam_tables, N, P, L, S, C, feat_dtype == FAR3D_DT_F32 ? 4 : 2);     // far3d_aggregate_forward's variant 0
-  FAR3D_CHECK_ARG(v8 || Vc, "far3d_aggregate_batched: kernel 7 (no cam_tables, N=%d > 8, P=%d > 16 or a sample's value maps >= 4 GiB) needs Vc", N, P);
-  AggParams prm;
-  if (const int rc = agg_fill_params(who, prm, A, N, S, G, P, L, level_hw, level_start, pc_range, pad_h, pad_w, U, ldU, ldOffs, out_dt)) return rc;
-  // grid x: a multiple of 8 (blockIdx.x & 7 = XCD), y: the sample; no perm
-  const AggLaunch k = {dim3(8 * prm.q_per_xcd, B), (hipStream_t)stream, feat, feat_dtype, ref, offsets, lidar2img, U, nullptr, out};
-  if (v8) agg_launch_v8<false, false, -1, 0, true>(k, cam_tables, prm, nullptr);
-  else agg_launch_v7<0, true>(k, Vc, prm);
-  FAR3D_CHECK_LAUNCH("far3d_aggregate_batched");
-  return FAR3D_OK;
+  return agg_batched("far3d_aggregate_batched", feat, feat_dtype, ref, offsets, lidar2img, U, Vc, cam_tables, out, out_dt, B, A, N, S, C, G, P, L,
+                     level_hw, level_start, pc_range, pad_h, pad_w, ldU, ldOffs, nullptr, 0, 0, stream);
+}
+extern "C" int far3d_aggregate_batched_holes(const void* feat, int feat_dtype, const float* ref, const float* offsets,
+                                             const float* lidar2img, const float* U, const float* Vc, const float* cam_tables,
+                                             void* out, int out_dt, int B, int A, int N, int S, int C, int G, int P, int L,
+                                             const int32_t* level_hw, const int32_t* level_start, const float* pc_range,
+                                             float pad_h, float pad_w, int ldU, int ldOffs, const int32_t* hole_count, int hole_start,
+                                             int hole_end, void* stream) {
+  return agg_batched("far3d_aggregate_batched_holes", feat, feat_dtype, ref, offsets, lidar2img, U, Vc, cam_tables, out, out_dt, B, A, N, S, C, G,
+                     P, L, level_hw, level_start, pc_range, pad_h, pad_w, ldU, ldOffs, hole_count, hole_start, hole_end, stream);
 }
 

@@ -984,11 +984,15 @@ class Far3DEngine:
                 ops.add_cast(ws.outs[li], qpos, at, out_sum=X2[:A, :E], out_a=X2[:A, E:])
         return ws.outs
 
-    def decoder_streams(self, X2, x0, qpos, tokens, ref, hw, starts, lidar2img, pad_hw, A):
+    def decoder_streams(self, X2, x0, qpos, tokens, ref, hw, starts, lidar2img, pad_hw, A, holes=None):
         """`decoder` for B scene streams in ONE pass: X2, x0, qpos, tokens, ref, lidar2img are lists of B per-stream operands as
         `decoder` takes them (same shapes in every stream); hw, starts, pad_hw, A are shared.  Returns (B, layers, A, E) f32 whose
-        [b] is, bit for bit, decoder(...) on stream b's operands in its unfused form (fused_rows off; no hole: the static top-K
-        proposal mode) -- in every decoder dtype and whatever B is.
+        [b] is, bit for bit, decoder(..., hole=holes[b]) on stream b's operands in its unfused form (fused_rows off), hole rows
+        included -- in every decoder dtype and whatever B is.
+        holes: None, or a list of B per-stream (count int32 device scalar, start, end) tuples (_head_prepare's hs.hole: the
+        fixed-capacity threshold mode and the multi-depth extra rows), all None or none, start / end the same in every stream.  The
+        B counts are gathered into ONE (B,) buffer of the pass -- B small device copies, no sync -- which every layer's
+        far3d_attention_streams and far3d_aggregate_batched_holes launch reads.
         Per layer ONE far3d_attention_streams launch, ONE far3d_aggregate_batched launch, and every row-local launch (out-projection,
         the three LayerNorms, logit / offset linear, output projection, FFN) once over all B * A rows of (B, A, .) working buffers.
         The GEMMs go through ops.linear_streams, which takes its tile from ONE stream's row count, so a tile table keyed on rows
@@ -1007,6 +1011,17 @@ class Far3DEngine:
         nO = cfg["num_pts"] * 3
         N = lidar2img[0].shape[0]
         buf = lambda name, shape, dt: self._buf(("ds_" + name, B), shape, dt)
+        hole = None
+        if holes is not None and any(h is not None for h in holes):
+            if len(holes) != B or any(h is None for h in holes):
+                raise ValueError("decoder_streams: holes is one (count, start, end) per stream (%d), all of them None or none" % B)
+            if any((int(h[1]), int(h[2])) != (int(holes[0][1]), int(holes[0][2])) for h in holes):
+                raise ValueError("decoder_streams: every stream's hole must have the same start and end, got %s" %
+                                 [(int(h[1]), int(h[2])) for h in holes])
+            cnt = buf("hole_cnt", (B,), torch.int32)
+            for b, h in enumerate(holes):
+                cnt[b:b + 1].copy_(h[0].view(-1)[:1])
+            hole = (cnt, int(holes[0][1]), int(holes[0][2]))
         outs = buf("outs", (nL, B, A, E), torch.float32)
         QKV = buf("qkv", (B, Kt, nL * 3 * E), at)                  # per stream and layer a [q | k | v] column block
         XW = buf("xw", (B, A, 2 * E), at)                          # [x1+pos | x1] operand of the logit / offset GEMM
@@ -1042,12 +1057,12 @@ class Far3DEngine:
                 ops.linear_streams(XN, ly["qkv"], out=QKV[:, :A, c0:c0 + 3 * E])
             x = X0 if li == 0 else outs[li - 1]
             ops.attention_streams(QKV[:, :A, c0:c0 + E], QKV[:, :, c0 + E:c0 + 2 * E], QKV[:, :, c0 + 2 * E:c0 + 3 * E],
-                                  num_heads=cfg["num_heads"], out=att)
+                                  num_heads=cfg["num_heads"], out=att, hole=hole)
             y = ops.linear_streams(att, ly["out"], res=x)
             ops.layernorm(flat(y), *ly["norms"][0], out=flat(x1), add=flat(QP), y2=flat(XW)[:, :E], yb=flat(XW)[:, E:])
             ops.linear_streams(XW, ly["wl"], out=UL[:, :, :nJ + nO])
             ops.aggregate_batched(tok, REF, UL[:, :, nJ:nJ + nO], L2I, UL[:, :, :nJ], VC[li], hw, starts, cfg["pc_range"], pad_hw,
-                                  num_groups=cfg["num_groups"], out=agg_out, tables=TAB[li] if tabs else None)
+                                  num_groups=cfg["num_groups"], out=agg_out, tables=TAB[li] if tabs else None, hole=hole)
             y = ops.linear_streams(agg_out, ly["oproj"], res=x1)
             ops.layernorm(flat(y), *ly["norms"][1], out=flat(x2), yb=None if x2b is None else flat(x2b))
             hdn = ops.linear_streams(x2 if x2b is None else x2b, ly["ffn1"], act="relu", out_dtype=at)
@@ -1061,6 +1076,15 @@ class Far3DEngine:
     def camera_stage(self, img, dd, cam_ids, pad_hw, block_rows=None):
         """Everything that is independent per camera: backbone, FPN (+MLN), 2D head, depth, proposal
         selection and adaptive-query construction.  img (n,3,H,W) on device for the contiguous camera block `cam_ids`."""
+        st, heads = self._camera_maps(img, dd, cam_ids, pad_hw)
+        st.update(self.proposals(*heads, st["tokens"], block_rows))
+        return st
+
+    @_with_tile_tables
+    def _camera_maps(self, img, dd, cam_ids, pad_hw):
+        """camera_stage up to the proposals: backbone, FPN (+MLN), 2D head and depth for the camera block -> (st without the proposal
+        part, (cls, reg, depth_logit, img2lidar): what `proposals` takes in front of the tokens).  camera_stage_streams runs this once
+        over the images of several scene streams and, where a stream's proposals carry a count of their own, `proposals` per stream."""
         cfg = self.cfg
         n = img.shape[0]
         cam_ids = list(cam_ids)
@@ -1086,10 +1110,9 @@ class Far3DEngine:
         raw, tokens, hw, starts = self.fpn(feats, mln_scale, mln_shift)
         st = dict(tokens=tokens, hw=hw, starts=starts, raw=raw, lidar2img=lidar2img, cams=(lo, hi))
         cls, reg, depth_logit = self.roi_head(raw)
-        st.update(self.proposals(cls, reg, depth_logit, img2lidar, tokens, block_rows))
-        return st
+        return st, (cls, reg, depth_logit, img2lidar)
 
-    def camera_stage_streams(self, dds, pad_hw, key, img):
+    def camera_stage_streams(self, dds, pad_hw, key, img, stream_keys=None):
         """camera_stage ONCE on the images of len(dds) scene streams (streams.StreamBatch): dds the streams' staged inputs
         (_stage_inputs), each of N cameras; img (len(dds) * N, 3, H, W) their images, stream-major -- the buffer the streams staged
         into (image_slices); key: the buffer set of this pass, whose token buffer (token_slices) spans the streams' slices of the
@@ -1097,18 +1120,37 @@ class Far3DEngine:
         streams' concatenated, so camera b * N + n is camera n of stream b everywhere; proposal selection and gather work per camera,
         and in the static top-K mode stream b's rows are [b * N * K, (b + 1) * N * K) of the joint ref2d / ctx / box2d / score2d.
         Every launch chooses its tile as ONE stream's N images would (ops.tiles_as_for), so each image has the bits of its own
-        stream's camera_stage.  Returns one `st` dict per stream, views into the joint results."""
+        stream's camera_stage.  Returns one `st` dict per stream, views into the joint results.
+        stream_keys (the streams' own buffer sets, one per stream): the modes whose proposals carry a count per frame -- the
+        fixed-capacity threshold mode and multi-depth topk > 1 in either static mode.  The joint pass then ends behind the 2D head
+        (_camera_maps) and `proposals` runs per stream, on that stream's slices of the head's maps, inside its own buffer set: each
+        stream gets its own count, overflow flag and multi-depth records, and its reference points land in its own query buffer, as
+        in the whole-frame path.  Without stream_keys those modes are refused."""
         cfg = self.cfg
         nb, N, K = len(dds), dds[0]["img"].shape[0], cfg["proposal_topk"]
-        if K is None or self.md_k > 1:
+        per_stream = K is None or self.md_k > 1
+        if per_stream and (stream_keys is None or (K is None and cfg.get("proposal_capacity") is None)):
             raise ValueError("camera_stage_streams: the static top-K proposal mode with single-depth proposals only")
+        if per_stream and len(stream_keys) != nb:
+            raise ValueError("camera_stage_streams: stream_keys names one buffer set per stream (%d), got %d" % (nb, len(stream_keys)))
         if tuple(img.shape) != (nb * N,) + tuple(dds[0]["img"].shape[1:]):
             raise ValueError("camera_stage_streams: img %s is not the %d streams' %d images each" % (tuple(img.shape), nb, N))
         joint = {k: torch.cat([dd[k] for dd in dds], dim=1) for k in ("lidar2img", "intrinsics", "extrinsics")}
-        with self.buffers(key), ops.tiles_as_for(N, nb * N):
-            st = self.camera_stage(img, joint, range(nb * N), pad_hw, block_rows=nb * N * K)
         rows = lambda t, b, per: t[b * per:(b + 1) * per]
         res = []
+        if per_stream:
+            with self.buffers(key), ops.tiles_as_for(N, nb * N):
+                st, (cls, reg, depth_logit, img2lidar) = self._camera_maps(img, joint, range(nb * N), pad_hw)
+            for b in range(nb):
+                sb = dict(tokens=rows(st["tokens"], b, N), raw=[rows(r, b, N) for r in st["raw"]], hw=st["hw"], starts=st["starts"],
+                          lidar2img=rows(st["lidar2img"], b, N), cams=(0, N))
+                with self.buffers(stream_keys[b]):
+                    sb.update(self.proposals([rows(c, b, N) for c in cls], [rows(r, b, N) for r in reg], rows(depth_logit, b, N),
+                                             rows(img2lidar, b, N), sb["tokens"]))
+                res.append(sb)
+            return res
+        with self.buffers(key), ops.tiles_as_for(N, nb * N):
+            st = self.camera_stage(img, joint, range(nb * N), pad_hw, block_rows=nb * N * K)
         for b in range(nb):
             res.append(dict(tokens=rows(st["tokens"], b, N), raw=[rows(r, b, N) for r in st["raw"]], hw=st["hw"], starts=st["starts"],
                             lidar2img=rows(st["lidar2img"], b, N), cams=(0, N), depth_logit=rows(st["depth_logit"], b, N),
@@ -1303,7 +1345,7 @@ class Far3DEngine:
         rr = ops.linear_streams(ops.linear_streams(rr, self.reg_b[1].pc, act="relu", out_dtype=at), self.reg_b[2].pc)
         BOX, SC = buf("box", (B, nl * A, code), torch.float32), buf("score", (B, A), torch.float32)
         for b, hs in enumerate(hss):
-            ops.head_finalize(rr[b], hs.ref, CLS[b], cfg["pc_range"], nl, ncls, out=(BOX[b], SC[b]))
+            ops.head_finalize(rr[b], hs.ref, CLS[b], cfg["pc_range"], nl, ncls, hole=hs.hole, out=(BOX[b], SC[b]))
         results, idx = self.decode_streams(CLS.view(B, nl, A, ncls)[:, -1], BOX.view(B, nl, A, code)[:, -1], SC, cfg["topk_proposals"])
         res = []
         for b, hs in enumerate(hss):
@@ -1356,9 +1398,10 @@ class Far3DEngine:
         img = dd["img"]
         return self.camera_stage(img, dd, range(img.shape[0]), pad_hw)
 
-    def _head_part(self, st, dd, img_metas, pad_hw):
-        cfg = self.cfg
-        N = dd["img"].shape[0]
+    def _head_rows(self, st, N):
+        """The step of _head_part in front of head_stage, for a frame of N cameras whose camera stage gave `st`: the multi-depth extra
+        rows, then -> (M: adaptive-query rows, Mb: rows of the 2D boxes, m_dev: the device count of the rows that hold a query,
+        None where the shapes are exact).  streams.StreamBatch calls it per stream (static modes: no sync)."""
         M = self.static_adaptive_rows(N)
         md = st.get("md")
         m_dev = st["m_dev"]
@@ -1374,12 +1417,21 @@ class Far3DEngine:
             m_dev = None                                 # exact shapes, no hole
         else:
             Mb = M if md is None else md["primary_rows"]
-        outs = self.head_stage(st["tokens"], st["ref2d"], st["ctx"], M, dd, img_metas, st["hw"], st["starts"], pad_hw, m_dev=m_dev)
+        return M, Mb, m_dev
+
+    @staticmethod
+    def _head_outputs(outs, st, Mb):
+        """The camera stage's part of a frame's outputs (st; Mb: _head_rows') into the head's `outs`."""
         outs.update(fpn=st["raw"], depth_logit=st["depth_logit"], bbox2d=st["box2d"][:Mb], bbox2d_scores=st["score2d"][:Mb],
                     sel_idx=st["sel_idx"], sel_cnt=st["sel_cnt"], proposal_overflow=st["overflow"])
-        if md is not None:
-            outs["md_records"] = md["records"]
+        if st.get("md") is not None:
+            outs["md_records"] = st["md"]["records"]
         return outs
+
+    def _head_part(self, st, dd, img_metas, pad_hw):
+        M, Mb, m_dev = self._head_rows(st, dd["img"].shape[0])
+        outs = self.head_stage(st["tokens"], st["ref2d"], st["ctx"], M, dd, img_metas, st["hw"], st["starts"], pad_hw, m_dev=m_dev)
+        return self._head_outputs(outs, st, Mb)
 
     @contextlib.contextmanager
     def buffers(self, key):

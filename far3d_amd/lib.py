@@ -34,6 +34,8 @@ SIGNATURES = {
                                 [_p, _p, _p, c_float, c_float, c_int, c_int, c_int, _p, _p, c_int, _p, _p]),
     "far3d_aggregate_batched": (c_int, [_p, c_int, _p, _p, _p, _p, _p, _p, _p, c_int] + [c_int] * 8 +
                                 [_p, _p, _p, c_float, c_float, c_int, c_int, _p]),
+    "far3d_aggregate_batched_holes": (c_int, [_p, c_int, _p, _p, _p, _p, _p, _p, _p, c_int] + [c_int] * 8 +
+                                      [_p, _p, _p, c_float, c_float, c_int, c_int, _p, c_int, c_int, _p]),
     "far3d_agg_operands": (c_int, [_p] * 8 + [c_int] * 6 + [_p, c_float, c_float, c_int, c_int, c_int, _p]),
     "far3d_camera_sum": (c_int, [_p, _p, c_int, c_int, c_int, c_int, _p]),
     "far3d_conv2d_nhwc": (c_int, [_p, c_int, _p, c_int, _p, _p, c_int] + [c_int] * 5 + [c_long] + [c_int] * 4 +

@@ -309,15 +309,23 @@ def _agg_batched(ref, offsets, lidar2img, U, Vc, who):
 
 
 def aggregate_batched(feat, ref, offsets, lidar2img, U, Vc, level_hw, level_start, pc_range, pad_hw,
-                      num_groups=8, out=None, out_dtype=torch.float32, tables=None):
+                      num_groups=8, out=None, out_dtype=torch.float32, tables=None, hole=None):
     """aggregate_forward for a batch of samples in ONE launch (far3d_aggregate_batched): the fused kernel with the sample as a second
     grid index.  feat (B*N,S,256) or (B,N,S,256) f32|bf16; ref (B,A,3); offsets (B,A,P,3) or (B,A,P*3); lidar2img (B,N,4,4);
     U (B,A,L*P*G); Vc (B,N,L*P*G) -- the batched operands agg_operands takes (or one sample's, without B); U / offsets may be
     row-strided views (column blocks of a merged-GEMM output; U's stride a multiple of 4 floats).  tables: agg_tables(Vc)
     (B, 2+N, L*P*G), computed here (one more launch) when kernel 8 applies and the caller did not pass them.  Returns (B,A,256) of
-    out_dtype; out[b] has the bits of aggregate_forward on sample b, whatever B is.  The shape family is aggregate_fused_supported's."""
+    out_dtype; out[b] has the bits of aggregate_forward on sample b, whatever B is.  The shape family is aggregate_fused_supported's.
+    hole: None or (counts int32 device tensor (B,), start, end), the tuple attention_streams takes: sample b's rows
+    [start + counts[b], end) hold no query (far3d_aggregate_batched_holes): zero rows, their operands are not read, and out[b] has the
+    bits of aggregate_forward with perm = aggregation_order(hole=(counts[b:b + 1], start, end))."""
     lib = _lib.require_device()
     B, A, N, ref, offs, l2i, U2, Vc = _agg_batched(ref, offsets, lidar2img, U, Vc, "aggregate_batched")
+    if hole is not None:
+        cnt = hole[0]
+        if not (isinstance(cnt, torch.Tensor) and cnt.is_cuda and cnt.dtype == torch.int32 and cnt.numel() == B and cnt.is_contiguous()):
+            raise ValueError("aggregate_batched: the hole needs one count per sample (%d) as an int32 device tensor, got %s" %
+                             (B, "%s %s" % (cnt.dtype, tuple(cnt.shape)) if isinstance(cnt, torch.Tensor) else type(cnt).__name__))
     _chk(feat, "feat")
     if feat.dim() == 4:
         feat = feat.reshape(-1, *feat.shape[2:])
@@ -339,11 +347,13 @@ def aggregate_batched(feat, ref, offsets, lidar2img, U, Vc, level_hw, level_star
     k8 = B * A > 0 and aggregate_kernel8_applies(N, P, L, S, C, feat.element_size())
     tables, _keep, hw_p, st_p, pc_p = _agg_host_operands("aggregate_batched", Vc, tables, k8, (B, 2 + N, J), "(B, 2+N, L*P*G)",
                                                          level_hw, level_start, pc_range)
-    _lib.check(lib.far3d_aggregate_batched(_ptr(feat), _dt(feat), _ptr(ref), _ptr(offs), _ptr(l2i), _ptr(U2), _ptr(Vc),
-                                           _ptr(tables) if tables is not None else None, _ptr(out), _dt(out), B, A, N, S, C, G, P, L,
-                                           hw_p, st_p, pc_p, float(pad_hw[0]), float(pad_hw[1]),
-                                           U2.stride(0) if B * A > 0 else 0, offs.stride(0) if B * A > 0 else 0, _stream(feat)),
-               "far3d_aggregate_batched")
+    args = (_ptr(feat), _dt(feat), _ptr(ref), _ptr(offs), _ptr(l2i), _ptr(U2), _ptr(Vc), _ptr(tables) if tables is not None else None,
+            _ptr(out), _dt(out), B, A, N, S, C, G, P, L, hw_p, st_p, pc_p, float(pad_hw[0]), float(pad_hw[1]),
+            U2.stride(0) if B * A > 0 else 0, offs.stride(0) if B * A > 0 else 0)
+    if hole is None:
+        _lib.check(lib.far3d_aggregate_batched(*args, _stream(feat)), "far3d_aggregate_batched")
+    else:
+        _lib.check(lib.far3d_aggregate_batched_holes(*args, *_hole(hole), _stream(feat)), "far3d_aggregate_batched_holes")
     return out
 
 

@@ -12,14 +12,20 @@ scene change, memory update), the query construction and head_finalize, each str
 With both switches off a call is the per-stream camera stage and head around the one decoder pass.  Every stream's outputs are, bit
 for bit, those of a plain engine with the same weights fed that stream's frames -- whatever B is, for B = 1 too, with any switches.
 
-Scope: eager execution on one GPU in the static top-K proposal mode (cfg proposal_topk = K) with single-depth proposals and the
-unfused decoder layers.  That mode has no hole of unused query rows, which far3d_aggregate_batched cannot skip.  Everything else is
-refused with a ValueError that names the option."""
+Scope: eager execution on one GPU with the unfused decoder layers.  By default the static top-K proposal mode (cfg proposal_topk = K)
+with single-depth proposals: the mode without a hole of unused query rows, which far3d_aggregate_batched cannot skip.
+StreamBatch(..., hole_rows=True) also runs the modes that leave one -- the fixed-capacity threshold mode (proposal_topk=None,
+proposal_capacity=R: the reference's shipped proposal rule at a static row count) and multi_depth topk > 1 in either static mode.
+There every stream carries its own count of rows that hold a query, on the device: `proposals` runs per stream behind the joint
+backbone / FPN / 2D-head pass, the decoder pass hands the B counts to far3d_attention_streams and far3d_aggregate_batched_holes, and
+head_finalize masks each stream's hole.  No host sync in any mode; check_proposal_overflow() is the one that reads the flags.
+Everything else is refused with a ValueError that names the option."""
 import contextlib
 import functools
 
 import torch
 
+from . import lib as _lib
 from . import ops
 
 # What the convolution entries bound for ONE launch (csrc/igemm.hip, far3d_conv2d_nhwc; csrc/conv_ws.hip, the grouped entry): the span
@@ -46,17 +52,23 @@ def stream_chunks(streams, images, image_span, limit=SPAN_LIMIT_BYTES, max_strea
     return [per] * (streams // per) + ([streams % per] if streams % per else [])
 
 
-def _refusal(engine):
-    """The first engine option StreamBatch does not run with, as the text of a ValueError; None when there is none."""
+def _refusal(engine, hole_rows=False):
+    """The first engine option StreamBatch does not run with, as the text of a ValueError; None when there is none.
+    hole_rows: the runner takes the modes with a hole of unused query rows (StreamBatch's keyword)."""
     cfg = engine.cfg
     if "head" not in engine.parts or "backbone" not in engine.parts:
         return "parts=%s: StreamBatch runs whole frames (backbone, neck, roi, head)" % (engine.parts,)
     if cfg["proposal_topk"] is None:
         if cfg.get("proposal_capacity") is not None:
-            return ("proposal_capacity=%s: the fixed-capacity threshold mode leaves a hole of unused query rows, which the batched "
-                    "aggregation cannot skip; use proposal_topk=K" % cfg["proposal_capacity"])
-        return "proposal_topk=None (the reference's threshold mode): its query count depends on the frame; use proposal_topk=K"
-    if engine.md_k > 1:
+            if not hole_rows:
+                return ("proposal_capacity=%s: the fixed-capacity threshold mode leaves a hole of unused query rows, which the batched "
+                        "aggregation cannot skip; use proposal_topk=K" % cfg["proposal_capacity"])
+        elif hole_rows:
+            return ("proposal_topk=None without proposal_capacity (the reference's threshold mode): its query count depends on the frame; "
+                    "use proposal_capacity=R or proposal_topk=K")
+        else:
+            return "proposal_topk=None (the reference's threshold mode): its query count depends on the frame; use proposal_topk=K"
+    if engine.md_k > 1 and not hole_rows:
         return "multi_depth topk=%d: the extra rows leave a hole of unused query rows; use topk=1" % engine.md_k
     if engine.use_graph:
         return "use_graph: StreamBatch runs eagerly"
@@ -72,17 +84,20 @@ def _refusal(engine):
 
 
 class StreamBatch:
-    def __init__(self, engine, streams, camera_batch=True, head_batch=True, max_camera_streams=None):
+    def __init__(self, engine, streams, camera_batch=True, head_batch=True, max_camera_streams=None, hole_rows=False):
         """camera_batch / head_batch: the shared camera pass and the shared head launches (module docstring); both off is the
-        per-stream path around the one decoder pass.  max_camera_streams caps the streams of one camera pass (stream_chunks)."""
+        per-stream path around the one decoder pass.  max_camera_streams caps the streams of one camera pass (stream_chunks).
+        hole_rows: also run the modes that leave a hole of unused query rows (module docstring); off, they are refused."""
         if int(streams) < 1:
             raise ValueError("streams=%s: at least one scene stream" % (streams,))
         if max_camera_streams is not None and int(max_camera_streams) < 1:
             raise ValueError("max_camera_streams=%s: a camera pass holds at least one stream" % (max_camera_streams,))
-        why = _refusal(engine)
+        self.hole_rows = bool(hole_rows)
+        why = _refusal(engine, self.hole_rows)
         if why is not None:
             raise ValueError("StreamBatch: " + why)
         self.engine, self.streams = engine, int(streams)
+        self._overflow = [None] * int(streams)      # per stream: the latest frame's overflow flag (device int32; None: the mode has none)
         self.camera_batch, self.head_batch, self.max_camera_streams = bool(camera_batch), bool(head_batch), max_camera_streams
         self.camera_chunks = None   # the stream counts of the latest call's camera passes (camera_batch)
         # per stream: the streaming memory (allocated once, zeroed in place on that stream's scene change) and the scene it is in
@@ -141,6 +156,20 @@ class StreamBatch:
         """Stream b's streaming memory (the dict of Far3DEngine.mem)."""
         return self._state[b]["mem"]
 
+    def check_proposal_overflow(self):
+        """Far3DEngine.check_proposal_overflow for the latest forward_frames call: raise, naming the streams, if a stream's frame had
+        more proposals than rows (or a camera filled its selection capacity).  One sync for all streams; the per-stream flags stay in
+        the outputs (proposal_overflow)."""
+        flags = [(b, f) for b, f in enumerate(self._overflow) if f is not None]
+        if not flags:
+            return
+        over = [b for (b, _), v in zip(flags, torch.stack([f.view(-1)[0] for _, f in flags]).tolist()) if v != 0]
+        if over:
+            cfg = self.engine.cfg
+            raise _lib.Far3dHipError("proposal capacity exceeded in streams %s: more than proposal_capacity=%s proposals (multi_depth_capacity=%s "
+                                     "extra rows) in the frame, or a camera reached proposal_cap=%s; raise them" %
+                                     (over, cfg.get("proposal_capacity"), cfg.get("multi_depth_capacity"), cfg["proposal_cap"]))
+
     def _camera_streams(self, dds, pad_hw):
         """The camera stage of all streams in as few passes as the kernels' extents allow -> the B per-stream `st` dicts."""
         e, B = self.engine, self.streams
@@ -156,7 +185,8 @@ class StreamBatch:
             b1 = b0 + nb
             key = ("streams_cam", id(self), b0, b1)
             e.token_slices[key] = functools.partial(self._pass_tokens, b0, b1)
-            sts += e.camera_stage_streams(dds[b0:b1], pad_hw, key, self._images[b0 * N:b1 * N])
+            sts += e.camera_stage_streams(dds[b0:b1], pad_hw, key, self._images[b0 * N:b1 * N],
+                                          stream_keys=[self._key(b) for b in range(b0, b1)] if self.hole_rows else None)
             b0 = b1
         return sts
 
@@ -168,7 +198,7 @@ class StreamBatch:
         e, B = self.engine, self.streams
         if len(datas) != B or len(img_metas_list) != B:
             raise ValueError("forward_frames: one frame per stream (%d), got %d / %d" % (B, len(datas), len(img_metas_list)))
-        why = _refusal(e)          # the options are attributes: they may have been set since the constructor looked
+        why = _refusal(e, self.hole_rows)          # the options are attributes: they may have been set since the constructor looked
         if why is not None:
             raise ValueError("StreamBatch: " + why)
         pad_hw = tuple(img_metas_list[0][0]["pad_shape"][0][:2])
@@ -176,7 +206,7 @@ class StreamBatch:
             raise ValueError("forward_frames: every stream's frame must have the same padded size")
         cfg = e.cfg
         with ops.use_tile_tables(e.bf16_tile_table()):
-            sts, hss, dds = [], [], []
+            sts, hss, dds, rows = [], [], [], []
             if self.camera_batch:
                 for b in range(B):
                     with self._stream(b):
@@ -188,11 +218,12 @@ class StreamBatch:
                         dds.append(e._stage_inputs(datas[b]))
                         sts.append(e._camera_part(dds[b], pad_hw))
                     dd, st = dds[b], sts[b]
-                    M = e.static_adaptive_rows(dd["img"].shape[0])
-                    hss.append(e._head_prepare(st["tokens"], st["ref2d"], st["ctx"], M, dd, img_metas_list[b], st["m_dev"]))
+                    M, Mb, m_dev = e._head_rows(st, dd["img"].shape[0])      # static modes (_refusal): no sync
+                    rows.append(Mb)
+                    hss.append(e._head_prepare(st["tokens"], st["ref2d"], st["ctx"], M, dd, img_metas_list[b], m_dev))
             pick = lambda name: [getattr(hs, name) for hs in hss]
             outs_dec = e.decoder_streams(pick("X2"), pick("x0"), pick("qpos"), pick("tokens"), pick("ref"), sts[0]["hw"], sts[0]["starts"],
-                                         pick("lidar2img"), pad_hw, hss[0].A)
+                                         pick("lidar2img"), pad_hw, hss[0].A, holes=pick("hole"))
             if self.head_batch:
                 res = e._head_finish_streams(hss, outs_dec, self._stream)
             else:
@@ -203,7 +234,7 @@ class StreamBatch:
                         od = e._buf(("outs_dec",), (len(e.layers), hs.A, cfg["embed_dims"]), torch.float32)
                         od.copy_(outs_dec[b])
                         res.append(e._head_finish(hs, od))
-            for st, hs, outs in zip(sts, hss, res):
-                outs.update(fpn=st["raw"], depth_logit=st["depth_logit"], bbox2d=st["box2d"][:hs.M], bbox2d_scores=st["score2d"][:hs.M],
-                            sel_idx=st["sel_idx"], sel_cnt=st["sel_cnt"], proposal_overflow=st["overflow"])
+            for st, Mb, outs in zip(sts, rows, res):
+                e._head_outputs(outs, st, Mb)
+            self._overflow = [st["overflow"] for st in sts]
         return res

@@ -139,6 +139,26 @@ int far3d_aggregate_batched(const void* feat, int feat_dtype, const float* ref, 
                             const int32_t* level_hw, const int32_t* level_start, const float* pc_range,
                             float pad_h, float pad_w, int ldU, int ldOffs, void* stream);
 
+/* far3d_aggregate_batched with a HOLE of unused query rows per sample (the fixed-capacity threshold proposal mode and the multi-depth
+ * extra rows of several scene streams: streams.StreamBatch(hole_rows=True)).  The arguments are far3d_aggregate_batched's, then the hole
+ * in far3d_attention_streams' convention: hole_count NULL (no hole) or a DEVICE int32 array of B counts; sample b's rows
+ * [hole_start + hole_count[b], hole_end) hold no query; hole_start and hole_end are shared by all samples.  A count outside
+ * [0, hole_end - hole_start] is clamped into that range (far3d_proposal_gather never writes one).
+ * Contract: a hole row of out[b] is an exact zero row in either out_dt and none of its operands (ref / offsets / U rows, which may hold
+ * anything, NaN included) is read -- what the one-sample kernels do for a perm entry ~a.  Every other row has the bits
+ * far3d_aggregate_batched writes, so out[b] as a whole is BIT-IDENTICAL to far3d_aggregate_forward on sample b with
+ * perm = far3d_agg_order(..., hole_count[b], hole_start, hole_end); it does not depend on B or on the other samples' counts, and it is the
+ * same from run to run.  hole_count == NULL: exactly far3d_aggregate_batched (hole_start / hole_end are ignored).
+ * Refused with FAR3D_ERR_ARG, the hole named in far3d_last_error(), nothing launched: hole_count != NULL with hole_start < 0,
+ * hole_end > A or hole_start > hole_end.  Every other rule (B == 0 / A == 0: FAR3D_OK, the sizes) is far3d_aggregate_batched's: the two
+ * entries share one host path.  The count is one scalar load per workgroup, issued with the loads that do not depend on the query. */
+int far3d_aggregate_batched_holes(const void* feat, int feat_dtype, const float* ref, const float* offsets,
+                                  const float* lidar2img, const float* U, const float* Vc, const float* cam_tables,
+                                  void* out, int out_dt, int B, int A, int N, int S, int C, int G, int P, int L,
+                                  const int32_t* level_hw, const int32_t* level_start, const float* pc_range,
+                                  float pad_h, float pad_w, int ldU, int ldOffs, const int32_t* hole_count, int hole_start,
+                                  int hole_end, void* stream);
+
 /* Softmax factors of the aggregation logits' camera part, for `layers` decoder layers in one launch (block = layer):
  * Vc (layers, N, J) f32 (far3d_cam_embed_chain's output, J = L*P*G, J % 4 == 0) -> tables (layers, 2+N, J) f32 =
  * [ mV = max_n Vc | EV = sum_n eV[n] | eV[n] = exp(Vc[n] - mV) ].  softmax_{n,j}(U[a][j] + Vc[n][j]) (ref models/utils/
