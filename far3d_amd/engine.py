@@ -159,6 +159,10 @@ class _Lin:
         return ops.linear(x, self.pc, act=act, res=res, out=out, out_dtype=out_dtype)
 
 
+# the (rows, C) view the row-local kernels take of a (rows, C) operand (itself) or of B streams' (B, A, C) blocks
+_rows = lambda t: t if t.dim() == 2 else t.view(-1, t.shape[-1])
+
+
 def _with_tile_tables(fn):
     """Entry points that issue (or capture) convolutions run under the engine's own tile tables: ops.use_tile_tables is thread-local and
     restores the previous selection on exit, so engines with different settings -- and stand-alone ops -- can share a process."""
@@ -826,40 +830,71 @@ class Far3DEngine:
         return bool(self.agg_sorted and split is None and self.agg_variant in (0, 8) and A > 0 and
                     ops.aggregate_sorted_applies(N, cfg["num_pts"], cfg["num_levels"], S, C, tokens.element_size()))
 
+    def _decoder_buffers(self, buf, lead, Kt, A, N, **operands):
+        """The persistent buffers of one decoder pass, with `operands`, as one object: lead () for one stream (_decoder_setup), (B,)
+        for B streams (decoder_streams); buf(name, shape, dtype) hands a buffer out under the caller's keys (the layer outputs' key
+        is not of that scheme: they come in with the operands).  Kt: A + memory keys."""
+        cfg, rows = self.cfg, lead + (A,)
+        E, nL, at = cfg["embed_dims"], len(self.layers), self.prec["dec"]
+        nJ, nO = cfg["num_groups"] * cfg["num_levels"] * cfg["num_pts"], cfg["num_pts"] * 3
+        return SimpleNamespace(
+            nJ=nJ, nO=nO, QKV=buf("qkv", lead + (Kt, nL * 3 * E), at),  # per layer a [q | k | v] column block
+            XW=buf("xw", rows + (2 * E,), at),                           # [x1+pos | x1] operand of the logit / offset GEMM
+            UL=buf("ul", rows + (-(-(nJ + nO) // 64) * 64,), torch.float32),     # [U (nJ) | key-point offsets (nO)] per query
+            x1=buf("x1", rows + (E,), torch.float32), x2=buf("x2", rows + (E,), torch.float32),
+            x2b=buf("x2b", rows + (E,), at) if at == torch.bfloat16 else None,      # the bf16 copy the bf16 FFN reads
+            agg_out=buf("agg_out", rows + (E,), at), att_out=buf("att_out", rows + (E,), at),
+            tab=buf("agg_tab", (nL,) + lead + (2 + N, nJ), torch.float32), **operands)
+
+    def _decoder_prologue(self, X2, lidar2img, QKV, A):
+        """One stream's query-independent launches: the memory rows' K / V of all layers (one GEMM, X2[A:] -> QKV[A:]), the camera
+        term of the aggregation logits of all layers (one launch) -> (layers, N, nJ), bias included."""
+        if X2.shape[0] > A:
+            ops.linear(X2[A:], self.memkv, out=QKV[A:], out_dtype=self.prec["dec"])
+        return ops.cam_embed_chain(lidar2img, self.cam_chain)
+
+    def _in_projection(self, li, X2, QKV, A):
+        """Layer li's q / k / v of one stream's query rows: X2[:A] ([x+pos | x]) -> the layer's column block of QKV[:A]."""
+        E3 = 3 * self.cfg["embed_dims"]
+        ops.linear(X2[:A], self.layers[li]["qkv"], out=QKV[:A, li * E3:(li + 1) * E3], out_dtype=self.prec["dec"])
+
+    def _layer_after_attention(self, linear, ly, att, x, qpos, x1, xw, ul, out_rows=None):
+        """The unfused layer from the attention core to the aggregation, ONE copy for _decoder_layer (linear = ops.linear, (rows, .)
+        views) and decoder_streams (ops.linear_streams, (B, A, .) blocks): out-projection + residual x, LN0 -> x1 and
+        [x1 + pos | x1] -> xw (at the rows out_rows in the sorted mode), the logit / offset GEMM xw -> ul."""
+        E = x1.shape[-1]
+        y = linear(att, ly["out"], res=x)
+        ops.layernorm(_rows(y), *ly["norms"][0], out=_rows(x1), add=_rows(qpos), y2=_rows(xw)[:, :E], yb=_rows(xw)[:, E:], out_rows=out_rows)
+        linear(xw, ly["wl"], out=ul)
+
+    def _layer_after_aggregation(self, linear, ly, agg, x1, qpos, x2, x2b, dst, nxt):
+        """The unfused layer behind the aggregation, as _layer_after_attention: output projection + residual x1, LN1 -> x2 (x2b: its
+        bf16 copy, None in the fp32 decoder), FFN x + W2 relu(W1 x), hidden 1024 (SURVEY.md finding 4), LN2 -> dst and, with nxt, the
+        next in-projection's operand [dst + pos | dst] -> nxt."""
+        E = x1.shape[-1]
+        y = linear(agg, ly["oproj"], res=x1)
+        ops.layernorm(_rows(y), *ly["norms"][1], out=_rows(x2), yb=None if x2b is None else _rows(x2b))
+        hdn = linear(x2 if x2b is None else x2b, ly["ffn1"], act="relu", out_dtype=self.prec["dec"])
+        y = linear(hdn, ly["ffn2"], res=x2)
+        feed = {} if nxt is None else dict(add=_rows(qpos), y2=_rows(nxt)[:, :E], yb=_rows(nxt)[:, E:])
+        ops.layernorm(_rows(y), *ly["norms"][2], out=_rows(dst), **feed)
+
     def _decoder_setup(self, X2, x0, qpos, tokens, ref, hw, starts, lidar2img, pad_hw, A, hole, rows=None):
         """The decoder's per-frame working set (buffers, static operands, the aggregation's order and tables) as one object, and the
         query-independent launches.  rows None: the replicated run over all A queries; rows (a0, a1): a rank's share of the
         query-sharded run, which orders only its own rows and runs neither the sorted mode nor sibling workgroups."""
         cfg = self.cfg
-        E = cfg["embed_dims"]
-        nL = len(self.layers)
-        Kt = X2.shape[0]                      # A + memory keys
-        at = self.prec["dec"]
-        nJ = cfg["num_groups"] * cfg["num_levels"] * cfg["num_pts"]
-        nO = cfg["num_pts"] * 3
-        ws = SimpleNamespace(X2=X2, x0=x0, qpos=qpos, tokens=tokens, ref=ref, hw=hw, starts=starts, lidar2img=lidar2img, pad_hw=pad_hw, hole=hole,
-                             nJ=nJ, nO=nO, chains=self._row_chains(ly["rc"] for ly in self.layers), perm=None, inv=None, qbase=None, split=None)
-        ws.outs = self._buf(("outs_dec",), (nL, A, E), torch.float32)
-        ws.QKV = self._buf(("qkv",), (Kt, nL * 3 * E), at)          # per layer a [q | k | v] column block
-        ws.XW = self._buf(("xw",), (A, 2 * E), at)                   # [x+pos | x] operand of the cross-attention GEMM
-        ws.UL = self._buf(("ul",), (A, -(-(nJ + nO) // 64) * 64), torch.float32)    # [U (nJ) | key-point offsets (nO)] per query
-        ws.x1 = self._buf(("x1",), (A, E), torch.float32)
-        ws.x2 = self._buf(("x2",), (A, E), torch.float32)
-        ws.x2b = self._buf(("x2b",), (A, E), at) if at == torch.bfloat16 else None
-        ws.agg_out = self._buf(("agg_out",), (A, E), at)
-        ws.att_out = self._buf(("att_out",), (A, E), at)
-        # query-independent work first: the memory rows' K/V of all layers (one GEMM) and the camera term of the
-        # aggregation logits of all layers (one launch)
-        if Kt > A:
-            ops.linear(X2[A:], self.memkv, out=ws.QKV[A:], out_dtype=at)
-        ws.vc_all = ops.cam_embed_chain(lidar2img, self.cam_chain)             # (layers, N, nJ), bias included
-        tab = self._buf(("agg_tab",), (nL, 2 + ws.vc_all.shape[1], nJ), torch.float32)
+        ws = self._decoder_buffers(lambda name, shape, dt: self._buf((name,), shape, dt), (), X2.shape[0], A, lidar2img.shape[0],
+                                   X2=X2, x0=x0, qpos=qpos, tokens=tokens, ref=ref, hw=hw, starts=starts, lidar2img=lidar2img, pad_hw=pad_hw,
+                                   hole=hole, chains=self._row_chains(ly["rc"] for ly in self.layers), perm=None, inv=None, qbase=None, split=None,
+                                   outs=self._buf(("outs_dec",), (len(self.layers), A, cfg["embed_dims"]), torch.float32))
+        ws.vc_all = self._decoder_prologue(X2, lidar2img, ws.QKV, A)
         if rows is not None:
             # a rank's share: the order of its own rows (absolute row indices; nothing to order for a rank without rows) and the tables
             if rows[1] > rows[0]:
                 ws.perm = ops.aggregation_order(ref, lidar2img, cfg["pc_range"], pad_hw, out=self._buf(("perm_qs",), (rows[1] - rows[0],), torch.int32),
                                                 hole=hole, rows=rows)
-            ws.tabs = ops.agg_tables(ws.vc_all, out=tab)
+            ws.tabs = ops.agg_tables(ws.vc_all, out=ws.tab)
             return ws
         # per-frame preparations of the aggregation in ONE launch: reference points are fixed across the layers -> one camera-sorted
         # workgroup order (scheduling only); the camera factors of the factored softmax for all layers (include/far3d_hip.h)
@@ -875,7 +910,7 @@ class Far3DEngine:
             srt = (self._buf(("agg_inv",), (A,), torch.int32), self._buf(("agg_qbase",), (A, 4), torch.float32))
             ws.inv, ws.qbase = srt
         res = ops.aggregation_order(ref, lidar2img, cfg["pc_range"], pad_hw, out=self._buf(("perm",), (A + (sp.extra if sp else 0),), torch.int32),
-                                    hole=hole, Vc=ws.vc_all, tables_out=tab, split=sp, sorted_operands=srt)
+                                    hole=hole, Vc=ws.vc_all, tables_out=ws.tab, split=sp, sorted_operands=srt)
         ws.perm, ws.tabs = res[0], res[1]
         return ws
 
@@ -884,18 +919,17 @@ class Far3DEngine:
         layer's q / k / v): attention, out-projection, aggregation, FFN, the three LayerNorms; the post-LN2 rows go to dst
         ((a1 - a0, E) f32).  Every kernel here works row by row and gives a row the same bits whatever rows the launch covers, which
         is what makes ONE body valid for the whole range (the replicated run) and for any rank's share of it.
-        Two forms.  Unfused: 10 launches (11 with the in-projection the caller issues).  Row chains (ws.chains, csrc/rowchain.hip):
-        the attention core, far3d_rowchain_attn_out (out-projection + residual + LN0 + the aggregation's logit / offset linears),
-        the aggregation kernel, far3d_rowchain_ffn (output projection + residual + LN1 + FFN + LN2) -- 4 launches; same operands
-        and arithmetic as the unfused form (bf16 operands, fp32 accumulation and LayerNorms), a different K order inside the GEMMs.
+        Two forms.  Unfused (_layer_after_attention, _layer_after_aggregation -- the halves decoder_streams runs too): 10 launches
+        (11 with the in-projection the caller issues).  Row chains (ws.chains, csrc/rowchain.hip): the attention core,
+        far3d_rowchain_attn_out (out-projection + residual + LN0 + the aggregation's logit / offset linears), the aggregation kernel,
+        far3d_rowchain_ffn (output projection + residual + LN1 + FFN + LN2) -- 4 launches; same operands and arithmetic as the
+        unfused form (bf16 operands, fp32 accumulation and LayerNorms), a different K order inside the GEMMs.
         feed_next (the replicated run): the last launch also writes the next layer's operand for these rows -- unfused [x + pos | x]
         into ws.X2, with the chains the NEXT layer's q / k / v into ws.QKV (nothing after the last layer).  Without it (a rank's
         share, dst = its send buffer) nothing but dst is written: the next operand is built from the exchanged rows."""
         cfg, ly = self.cfg, self.layers[li]
-        E, at = cfg["embed_dims"], self.prec["dec"]
-        nJ, nO = ws.nJ, ws.nO
-        c0 = li * 3 * E
-        r = slice(a0, a1)
+        E, nJ, nO = cfg["embed_dims"], ws.nJ, ws.nO
+        c0, r = li * 3 * E, slice(a0, a1)
         x = (ws.x0 if li == 0 else ws.outs[li - 1])[r]
         qpos, x1, att = ws.qpos[r], ws.x1[r], ws.att_out[r]
         # self-attention: q = x+pos, k = cat[x,mem]+cat[pos,mempos], v = cat[x,mem] (detr3d_transformer.py:378-396)
@@ -906,9 +940,7 @@ class Far3DEngine:
         if ws.chains:
             ops.rowchain_attn_out(att, x, qpos, ly["rc"], x1, ws.UL[r], ul_rows=ws.inv)
         else:
-            y = ops.linear(att, ly["out"], res=x)
-            ops.layernorm(y, *ly["norms"][0], out=x1, add=qpos, y2=ws.XW[r, :E], yb=ws.XW[r, E:], out_rows=ws.inv)
-            ops.linear(ws.XW[r], ly["wl"], out=ws.UL[r, :nJ + nO])
+            self._layer_after_attention(ops.linear, ly, att, x, qpos, x1, ws.XW[r], ws.UL[r, :nJ + nO], out_rows=ws.inv)
         # cross-attention: fused perspective-aware aggregation (detr3d_transformer.py:522-569) of the rows ws.perm lists, on the
         # full-size buffers
         U, off = ws.UL[:, :nJ], ws.UL[:, nJ:nJ + nO]
@@ -922,14 +954,8 @@ class Far3DEngine:
             ops.rowchain_ffn(agg, x1, qpos, ly["rc"], dst, nxt=self.layers[li + 1]["rc"] if feed else None,
                              qkv=ws.QKV[r, c0 + 3 * E:c0 + 6 * E] if feed else None)
         else:
-            x2, x2b = ws.x2[r], (ws.x2b[r] if ws.x2b is not None else None)          # x2b: the bf16 copy the bf16 FFN reads
-            y = ops.linear(agg, ly["oproj"], res=x1)
-            ops.layernorm(y, *ly["norms"][1], out=x2, yb=x2b)
-            # FFN: x + W2 relu(W1 x), hidden 1024 (SURVEY.md finding 4)
-            hdn = ops.linear(x2 if x2b is None else x2b, ly["ffn1"], act="relu", out_dtype=at)
-            y = ops.linear(hdn, ly["ffn2"], res=x2)
-            nxt = dict(add=qpos, y2=ws.X2[r, :E], yb=ws.X2[r, E:]) if feed_next else {}
-            ops.layernorm(y, *ly["norms"][2], out=dst, **nxt)
+            self._layer_after_aggregation(ops.linear, ly, agg, x1, qpos, ws.x2[r], None if ws.x2b is None else ws.x2b[r], dst,
+                                          ws.X2[r] if feed_next else None)
 
     def decoder(self, X2, x0, qpos, tokens, ref, hw, starts, lidar2img, pad_hw, A, hole=None, qshard=None):
         """X2 (A+Km, 2E) `dec` dtype: rows [:A] = [tgt+pos | tgt] of the queries, rows [A:] = [mem+mempos | mem] of the memory
@@ -938,12 +964,11 @@ class Far3DEngine:
         if qshard is not None:
             return self.decoder_query_sharded(X2, x0, qpos, tokens, ref, hw, starts, lidar2img, pad_hw, A, hole, qshard)
         ws = self._decoder_setup(X2, x0, qpos, tokens, ref, hw, starts, lidar2img, pad_hw, A, hole)
-        E = self.cfg["embed_dims"]
-        for li, ly in enumerate(self.layers):
+        for li in range(len(self.layers)):
             # the in-projection is a GEMM launch of its own for layer 0 only with the row chains (the FFN chain of layer li - 1 wrote
             # this layer's q / k / v), for every layer without them
             if li == 0 or not ws.chains:
-                ops.linear(X2[:A], ly["qkv"], out=ws.QKV[:A, li * 3 * E:(li + 1) * 3 * E], out_dtype=self.prec["dec"])
+                self._in_projection(li, X2, ws.QKV, A)
             self._decoder_layer(ws, li, 0, A, ws.outs[li], True)
         return ws.outs
 
@@ -973,7 +998,7 @@ class Far3DEngine:
             if ws.chains and li > 0:
                 ops.rowchain_qkv(ws.outs[li - 1], qpos, ly["rc"], ws.QKV[:A, c0:c0 + 3 * E])
             else:
-                ops.linear(X2[:A], ly["qkv"], out=ws.QKV[:A, c0:c0 + 3 * E], out_dtype=at)
+                self._in_projection(li, X2, ws.QKV, A)
             if nr > 0:
                 self._decoder_layer(ws, li, a0, a1, gsrc[:nr], False)
             qs.gather(gsrc, gdst)                                       # the layer's ONE exchange (never captured into a graph)
@@ -993,23 +1018,18 @@ class Far3DEngine:
         fixed-capacity threshold mode and the multi-depth extra rows), all None or none, start / end the same in every stream.  The
         B counts are gathered into ONE (B,) buffer of the pass -- B small device copies, no sync -- which every layer's
         far3d_attention_streams and far3d_aggregate_batched_holes launch reads.
-        Per layer ONE far3d_attention_streams launch, ONE far3d_aggregate_batched launch, and every row-local launch (out-projection,
-        the three LayerNorms, logit / offset linear, output projection, FFN) once over all B * A rows of (B, A, .) working buffers.
-        The GEMMs go through ops.linear_streams, which takes its tile from ONE stream's row count, so a tile table keyed on rows
-        cannot choose another K order; the LayerNorms, the attention and the aggregation give a row the same bits whatever rows the
-        launch covers (_decoder_layer).  Per stream stay: the launches that read the caller's own buffers (layer 0's in-projection
-        and the memory rows' K / V GEMM from X2[b]), cam_embed_chain, and small copies of x0 / qpos / ref / lidar2img into the
-        batched buffers.  The value maps are not copied when tokens[b] are the slices of one (B, N, S, 256) allocation
-        (_token_buffer); otherwise they are stacked."""
+        Per layer ONE far3d_attention_streams launch, ONE far3d_aggregate_batched launch, and the halves of _decoder_layer's unfused
+        form (_layer_after_attention, _layer_after_aggregation) once over all B * A rows of _decoder_buffers' (B, A, .) set.  Their
+        GEMMs go through ops.linear_streams, which takes its tile from ONE stream's row count, so a tile table keyed on rows cannot
+        choose another K order; every other kernel gives a row the same bits whatever rows the launch covers (_decoder_layer).  Per
+        stream stay _decoder_prologue and layer 0's in-projection (they read the caller's X2[b]) and small copies of x0 / qpos / ref /
+        lidar2img.  The value maps are read in place when tokens[b] are the slices of one (B, N, S, 256) allocation (_token_buffer)."""
         cfg = self.cfg
         B, E, nL, at = len(X2), cfg["embed_dims"], len(self.layers), self.prec["dec"]
-        Kt = X2[0].shape[0]
+        Kt, N = X2[0].shape[0], lidar2img[0].shape[0]
         if any(tuple(x.shape) != (Kt, 2 * E) for x in X2) or any(tuple(t.shape) != tuple(tokens[0].shape) for t in tokens) or \
                 not (len(x0) == len(qpos) == len(tokens) == len(ref) == len(lidar2img) == B):
             raise ValueError("decoder_streams: every stream needs operands of the same shapes (one X2, x0, qpos, tokens, ref, lidar2img each)")
-        nJ = cfg["num_groups"] * cfg["num_levels"] * cfg["num_pts"]
-        nO = cfg["num_pts"] * 3
-        N = lidar2img[0].shape[0]
         buf = lambda name, shape, dt: self._buf(("ds_" + name, B), shape, dt)
         hole = None
         if holes is not None and any(h is not None for h in holes):
@@ -1022,18 +1042,12 @@ class Far3DEngine:
             for b, h in enumerate(holes):
                 cnt[b:b + 1].copy_(h[0].view(-1)[:1])
             hole = (cnt, int(holes[0][1]), int(holes[0][2]))
-        outs = buf("outs", (nL, B, A, E), torch.float32)
-        QKV = buf("qkv", (B, Kt, nL * 3 * E), at)                  # per stream and layer a [q | k | v] column block
-        XW = buf("xw", (B, A, 2 * E), at)                          # [x1+pos | x1] operand of the logit / offset GEMM
+        ws = self._decoder_buffers(buf, (B,), Kt, A, N, outs=buf("outs", (nL, B, A, E), torch.float32))
+        nJ, nO, QKV, UL, outs = ws.nJ, ws.nO, ws.QKV, ws.UL, ws.outs
         XN = buf("xn", (B, A, 2 * E), at)                          # [x+pos | x] operand of the next layer's in-projection
-        UL = buf("ul", (B, A, -(-(nJ + nO) // 64) * 64), torch.float32)
         X0, QP = buf("x0", (B, A, E), torch.float32), buf("qpos", (B, A, E), torch.float32)
-        x1, x2 = buf("x1", (B, A, E), torch.float32), buf("x2", (B, A, E), torch.float32)
-        x2b = buf("x2b", (B, A, E), at) if at == torch.bfloat16 else None
-        agg_out, att = buf("agg_out", (B, A, E), at), buf("att_out", (B, A, E), at)
         REF, L2I = buf("ref", (B, A, 3), torch.float32), buf("l2i", (B, N, 4, 4), torch.float32)
         VC = buf("vc", (nL, B, N, nJ), torch.float32)              # camera term of the aggregation logits, bias included
-        TAB = buf("agg_tab", (nL, B, 2 + N, nJ), torch.float32)
         t0 = tokens[0]
         if all(t.is_contiguous() and t.dtype == t0.dtype and t.data_ptr() == t0.data_ptr() + b * t0.numel() * t0.element_size()
                for b, t in enumerate(tokens)):
@@ -1042,33 +1056,22 @@ class Far3DEngine:
             tok = torch.stack(list(tokens))
         for b in range(B):
             X0[b].copy_(x0[b]); QP[b].copy_(qpos[b]); REF[b].copy_(ref[b]); L2I[b].copy_(lidar2img[b])
-            if Kt > A:
-                ops.linear(X2[b][A:], self.memkv, out=QKV[b, A:], out_dtype=at)
-            VC[:, b].copy_(ops.cam_embed_chain(lidar2img[b], self.cam_chain))
-            ops.linear(X2[b][:A], self.layers[0]["qkv"], out=QKV[b, :A, :3 * E], out_dtype=at)
+            VC[:, b].copy_(self._decoder_prologue(X2[b], lidar2img[b], QKV[b], A))
+            self._in_projection(0, X2[b], QKV[b], A)
         # the same table pass as far3d_agg_order's (agg_tables_body): the bits of the one-stream decoder's tables, where its kernel reads them
         tabs = ops.aggregate_kernel8_applies(N, cfg["num_pts"], cfg["num_levels"], tok.shape[2], tok.shape[3], tok.element_size())
         if tabs:
-            ops.agg_tables(VC.view(nL * B, N, nJ), out=TAB.view(nL * B, 2 + N, nJ))
-        flat = lambda t: t.view(B * A, t.shape[2])
+            ops.agg_tables(VC.view(nL * B, N, nJ), out=ws.tab.view(nL * B, 2 + N, nJ))
         for li, ly in enumerate(self.layers):
             c0 = li * 3 * E
             if li > 0:
                 ops.linear_streams(XN, ly["qkv"], out=QKV[:, :A, c0:c0 + 3 * E])
-            x = X0 if li == 0 else outs[li - 1]
             ops.attention_streams(QKV[:, :A, c0:c0 + E], QKV[:, :, c0 + E:c0 + 2 * E], QKV[:, :, c0 + 2 * E:c0 + 3 * E],
-                                  num_heads=cfg["num_heads"], out=att, hole=hole)
-            y = ops.linear_streams(att, ly["out"], res=x)
-            ops.layernorm(flat(y), *ly["norms"][0], out=flat(x1), add=flat(QP), y2=flat(XW)[:, :E], yb=flat(XW)[:, E:])
-            ops.linear_streams(XW, ly["wl"], out=UL[:, :, :nJ + nO])
+                                  num_heads=cfg["num_heads"], out=ws.att_out, hole=hole)
+            self._layer_after_attention(ops.linear_streams, ly, ws.att_out, X0 if li == 0 else outs[li - 1], QP, ws.x1, ws.XW, UL[:, :, :nJ + nO])
             ops.aggregate_batched(tok, REF, UL[:, :, nJ:nJ + nO], L2I, UL[:, :, :nJ], VC[li], hw, starts, cfg["pc_range"], pad_hw,
-                                  num_groups=cfg["num_groups"], out=agg_out, tables=TAB[li] if tabs else None, hole=hole)
-            y = ops.linear_streams(agg_out, ly["oproj"], res=x1)
-            ops.layernorm(flat(y), *ly["norms"][1], out=flat(x2), yb=None if x2b is None else flat(x2b))
-            hdn = ops.linear_streams(x2 if x2b is None else x2b, ly["ffn1"], act="relu", out_dtype=at)
-            y = ops.linear_streams(hdn, ly["ffn2"], res=x2)
-            nxt = dict(add=flat(QP), y2=flat(XN)[:, :E], yb=flat(XN)[:, E:]) if li + 1 < nL else {}
-            ops.layernorm(flat(y), *ly["norms"][2], out=flat(outs[li]), **nxt)
+                                  num_groups=cfg["num_groups"], out=ws.agg_out, tables=ws.tab[li] if tabs else None, hole=hole)
+            self._layer_after_aggregation(ops.linear_streams, ly, ws.agg_out, ws.x1, QP, ws.x2, ws.x2b, outs[li], XN if li + 1 < nL else None)
         return outs.permute(1, 0, 2, 3)
 
     # ------------------------------------------------------------------------------------------ one frame
@@ -1242,7 +1245,7 @@ class Far3DEngine:
         """The part of head_stage in front of the decoder (a6): scene change, memory pre-update, temporal codes, the query-major
         state buffers -> the decoder's operands and what _head_finish needs, as one object."""
         cfg = self.cfg
-        E = cfg["embed_dims"]
+        E, at = cfg["embed_dims"], self.prec["dec"]
         lidar2img = dd["lidar2img"][0]
         # ---- scene change / memory (detectors/far3d.py:252-257): the persistent buffers are zeroed IN PLACE
         fresh = img_metas[0]["scene_token"] != self.prev_scene or not self._mem_valid
@@ -1253,8 +1256,6 @@ class Far3DEngine:
             self._mem_valid = True
         P_, Lm, nq = cfg["num_propagated"], cfg["memory_len"], cfg["num_query"]
         A, Kt = nq + M + P_, nq + M + Lm
-        at = self.prec["dec"]
-        fast = at == torch.bfloat16
         # query-major state buffers: rows [0,nq) learned queries (constant), [nq,nq+M) adaptive queries, then the Lm memory
         # slots, whose first P_ are the propagated queries and whose rest are the extra self-attention keys
         # (farhead.py:305-311) -- so tgt = TQ[:A], memory = TQ[A:], with no concatenation copies
@@ -1285,64 +1286,65 @@ class Far3DEngine:
         return SimpleNamespace(X2=X2, x0=TQ[:A], qpos=QP[:A], ref=RF[:A], tokens=tokens, lidar2img=lidar2img, A=A, M=M, m=m, m_dev=m_dev,
                                hole=hole, dd=dd)
 
+    def _head_operand(self, outs_dec):
+        """nan_to_num of the decoder's contiguous f32 outputs, in place -> the heads' (rows, E) operand (bf16 decoder: the bf16 copy)."""
+        flat = outs_dec.view(-1, outs_dec.shape[-1])
+        flatb = ops.nan_to_num_(flat, bf16_copy=self.prec["dec"] == torch.bfloat16)
+        return flat if flatb is None else flatb
+
+    def _head_branches(self, linear, hin, cls_out=None):
+        """The unfused cls branch (linear, LN + relu, linear, LN + relu, linear) and reg branch (three linears), ONE copy for _head_finish
+        (ops.linear, hin (rows, E)) and _head_finish_streams (ops.linear_streams, hin (B, rows, E)) -> (logits, in cls_out if given; box codes)."""
+        at, fast = self.prec["dec"], self.prec["dec"] == torch.bfloat16
+        def ln_relu(t, ln):
+            r = ops.layernorm(_rows(t), *ln, act="relu", bf16_copy=fast)
+            return (r[1] if fast else r).view(t.shape)
+        h = ln_relu(linear(hin, self.cls_b[0].pc), self.cls_ln[0])
+        h = ln_relu(linear(h, self.cls_b[1].pc), self.cls_ln[1])
+        cls = linear(h, self.cls_b[2].pc, out=cls_out)
+        rr = linear(hin, self.reg_b[0].pc, act="relu", out_dtype=at)
+        return cls, linear(linear(rr, self.reg_b[1].pc, act="relu", out_dtype=at), self.reg_b[2].pc)
+
+    @staticmethod
+    def _head_result(hs, all_cls, all_box, outs_dec, idx, result):
+        """One stream's `outs` of the head (hs: its _head_prepare result)."""
+        return dict(all_cls_scores=all_cls, all_bbox_preds=all_box, outs_dec=outs_dec, num_adaptive=hs.M, num_adaptive_dev=hs.m_dev,
+                    feat_flatten=hs.tokens, reference_points=hs.ref, memory_topk=idx, result=result)
+
     def _head_finish(self, hs, outs_dec):
-        """The part of head_stage behind the decoder: the shared cls / reg heads over all layers, finalize, decode, the memory's
-        post-update.  hs: _head_prepare's result; outs_dec (layers, A, E) f32, contiguous."""
-        cfg = self.cfg
-        E, at = cfg["embed_dims"], self.prec["dec"]
-        fast = at == torch.bfloat16
-        A, M, m, m_dev, hole, ref, tokens, dd = hs.A, hs.M, hs.m, hs.m_dev, hs.hole, hs.ref, hs.tokens, hs.dd
-        # ---- a10: shared heads over all layers at once (farhead.py:646-664)
-        flat = outs_dec.view(-1, E)
-        flatb = ops.nan_to_num_(flat, bf16_copy=fast)
-        hin = flatb if fast else flat
-        nl = cfg["num_layers"]
+        """The part of head_stage behind the decoder: the shared cls / reg heads over all layers (_head_branches, or the row chain),
+        finalize, decode, the memory's post-update.  hs: _head_prepare's result; outs_dec (layers, A, E) f32, contiguous."""
+        cfg, A, nl = self.cfg, hs.A, self.cfg["num_layers"]
+        hin = self._head_operand(outs_dec)          # ---- a10: shared heads over all layers at once (farhead.py:646-664)
         if self._row_chains([self.branch_rc]):      # both branches in one row-resident launch (csrc/rowchain.hip)
             cls_flat = self._buf(("cls_flat",), (nl * A, cfg["num_classes"]), torch.float32)
             rr = self._buf(("reg_flat",), (nl * A, cfg["code_size"]), torch.float32)
             ops.rowchain_branches(hin, self.branch_rc, cls_flat, rr)
-            all_cls = cls_flat.view(nl, 1, A, cfg["num_classes"])
         else:
-            r1 = ops.layernorm(self.cls_b[0](hin), *self.cls_ln[0], act="relu", bf16_copy=fast)
-            r2 = ops.layernorm(self.cls_b[1](r1[1] if fast else r1), *self.cls_ln[1], act="relu", bf16_copy=fast)
-            all_cls = self.cls_b[2](r2[1] if fast else r2).view(nl, 1, A, cfg["num_classes"])
-            rr = self.reg_b[2](self.reg_b[1](self.reg_b[0](hin, act="relu", out_dtype=at), act="relu", out_dtype=at))
-        box_flat, sc = ops.head_finalize(rr, ref, all_cls, cfg["pc_range"], nl, cfg["num_classes"], hole=hole)
+            cls_flat, rr = self._head_branches(ops.linear, hin)
+        all_cls = cls_flat.view(nl, 1, A, cfg["num_classes"])
+        box_flat, sc = ops.head_finalize(rr, hs.ref, all_cls, cfg["pc_range"], nl, cfg["num_classes"], hole=hs.hole)
         all_box = box_flat.view(nl, 1, A, cfg["code_size"])
         # ---- a11: memory post-update (farhead.py:479-508): top-k by max-class score, push, truncate, ego warp -- in place
         # (the top-k rides in the decode's launch as a second workgroup: far3d_decode_topk_mem -- both rank the last layer's outputs)
         result, idx = self.decode(all_cls, all_box, mem_scores=sc, mem_K=cfg["topk_proposals"])
-        ops.memory_post_update(m, idx, outs_dec[-1], all_box[-1][0], dd["ego_pose"], dd["timestamp"], self.mem)
-        outs = dict(all_cls_scores=all_cls, all_bbox_preds=all_box, outs_dec=outs_dec, num_adaptive=M, num_adaptive_dev=m_dev,
-                    feat_flatten=tokens, reference_points=ref, memory_topk=idx)
-        outs["result"] = result
-        return outs
+        ops.memory_post_update(hs.m, idx, outs_dec[-1], all_box[-1][0], hs.dd["ego_pose"], hs.dd["timestamp"], self.mem)
+        return self._head_result(hs, all_cls, all_box, outs_dec, idx, result)
 
     def _head_finish_streams(self, hss, outs_dec, enter):
         """_head_finish for B scene streams (streams.StreamBatch): hss the B _head_prepare results, outs_dec decoder_streams' result
         (B, layers, A, E), enter(b) a context manager that makes the engine stream b (its buffer set and streaming memory).  Returns the
         B result dicts of _head_finish, bit for bit.  The row-local work runs once over all streams' rows on (B, layers * A, .)
-        buffers: ONE gathering copy of the decoder's (layers, B, A, E) rows into stream-major order, nan_to_num, the cls / reg branches
-        through ops.linear_streams (the tile of ONE stream's layers * A rows) and ops.layernorm (row-local); the decode and the
-        memory update's top-k of all streams are ONE far3d_decode_topk_mem_streams launch.  Per stream stay head_finalize and
-        memory_post_update.  The unfused branches only (StreamBatch refuses fused_rows)."""
+        buffers: ONE gathering copy of the decoder's (layers, B, A, E) rows into stream-major order, nan_to_num, _head_finish's own
+        unfused cls / reg branches (_head_branches; StreamBatch refuses fused_rows) through ops.linear_streams (the tile of ONE stream's
+        layers * A rows); the decode and the memory update's top-k of all streams are ONE far3d_decode_topk_mem_streams launch.  Per
+        stream stay head_finalize and memory_post_update."""
         cfg = self.cfg
-        E, at, nl, ncls, code = cfg["embed_dims"], self.prec["dec"], cfg["num_layers"], cfg["num_classes"], cfg["code_size"]
-        fast = at == torch.bfloat16
+        E, nl, ncls, code = cfg["embed_dims"], cfg["num_layers"], cfg["num_classes"], cfg["code_size"]
         B, A = len(hss), hss[0].A
         buf = lambda name, shape, dt: self._buf(("hs_" + name, B), shape, dt)
-        OD = buf("outs_dec", (B, nl, A, E), torch.float32)
-        OD.copy_(outs_dec)
-        flat = OD.view(-1, E)
-        flatb = ops.nan_to_num_(flat, bf16_copy=fast)
-        hin = (flatb if fast else flat).view(B, nl * A, E)
-        rows = lambda t: t.view(B * nl * A, t.shape[2])
-        blocks = lambda t: t.view(B, nl * A, t.shape[1])
-        r1 = ops.layernorm(rows(ops.linear_streams(hin, self.cls_b[0].pc)), *self.cls_ln[0], act="relu", bf16_copy=fast)
-        r2 = ops.layernorm(rows(ops.linear_streams(blocks(r1[1] if fast else r1), self.cls_b[1].pc)), *self.cls_ln[1], act="relu", bf16_copy=fast)
-        CLS = ops.linear_streams(blocks(r2[1] if fast else r2), self.cls_b[2].pc, out=buf("cls", (B, nl * A, ncls), torch.float32))
-        rr = ops.linear_streams(hin, self.reg_b[0].pc, act="relu", out_dtype=at)
-        rr = ops.linear_streams(ops.linear_streams(rr, self.reg_b[1].pc, act="relu", out_dtype=at), self.reg_b[2].pc)
+        OD = buf("outs_dec", (B, nl, A, E), torch.float32).copy_(outs_dec)
+        CLS, rr = self._head_branches(ops.linear_streams, self._head_operand(OD).view(B, nl * A, E), cls_out=buf("cls", (B, nl * A, ncls), torch.float32))
         BOX, SC = buf("box", (B, nl * A, code), torch.float32), buf("score", (B, A), torch.float32)
         for b, hs in enumerate(hss):
             ops.head_finalize(rr[b], hs.ref, CLS[b], cfg["pc_range"], nl, ncls, hole=hs.hole, out=(BOX[b], SC[b]))
@@ -1352,10 +1354,7 @@ class Far3DEngine:
             all_cls, all_box = CLS[b].view(nl, 1, A, ncls), BOX[b].view(nl, 1, A, code)
             with enter(b):
                 ops.memory_post_update(hs.m, idx[b], OD[b, -1], all_box[-1][0], hs.dd["ego_pose"], hs.dd["timestamp"], self.mem)
-            outs = dict(all_cls_scores=all_cls, all_bbox_preds=all_box, outs_dec=OD[b], num_adaptive=hs.M, num_adaptive_dev=hs.m_dev,
-                        feat_flatten=hs.tokens, reference_points=hs.ref, memory_topk=idx[b])
-            outs["result"] = {k: v[b] for k, v in results.items()}
-            res.append(outs)
+            res.append(self._head_result(hs, all_cls, all_box, OD[b], idx[b], {k: v[b] for k, v in results.items()}))
         return res
 
     def decode_streams(self, cls_last, box_last, mem_scores, mem_K):
