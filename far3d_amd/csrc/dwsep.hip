@@ -12,12 +12,11 @@
 // next chunk's global loads are in flight during the depthwise arithmetic.  A lane ends up with 4 consecutive output channels of its pixel
 // per accumulator quad -> 8-byte stores (pair: 8 bytes of hi + 8 of lo).
 //
-// Depthwise half: the nine pinned fmaf of dwconv3x3_kernel in its tap order (padding taps as x = 0), one fp32 add of the bias (none when
-// b1 is NULL), the activation, then the rounding of DwIo<T>::st -- bf16 round-to-nearest-even, or hi = bf16(v), lo = bf16(v - hi) -- so
-// the MFMA operand holds bit for bit what far3d_dwconv3x3_act_nhwc stores.  Pair storage: the three products hi.hi, hi.lo, lo.hi of the
-// split kernels.  Restated here rather than shared through a header: dwconv.hip stays byte for byte what its bitwise tests pinned.
-#include "common.hpp"
-#include "far3d_hip.h"
+// Depthwise half: the arithmetic contract of dw_core.hpp -- the nine pinned fmaf in its tap order (padding taps as x = 0), one fp32 add of
+// the bias (none when b1 is NULL), DW_ACT, then DwIo<T>::pack, the rounding of the window kernel's store -- so the MFMA operand holds bit
+// for bit what far3d_dwconv3x3_act_nhwc stores.  Pair storage: the three products hi.hi, hi.lo, lo.hi of the split kernels.  The vector
+// load, the activation and the rounding are dw_core.hpp's; the tap chain is written out here as in dwconv.hip.
+#include "dw_core.hpp"
 
 namespace {
 
@@ -31,23 +30,6 @@ constexpr int DS_BK = 32;                                                 // cha
 template <typename T> struct DsT;
 template <> struct DsT<bf16_t> { static constexpr int CS = 1, ROW = DS_BK + 8; };          // LDS row: 32 bf16 + 16 B pad
 template <> struct DsT<pair_t> { static constexpr int CS = 2, ROW = 2 * DS_BK + 8; };      // [32 hi | 32 lo] + 16 B pad
-
-__device__ __forceinline__ void ds_unpack8(const uint4& r, float* v) {
-  v[0] = __uint_as_float(r.x << 16); v[1] = __uint_as_float(r.x & 0xffff0000u);
-  v[2] = __uint_as_float(r.y << 16); v[3] = __uint_as_float(r.y & 0xffff0000u);
-  v[4] = __uint_as_float(r.z << 16); v[5] = __uint_as_float(r.z & 0xffff0000u);
-  v[6] = __uint_as_float(r.w << 16); v[7] = __uint_as_float(r.w & 0xffff0000u);
-}
-// p -> 8 channels of one pixel (pair: their hi halves, the lo halves 32 elements on; hi + lo is exact)
-template <typename T> __device__ __forceinline__ void ds_ld8(const T* p, float* v) {
-  ds_unpack8(*reinterpret_cast<const uint4*>(p), v);
-  if constexpr (DsT<T>::CS == 2) {
-    float lo[8];
-    ds_unpack8(*reinterpret_cast<const uint4*>(p + 32), lo);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] += lo[j];
-  }
-}
 
 __device__ __forceinline__ void ds_mma(ds_f32x16_t& acc, const ds_u32x4_t& a, const ds_u32x4_t& b) {
   acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(ds_bf16x8_t, a), __builtin_bit_cast(ds_bf16x8_t, b), acc, 0, 0, 0);
@@ -130,7 +112,7 @@ __global__ __launch_bounds__(DS_THREADS) void dwsep_kernel(const T* __restrict__
       for (int t = 0; t < 9; ++t) {
         float xv[8];
         if (tvm & (1u << t)) {
-          ds_ld8<T>(xw + ((long)(t / 3) * W + (t % 3)) * ldx + chan_off<T>(c), xv);
+          DwIo<T>::ld(xw + ((long)(t / 3) * W + (t % 3)) * ldx + chan_off<T>(c), xv);
         } else {
 #pragma unroll
           for (int j = 0; j < 8; ++j) xv[j] = 0.f;
@@ -146,20 +128,15 @@ __global__ __launch_bounds__(DS_THREADS) void dwsep_kernel(const T* __restrict__
         s[4] = s[4] + q1.x; s[5] = s[5] + q1.y; s[6] = s[6] + q1.z; s[7] = s[7] + q1.w;
       }
 #pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        if (act1 == 1) s[j] = fmaxf(s[j], 0.f);
-        else if (act1 == 2) s[j] = swish_f32(s[j]);
-      }
-      // round to storage as DwIo<T>::st does: the MFMA operand is what the two-launch path writes to its scratch map
+      for (int j = 0; j < 8; ++j) { DW_ACT(s[j], act1); }
+      // round to storage with the statement of DwIo<T>::st: the MFMA operand is what the two-launch path writes to its scratch map
+      const typename DwIo<T>::Raw q = DwIo<T>::pack(s);
       ds_u32x4_t bh, bl;
       if constexpr (CS == 2) {
-        uint2 h0, l0, h1, l1;
-        split4f(s[0], s[1], s[2], s[3], h0, l0);
-        split4f(s[4], s[5], s[6], s[7], h1, l1);
-        bh = ds_u32x4_t{h0.x, h0.y, h1.x, h1.y};
-        bl = ds_u32x4_t{l0.x, l0.y, l1.x, l1.y};
+        bh = ds_u32x4_t{q.h.x, q.h.y, q.h.z, q.h.w};
+        bl = ds_u32x4_t{q.l.x, q.l.y, q.l.z, q.l.w};
       } else {
-        bh = ds_u32x4_t{pack_bf16x2(s[0], s[1]), pack_bf16x2(s[2], s[3]), pack_bf16x2(s[4], s[5]), pack_bf16x2(s[6], s[7])};
+        bh = ds_u32x4_t{q.a.x, q.a.y, q.a.z, q.a.w};
       }
       const bf16_t* arow = lds + r * ROW + kk * 16 + h * 8;   // A[row r][k = 8h + j] of this k step
 #pragma unroll
@@ -193,10 +170,7 @@ __global__ __launch_bounds__(DS_THREADS) void dwsep_kernel(const T* __restrict__
         v[0] += q.x; v[1] += q.y; v[2] += q.z; v[3] += q.w;
       }
 #pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        if (act2 == 1) v[e] = fmaxf(v[e], 0.f);
-        else if (act2 == 2) v[e] = swish_f32(v[e]);
-      }
+      for (int e = 0; e < 4; ++e) { DW_ACT(v[e], act2); }
       store4(yp + chan_off<T>(o), make_float4(v[0], v[1], v[2], v[3]));
     }
   }
@@ -227,24 +201,18 @@ void dwsep_launch(const void* x, const float* w9, const float* b1, const void* w
 extern "C" int far3d_dwsep_conv_nhwc(const void* x, int dt, const float* w9, const float* b1, int act1, const void* w_pw, int w_dt,
                                      const float* b2, int act2, void* y, int N, int H, int W, int C, int ldx, long x_img_stride, int Ho,
                                      int Wo, int Cout, int ldy, long y_img_stride, int stride, void* stream) {
+  const char* who = "far3d_dwsep_conv_nhwc";      // for the checks of dw_core.hpp; the entry's own are spelled out
   FAR3D_CHECK_ARG(x && w9 && w_pw && y, "far3d_dwsep_conv_nhwc: null pointer argument");
   FAR3D_CHECK_ARG((dt == FAR3D_DT_BF16 && w_dt == FAR3D_DT_BF16) || (dt == FAR3D_DT_BF16_PAIR && w_dt == FAR3D_DT_F32_BF16X3),
                   "far3d_dwsep_conv_nhwc: storage %d with weights %d (bf16 with bf16 weights, or pair storage with split weights)", dt, w_dt);
-  FAR3D_CHECK_ARG(stride == 1 || stride == 2, "far3d_dwsep_conv_nhwc: stride %d (1 or 2 only)", stride);
-  FAR3D_CHECK_ARG(act1 >= 0 && act1 <= 2 && act2 >= 0 && act2 <= 2, "far3d_dwsep_conv_nhwc: act %d / %d (0 none, 1 ReLU, 2 Swish)", act1, act2);
+  if (const int rc = dw_check_stride(who, stride)) return rc;
+  FAR3D_CHECK_ARG(dw_act_ok(act1) && dw_act_ok(act2), "far3d_dwsep_conv_nhwc: act %d / %d (0 none, 1 ReLU, 2 Swish)", act1, act2);
   FAR3D_CHECK_ARG(N > 0 && H > 0 && W > 0 && C > 0 && Cout > 0, "far3d_dwsep_conv_nhwc: bad sizes N=%d H=%d W=%d C=%d Cout=%d", N, H, W, C, Cout);
   FAR3D_CHECK_ARG(C % 32 == 0 && Cout % 32 == 0 && Cout <= 256, "far3d_dwsep_conv_nhwc: C=%d Cout=%d (multiples of 32, Cout <= 256)", C, Cout);
-  const int eh = (H - 1) / stride + 1, ew = (W - 1) / stride + 1;
-  FAR3D_CHECK_ARG(Ho == eh && Wo == ew, "far3d_dwsep_conv_nhwc: output %dx%d != %dx%d (3x3, pad 1, stride %d of %dx%d)", Ho, Wo, eh, ew, stride,
-                  H, W);
+  if (const int rc = dw_check_out_size(who, H, W, stride, Ho, Wo)) return rc;
   const int cs = dt == FAR3D_DT_BF16_PAIR ? 2 : 1;     // stored elements per logical channel
-  FAR3D_CHECK_ARG(ldx >= C * cs && ldy >= Cout * cs, "far3d_dwsep_conv_nhwc: pixel strides %d / %d below the %d / %d stored channels", ldx, ldy,
-                  C * cs, Cout * cs);
-  FAR3D_CHECK_ARG(N == 1 || (x_img_stride >= (long)H * W * ldx - (ldx - C * cs) && y_img_stride >= (long)Ho * Wo * ldy - (ldy - Cout * cs)),
-                  "far3d_dwsep_conv_nhwc: image strides below one image");
-  FAR3D_CHECK_ARG(ldx % 8 == 0 && ldy % 8 == 0 && x_img_stride % 8 == 0 && y_img_stride % 8 == 0 && ((uintptr_t)x % 16) == 0 &&
-                      ((uintptr_t)y % 16) == 0 && ((uintptr_t)w9 % 16) == 0 && ((uintptr_t)b1 % 16) == 0 && ((uintptr_t)w_pw % 16) == 0 &&
-                      ((uintptr_t)b2 % 16) == 0,
+  if (const int rc = dw_check_strides(who, false, cs, N, H, W, C, ldx, x_img_stride, Ho, Wo, Cout, ldy, y_img_stride)) return rc;
+  FAR3D_CHECK_ARG(dw_aligned16(8, ldx, ldy, x_img_stride, y_img_stride, {x, y, w9, b1, w_pw, b2}),
                   "far3d_dwsep_conv_nhwc: misaligned rows (pointers and strides must be multiples of 16 bytes = 8 bf16 elements)");
   // the bytes the launch reads of x and writes of y: [first channel of the first pixel, last channel of the last pixel]
   const uintptr_t x0 = (uintptr_t)x, x1 = x0 + 2 * (size_t)((long)(N - 1) * x_img_stride + ((long)H * W - 1) * ldx + C * cs);
@@ -262,7 +230,7 @@ extern "C" int far3d_dwsep_conv_nhwc(const void* x, int dt, const float* w9, con
   }
   const long npix = (long)N * Ho * Wo;
   const long blocks = (npix + DS_PIX - 1) / DS_PIX;
-  FAR3D_CHECK_ARG(blocks <= 0x7fffffffL, "far3d_dwsep_conv_nhwc: launch too large (%ld workgroups)", blocks);
+  if (const int rc = dw_check_launch_size(who, blocks)) return rc;
   hipStream_t st = (hipStream_t)stream;
   if (cs == 2)
     dwsep_launch<pair_t>(x, w9, b1, w_pw, b2, y, npix, blocks, H, W, C, ldx, x_img_stride, Ho, Wo, Cout, ldy, y_img_stride, stride, act1, act2, st);

@@ -7,6 +7,7 @@
 //   far3d_ese_nhwc         -- VoVNet eSE: x * hsigmoid(fc(avgpool(x))) (+ identity) (ref models/backbones/vovnet.py:173-185,232-236).
 //   far3d_maxpool3x3s2_nhwc-- MaxPool2d(3, 2, ceil_mode=True) (ref models/backbones/vovnet.py:249-250).
 #include "common.hpp"
+#include "dw_core.hpp"
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
@@ -363,75 +364,8 @@ extern "C" int far3d_ese_nhwc(const void* x, int dt, const float* fcw, const flo
 // hand-over needs either agent-scope fences (`buffer_wbl2 sc1` + `buffer_inv sc1`: a write-back and an invalidation of the XCD's whole L2,
 // once per workgroup) or sc1 loads / stores that go past the L2 for every gate of every thread, and a thousand resident workgroups
 // polling seven counters serialise on their cache lines.  A kernel boundary is the cheap device-wide release / acquire here.
-template <typename T> struct Vec8;
-template <> struct Vec8<bf16_t> {
-  struct Raw { uint4 a; };                             // the 16 bytes as loaded: conversion can wait until every load is issued
-  static __device__ __forceinline__ Raw ldraw(const bf16_t* p) { Raw r; r.a = *reinterpret_cast<const uint4*>(p); return r; }
-  static __device__ __forceinline__ void cvt(const Raw& q, float (&v)[8]) {
-    const uint4 r = q.a;
-    v[0] = __uint_as_float(r.x << 16); v[1] = __uint_as_float(r.x & 0xffff0000u); v[2] = __uint_as_float(r.y << 16); v[3] = __uint_as_float(r.y & 0xffff0000u);
-    v[4] = __uint_as_float(r.z << 16); v[5] = __uint_as_float(r.z & 0xffff0000u); v[6] = __uint_as_float(r.w << 16); v[7] = __uint_as_float(r.w & 0xffff0000u);
-  }
-  static __device__ __forceinline__ void ld(const bf16_t* p, float (&v)[8]) {
-    const uint4 r = *reinterpret_cast<const uint4*>(p);
-    v[0] = __uint_as_float(r.x << 16); v[1] = __uint_as_float(r.x & 0xffff0000u); v[2] = __uint_as_float(r.y << 16); v[3] = __uint_as_float(r.y & 0xffff0000u);
-    v[4] = __uint_as_float(r.z << 16); v[5] = __uint_as_float(r.z & 0xffff0000u); v[6] = __uint_as_float(r.w << 16); v[7] = __uint_as_float(r.w & 0xffff0000u);
-  }
-  static __device__ __forceinline__ void st(bf16_t* p, const float (&v)[8]) {
-    *reinterpret_cast<uint4*>(p) = make_uint4(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]), pack_bf16x2(v[4], v[5]), pack_bf16x2(v[6], v[7]));
-  }
-  static __device__ __forceinline__ void round(float (&v)[8]) {      // what a store followed by a load returns
-#pragma unroll
-    for (int e = 0; e < 8; e += 2) { const uint32_t q = pack_bf16x2(v[e], v[e + 1]); v[e] = __uint_as_float(q << 16); v[e + 1] = __uint_as_float(q & 0xffff0000u); }
-  }
-};
-template <> struct Vec8<pair_t> {        // p -> hi of 8 consecutive channels of one 32-block; lo 32 elements on
-  struct Raw { uint4 h, l; };
-  static __device__ __forceinline__ Raw ldraw(const pair_t* p) {
-    Raw r;
-    r.h = *reinterpret_cast<const uint4*>(p);
-    r.l = *reinterpret_cast<const uint4*>(reinterpret_cast<const bf16_t*>(p) + 32);
-    return r;
-  }
-  static __device__ __forceinline__ void cvt(const Raw& q, float (&v)[8]) {
-    float h[8], l[8];
-    Vec8<bf16_t>::Raw a, b;
-    a.a = q.h; b.a = q.l;
-    Vec8<bf16_t>::cvt(a, h);
-    Vec8<bf16_t>::cvt(b, l);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) v[e] = h[e] + l[e];
-  }
-  static __device__ __forceinline__ void ld(const pair_t* p, float (&v)[8]) {
-    float h[8], l[8];
-    Vec8<bf16_t>::ld(reinterpret_cast<const bf16_t*>(p), h);
-    Vec8<bf16_t>::ld(reinterpret_cast<const bf16_t*>(p) + 32, l);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) v[e] = h[e] + l[e];
-  }
-  static __device__ __forceinline__ void split(const float (&v)[8], uint4& h, uint4& l) {
-    uint2 h0, l0, h1, l1;
-    split4f(v[0], v[1], v[2], v[3], h0, l0);
-    split4f(v[4], v[5], v[6], v[7], h1, l1);
-    h = make_uint4(h0.x, h0.y, h1.x, h1.y); l = make_uint4(l0.x, l0.y, l1.x, l1.y);
-  }
-  static __device__ __forceinline__ void st(pair_t* p, const float (&v)[8]) {
-    uint4 h, l;
-    split(v, h, l);
-    *reinterpret_cast<uint4*>(p) = h;
-    *reinterpret_cast<uint4*>(reinterpret_cast<bf16_t*>(p) + 32) = l;
-  }
-  static __device__ __forceinline__ void round(float (&v)[8]) {
-    uint4 h, l;
-    split(v, h, l);
-    const uint32_t hh[4] = {h.x, h.y, h.z, h.w}, ll[4] = {l.x, l.y, l.z, l.w};
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      v[2 * e] = __uint_as_float(hh[e] << 16) + __uint_as_float(ll[e] << 16);
-      v[2 * e + 1] = __uint_as_float(hh[e] & 0xffff0000u) + __uint_as_float(ll[e] & 0xffff0000u);
-    }
-  }
-};
+// the 16-byte channel vectors of a pixel (ld / ldraw / cvt / st / round) are the depthwise family's: dw_core.hpp
+template <typename T> using Vec8 = DwIo<T>;
 
 struct EseFusedParams {
   const void* x; const void* idn; void* y; void* pooled;

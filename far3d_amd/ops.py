@@ -1374,34 +1374,54 @@ def pack_dw3x3(weight, device=None):
     return w.to(device) if device is not None else w
 
 
+DW_ACTS = {None: 0, "none": 0, "relu": 1, "swish": 2}
+
+
+def _dw_act(act):
+    """None | "relu" | "swish" (or the library's code 0 / 1 / 2) -> the library's code."""
+    return DW_ACTS[act] if (act is None or isinstance(act, str)) else int(act)
+
+
+def _dw_operands(who, x, pair, w, w_name, w_ndim, w_text, bias, b_name, stride, out, out_text="", sets=1, Cout=None):
+    """What the three depthwise wrappers do alike.  x: NHWC view (pair: bf16 with 2C stored channels).  w: f32 whose last two dimensions
+    are (9, C) (`w_text`: its message, taking the shape and C); bias: None or f32 of w's leading dimensions + (C,).  out: None (allocated
+    for 3x3 / pad 1 / `stride`) or an NHWC view of x's storage with Cout (None: sets * C) logical channels (`out_text` ends its message).
+    Returns the storage code, C, out and the library's arguments of the two maps: (ldx, x_img_stride), (Ho, Wo, ldy, y_img_stride)."""
+    N, H, W, Cs = x.shape
+    cs = 2 if pair else 1
+    C = Cs // cs
+    if pair and x.dtype != torch.bfloat16:
+        raise TypeError("%s: pair storage is bf16" % who)
+    _chk(w, w_name, torch.float32, w_ndim)
+    if tuple(w.shape[-2:]) != (9, C):
+        raise ValueError(("%s: " + w_text) % (who, tuple(w.shape), C))
+    if bias is not None:
+        _chk(bias, b_name, torch.float32, w.dim() - 1)
+        if tuple(bias.shape) != tuple(w.shape[:-2]) + (C,):
+            raise ValueError("%s: %s %s != %s" % (who, b_name, tuple(bias.shape), tuple(w.shape[:-2]) + (C,)))
+    xv = _nhwc_view(x, "x")
+    Cy = (sets * C if Cout is None else Cout) * cs
+    if out is None:
+        s = int(stride)
+        if s < 1:
+            raise ValueError("%s: stride %r" % (who, stride))
+        out = torch.empty((N, (H - 1) // s + 1, (W - 1) // s + 1, Cy), dtype=x.dtype, device=x.device)
+    if out.dtype != x.dtype or out.shape[0] != N or out.shape[3] != Cy:
+        raise ValueError("%s: out %s %s does not match x %s %s%s" % (who, tuple(out.shape), out.dtype, tuple(x.shape), x.dtype, out_text))
+    return (DT_BF16_PAIR if pair else _dt(x)), C, out, xv, (out.shape[1], out.shape[2]) + _nhwc_view(out, "out")
+
+
 def dwconv3x3_nhwc(x, w9c, stride, out=None, pair=False):
     """Depthwise 3x3 / pad 1 / stride 1|2 convolution without bias or activation (nn.Conv2d(C, C, 3, stride, 1, groups=C, bias=False)) on
     an NHWC view x (f32 | bf16; pair: a pair-stored bf16 map of 2C stored channels).  w9c: (9, C) f32 (pack_dw3x3).  out: optional NHWC view
     of x's storage (a channel slice of a wider buffer is fine).  Sizes, strides and alignment are checked by the library
     (Far3dHipError, nothing launched)."""
     lib = _lib.require_device()
-    N, H, W, Cs = x.shape
-    C = Cs // 2 if pair else Cs
-    if pair and x.dtype != torch.bfloat16:
-        raise TypeError("dwconv3x3_nhwc: pair storage is bf16")
-    _chk(w9c, "w9c", torch.float32, 2)
-    if tuple(w9c.shape) != (9, C):
-        raise ValueError("dwconv3x3_nhwc: weights %s != (9, %d)" % (tuple(w9c.shape), C))
-    ldx, xs = _nhwc_view(x, "x")
-    if out is None:
-        s = int(stride)
-        if s < 1:
-            raise ValueError("dwconv3x3_nhwc: stride %r" % (stride,))
-        out = torch.empty((N, (H - 1) // s + 1, (W - 1) // s + 1, Cs), dtype=x.dtype, device=x.device)
-    if out.dtype != x.dtype or out.shape[0] != N or out.shape[3] != Cs:
-        raise ValueError("dwconv3x3_nhwc: out %s %s does not match x %s %s" % (tuple(out.shape), out.dtype, tuple(x.shape), x.dtype))
-    ldy, ys = _nhwc_view(out, "out")
-    _lib.check(lib.far3d_dwconv3x3_nhwc(_ptr(x), DT_BF16_PAIR if pair else _dt(x), _ptr(w9c), _ptr(out), N, H, W, C, ldx, xs,
-                                        out.shape[1], out.shape[2], ldy, ys, int(stride), _stream(x)), "far3d_dwconv3x3_nhwc")
+    dt, C, out, (ldx, xs), (Ho, Wo, ldy, ys) = _dw_operands("dwconv3x3_nhwc", x, pair, w9c, "w9c", 2, "weights %s != (9, %d)", None, None,
+                                                            stride, out)
+    _lib.check(lib.far3d_dwconv3x3_nhwc(_ptr(x), dt, _ptr(w9c), _ptr(out), x.shape[0], x.shape[1], x.shape[2], C, ldx, xs, Ho, Wo, ldy, ys,
+                                        int(stride), _stream(x)), "far3d_dwconv3x3_nhwc")
     return out
-
-
-DW_ACTS = {None: 0, "none": 0, "relu": 1, "swish": 2}
 
 
 def pack_dw3x3_sets(weights, biases=None, device=None):
@@ -1423,36 +1443,16 @@ def dwconv3x3_act_nhwc(x, w, stride, bias=None, act=None, out=None, pair=False):
     activation the result is dwconv3x3_nhwc's, bit for bit.  Sizes, strides, alignment, reps and act are checked by the library
     (Far3dHipError, nothing launched)."""
     lib = _lib.require_device()
-    N, H, W, Cs = x.shape
-    C = Cs // 2 if pair else Cs
-    if pair and x.dtype != torch.bfloat16:
-        raise TypeError("dwconv3x3_act_nhwc: pair storage is bf16")
     if w.dim() == 2:
         w = w[None]
-    _chk(w, "w", torch.float32, 3)
-    reps = w.shape[0]
-    if tuple(w.shape[1:]) != (9, C):
-        raise ValueError("dwconv3x3_act_nhwc: weights %s != (reps, 9, %d)" % (tuple(w.shape), C))
-    if bias is not None:
-        if bias.dim() == 1:
-            bias = bias[None]
-        _chk(bias, "bias", torch.float32, 2)
-        if tuple(bias.shape) != (reps, C):
-            raise ValueError("dwconv3x3_act_nhwc: bias %s != (%d, %d)" % (tuple(bias.shape), reps, C))
-    code = DW_ACTS[act] if (act is None or isinstance(act, str)) else int(act)
-    ldx, xs = _nhwc_view(x, "x")
-    if out is None:
-        s = int(stride)
-        if s < 1:
-            raise ValueError("dwconv3x3_act_nhwc: stride %r" % (stride,))
-        out = torch.empty((N, (H - 1) // s + 1, (W - 1) // s + 1, max(reps, 1) * Cs), dtype=x.dtype, device=x.device)
-    if out.dtype != x.dtype or out.shape[0] != N or out.shape[3] != reps * Cs:
-        raise ValueError("dwconv3x3_act_nhwc: out %s %s does not match x %s %s with %d weight sets" %
-                         (tuple(out.shape), out.dtype, tuple(x.shape), x.dtype, reps))
-    ldy, ys = _nhwc_view(out, "out")
-    _lib.check(lib.far3d_dwconv3x3_act_nhwc(_ptr(x), DT_BF16_PAIR if pair else _dt(x), _ptr(w), _ptr(bias) if bias is not None else None,
-                                            _ptr(out), N, H, W, C, ldx, xs, out.shape[1], out.shape[2], ldy, ys, int(stride), int(reps), code,
-                                            _stream(x)), "far3d_dwconv3x3_act_nhwc")
+    if bias is not None and bias.dim() == 1:
+        bias = bias[None]
+    reps = w.shape[0] if w.dim() == 3 else 1
+    dt, C, out, (ldx, xs), (Ho, Wo, ldy, ys) = _dw_operands("dwconv3x3_act_nhwc", x, pair, w, "w", 3, "weights %s != (reps, 9, %d)", bias, "bias",
+                                                            stride, out, " with %d weight sets" % reps, sets=reps)
+    _lib.check(lib.far3d_dwconv3x3_act_nhwc(_ptr(x), dt, _ptr(w), _ptr(bias) if bias is not None else None, _ptr(out), x.shape[0], x.shape[1],
+                                            x.shape[2], C, ldx, xs, Ho, Wo, ldy, ys, int(stride), int(reps), _dw_act(act), _stream(x)),
+               "far3d_dwconv3x3_act_nhwc")
     return out
 
 
@@ -1479,37 +1479,17 @@ def dwsep_conv_nhwc(x, w9, pc, stride, bias1=None, act1=None, act2=None, out=Non
     pc.Cout logical channels.  What dwsep_supported refuses, a misaligned view or an overlap of x and out is an error of the library
     (Far3dHipError, nothing launched) -- there is no two-launch fallback in here."""
     lib = _lib.require_device()
-    N, H, W, Cs = x.shape
-    C = Cs // 2 if pair else Cs
-    if pair and x.dtype != torch.bfloat16:
-        raise TypeError("dwsep_conv_nhwc: pair storage is bf16")
     if w9.dim() == 3 and w9.shape[0] == 1:
         w9 = w9[0]
-    _chk(w9, "w9", torch.float32, 2)
-    if tuple(w9.shape) != (9, C):
-        raise ValueError("dwsep_conv_nhwc: depthwise weights %s != (9, %d)" % (tuple(w9.shape), C))
-    if bias1 is not None:
-        if bias1.dim() == 2 and bias1.shape[0] == 1:
-            bias1 = bias1[0]
-        _chk(bias1, "bias1", torch.float32, 1)
-        if bias1.shape[0] != C:
-            raise ValueError("dwsep_conv_nhwc: bias1 %s != (%d,)" % (tuple(bias1.shape), C))
+    if bias1 is not None and bias1.dim() == 2 and bias1.shape[0] == 1:
+        bias1 = bias1[0]
+    dt, C, out, (ldx, xs), (Ho, Wo, ldy, ys) = _dw_operands("dwsep_conv_nhwc", x, pair, w9, "w9", 2, "depthwise weights %s != (9, %d)", bias1,
+                                                            "bias1", stride, out, " and %d output channels" % pc.Cout, Cout=pc.Cout)
     if (pc.KH, pc.KW, pc.stride, pc.pad) != (1, 1, 1, 0) or pc.Cin != C or pc.terms != 3:
         raise ValueError("dwsep_conv_nhwc: pc must be a 1x1 / stride 1 / pad 0 layer of %d input channels with full products" % C)
-    codes = [DW_ACTS[a] if (a is None or isinstance(a, str)) else int(a) for a in (act1, act2)]
-    ldx, xs = _nhwc_view(x, "x")
-    s = int(stride)
-    if out is None:
-        if s < 1:
-            raise ValueError("dwsep_conv_nhwc: stride %r" % (stride,))
-        out = torch.empty((N, (H - 1) // s + 1, (W - 1) // s + 1, pc.Cout * (2 if pair else 1)), dtype=x.dtype, device=x.device)
-    if out.dtype != x.dtype or out.shape[0] != N or out.shape[3] != pc.Cout * (2 if pair else 1):
-        raise ValueError("dwsep_conv_nhwc: out %s %s does not match x %s %s and %d output channels" %
-                         (tuple(out.shape), out.dtype, tuple(x.shape), x.dtype, pc.Cout))
-    ldy, ys = _nhwc_view(out, "out")
-    _lib.check(lib.far3d_dwsep_conv_nhwc(_ptr(x), DT_BF16_PAIR if pair else _dt(x), _ptr(w9), _ptr(bias1) if bias1 is not None else None,
-                                         codes[0], _ptr(pc.w), pc.w_code, _ptr(pc.bias) if pc.bias is not None else None, codes[1], _ptr(out),
-                                         N, H, W, C, ldx, xs, out.shape[1], out.shape[2], pc.Cout, ldy, ys, s, _stream(x)),
+    _lib.check(lib.far3d_dwsep_conv_nhwc(_ptr(x), dt, _ptr(w9), _ptr(bias1) if bias1 is not None else None, _dw_act(act1), _ptr(pc.w),
+                                         pc.w_code, _ptr(pc.bias) if pc.bias is not None else None, _dw_act(act2), _ptr(out), x.shape[0],
+                                         x.shape[1], x.shape[2], C, ldx, xs, Ho, Wo, pc.Cout, ldy, ys, int(stride), _stream(x)),
                "far3d_dwsep_conv_nhwc")
     return out
 

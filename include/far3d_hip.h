@@ -470,7 +470,9 @@ int far3d_maxpool3x3s2_nhwc(const void* x, int dt, void* y, int N, int H, int W,
  * with C % 32 == 0 (hi + lo read, the fp32 result stored split).  w: [9][C] f32, w[ky*3 + kx][c] = weight[c][0][ky][kx].
  * Ho = (H-1)/stride + 1, Wo = (W-1)/stride + 1.  Every pointer and stride a multiple of 16 bytes.  x and y must not overlap.
  * fp32 accumulation in the fixed tap order (0,0) ... (2,2) with pinned fmas: the bits of an output element depend on its own window
- * and weights only, never on N or the launch's other pixels.  Bad arguments return FAR3D_ERR_ARG and launch nothing. */
+ * and weights only, never on N or the launch's other pixels.  The kernel is far3d_dwconv3x3_act_nhwc's, instantiated with one weight
+ * set and without bias and activation code; both entries run the same argument checks.  Bad arguments return FAR3D_ERR_ARG and launch
+ * nothing. */
 int far3d_dwconv3x3_nhwc(const void* x, int dt, const float* w, void* y, int N, int H, int W, int C, int ldx, long x_img_stride,
                          int Ho, int Wo, int ldy, long y_img_stride, int stride, void* stream);
 
@@ -496,7 +498,8 @@ int far3d_dwconv3x3_act_nhwc(const void* x, int dt, const float* w, const float*
  * Cin padded to 32; split weights as [32 hi | 32 lo] per 32-channel block) and padded bias (or NULL) of a 1x1 far3d_conv2d_nhwc layer;
  * act1, act2: 0 none / 1 ReLU / 2 Swish (full-precision expf).
  * Depthwise half: the nine pinned fmas of far3d_dwconv3x3_nhwc in its tap order, the bias add, the activation, then the rounding of
- * that kernel's store (bf16 round-to-nearest-even; pair hi = bf16(v), lo = bf16(v - hi)) -- the MFMA operand holds bit for bit what
+ * that kernel's store (bf16 round-to-nearest-even; pair hi = bf16(v), lo = bf16(v - hi); vector load, activation and rounding are one
+ * source for both kernels, csrc/dw_core.hpp) -- the MFMA operand holds bit for bit what
  * the two-launch path writes to its scratch map; only the accumulation order of the pointwise sums differs from far3d_conv2d_nhwc.
  * Anything else (f32 storage, other sizes, overlap, misalignment) returns FAR3D_ERR_ARG and launches nothing. */
 int far3d_dwsep_conv_nhwc(const void* x, int dt, const float* w9, const float* b1, int act1, const void* w_pw, int w_dt, const float* b2,
