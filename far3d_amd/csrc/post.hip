@@ -8,6 +8,8 @@
 //   far3d_decode_topk     NMSFreeCoder.decode_single + FarHead.get_bboxes: sigmoid, top-max_num over A*num_classes, label/query
 //                         split, denormalize_bbox (exp, atan2), post_center_range mask, z -= h/2.
 //                         ref core/bbox/coders/nms_free_coder.py:39-91, core/bbox/util.py:25-52, farhead.py:1224-1245.
+//   far3d_decode_topk_tracked   the decode + memory top-k of B streams that also writes the query row of every decoded box (track ids:
+//                         csrc/track.hip follows them through the streaming memory).
 //   far3d_camera_prep     img2lidar = inverse(lidar2img) (ref farhead.py:798) and the 14-float MLN camera code
 //                         (ref farhead.py:553-556).
 //   far3d_agg_order       camera / image-cell sorted query order for far3d_aggregate_forward (scheduling only).
@@ -500,14 +502,26 @@ struct DecodeParams {
 // otherwise cls points at candidate logits (the per-chunk winners of decode_chunk_kernel, chunk-major, each chunk sorted) and
 // cand_idx maps a position to the original index.  Equal logits keep their original index order in that layout, so the tie rule
 // (lowest index first) is the single-launch one.
-template <int MAXV>
-__global__ __launch_bounds__(TOPK_THREADS) void decode_topk_kernel(DecodeParams p, int n, const int* __restrict__ cand_idx) {
+//
+// QUERY OUTPUT (far3d_decode_topk_tracked): query[i] = the query row output i was decoded from, the flat index / ncls of DECODE_ROW.
+// It is the compile-time switch of the decode kernels, spelled as their trailing argument pack: the tracked instantiations have the
+// argument (Q = int* here, BS = DecodeStreamsQuery below), the others have an empty pack -- their argument lists and their code are
+// what they were, the store is a discarded `if constexpr` branch.
+__device__ __forceinline__ int decode_query_row(unsigned long long e, const int* cand_idx, int ncls) {
+  int idx = (int)(0xffffffffu - (unsigned)(e & 0xffffffffull));
+  if (cand_idx) idx = cand_idx[idx];
+  return idx / ncls;
+}
+__device__ __forceinline__ int* decode_query_arg(int* q) { return q; }
+template <int MAXV, typename... Q>      // Q: int* (the query output) or nothing
+__global__ __launch_bounds__(TOPK_THREADS) void decode_topk_kernel(DecodeParams p, int n, const int* __restrict__ cand_idx, Q... query) {
   __shared__ unsigned long long sel[TOPK_MAXK];
   // sigmoid is monotone: the top-K of sigmoid(logits) is the top-K of the logits
   block_topk_sorted<MAXV>(p.cls, n, p.K, sel);
   for (int i = threadIdx.x; i < p.K; i += TOPK_THREADS) {
     const unsigned long long e = sel[i];
     DECODE_ROW(p, p.box, p.boxes, p.scores, p.labels, p.keep, e, i, cand_idx)
+    if constexpr (sizeof...(Q) > 0) decode_query_arg(query...)[i] = decode_query_row(e, cand_idx, p.ncls);
   }
 }
 
@@ -523,8 +537,10 @@ __global__ __launch_bounds__(TOPK_THREADS) void decode_topk_kernel(DecodeParams 
 // instantiations have (BS = DecodeStreams; the one-stream instantiations have an empty pack: their argument list, and their code,
 // are what they were).
 struct DecodeStreams { long cls, box, boxes, scores, labels, keep, vals2, idx2; };
+struct DecodeStreamsQuery : DecodeStreams { int* query; long query_stride; };      // + the query output (above) and its stream stride
 __device__ __forceinline__ const DecodeStreams& decode_streams_arg(const DecodeStreams& s) { return s; }
-template <int MAXV, typename... BS>     // BS: DecodeStreams (blockIdx.y = stream) or nothing
+__device__ __forceinline__ const DecodeStreamsQuery& decode_streams_query(const DecodeStreamsQuery& s) { return s; }
+template <int MAXV, typename... BS>     // BS: DecodeStreams / DecodeStreamsQuery (blockIdx.y = stream) or nothing
 __global__ __launch_bounds__(TOPK_THREADS) void decode_topk_mem_kernel(DecodeParams p, int n, const float* __restrict__ vals2, int n2, int K2,
                                                                        long* __restrict__ idx2, BS... bs) {
   const float* cls = p.cls;
@@ -549,6 +565,10 @@ __global__ __launch_bounds__(TOPK_THREADS) void decode_topk_mem_kernel(DecodePar
   for (int i = threadIdx.x; i < p.K; i += TOPK_THREADS) {
     const unsigned long long e = sel[i];
     DECODE_ROW(p, box, boxes, scores, labels, keep, e, i, (const int*)nullptr)
+    if constexpr ((std::is_same<BS, DecodeStreamsQuery>::value || ...)) {
+      const DecodeStreamsQuery& s = decode_streams_query(bs...);
+      (s.query + (long)blockIdx.y * s.query_stride)[i] = decode_query_row(e, nullptr, p.ncls);
+    }
   }
 }
 
@@ -601,6 +621,24 @@ static int decode_chunks(const char* who, long n, int K, int& nchunks, long& nca
   return FAR3D_OK;
 }
 
+// The decode's launches for n = A * ncls logits: one workgroup up to DECODE_CHUNK, otherwise the chunk ranking (nchunks workgroups,
+// ncand candidates into the checked workspace) and the ranking of the candidates.  query: nothing, or the query output (above).
+template <typename... Q>
+static void decode_launch(DecodeParams p, long n, int nchunks, long ncand, void* workspace, hipStream_t st, Q... query) {
+  if (n <= DECODE_CHUNK) {
+    topk_for_maxv(n, [&](auto mv) { hipLaunchKernelGGL((decode_topk_kernel<decltype(mv)::value, Q...>), dim3(1), dim3(TOPK_THREADS), 0, st, p, (int)n, (const int*)nullptr, query...); });
+    return;
+  }
+  float* cand_val = (float*)workspace;
+  int* cand_idx = (int*)(cand_val + ncand);
+  hipLaunchKernelGGL(decode_chunk_kernel, dim3(nchunks), dim3(TOPK_THREADS), 0, st, p.cls, (int)n, p.K, cand_val, cand_idx);
+  p.cls = cand_val;
+  if (ncand <= TOPK_THREADS * 4)
+    hipLaunchKernelGGL((decode_topk_kernel<4, Q...>), dim3(1), dim3(TOPK_THREADS), 0, st, p, (int)ncand, (const int*)cand_idx, query...);
+  else
+    hipLaunchKernelGGL((decode_topk_kernel<TOPK_MAXV, Q...>), dim3(1), dim3(TOPK_THREADS), 0, st, p, (int)ncand, (const int*)cand_idx, query...);
+}
+
 extern "C" int far3d_decode_topk(const float* cls_last, const float* box_last, int A, int num_classes, int code_size, int K,
                                  const float* post_center_range, float* boxes, float* scores, int64_t* labels,
                                  unsigned char* keep, void* workspace, long workspace_bytes, void* stream) {
@@ -609,23 +647,14 @@ extern "C" int far3d_decode_topk(const float* cls_last, const float* box_last, i
   if (const int rc = decode_check_sizes("far3d_decode_topk", A, num_classes, code_size, K)) return rc;
   DecodeParams p = decode_fill_params(cls_last, box_last, A, num_classes, code_size, K, post_center_range, boxes, scores, labels, keep);
   hipStream_t st = (hipStream_t)stream;
-  if (n <= DECODE_CHUNK) {
-    topk_for_maxv(n, [&](auto mv) { hipLaunchKernelGGL(decode_topk_kernel<decltype(mv)::value>, dim3(1), dim3(TOPK_THREADS), 0, st, p, (int)n, (const int*)nullptr); });
-  } else {
-    int nchunks; long ncand;
+  int nchunks = 0; long ncand = 0;
+  if (n > DECODE_CHUNK) {
     if (const int rc = decode_chunks("far3d_decode_topk", n, K, nchunks, ncand)) return rc;
     FAR3D_CHECK_ARG(workspace && workspace_bytes >= ncand * 8 && ((uintptr_t)workspace % 8) == 0,
                     "far3d_decode_topk: A*num_classes=%ld > %d needs a workspace of FAR3D_DECODE_WS_BYTES = %ld bytes (got %ld)", n, DECODE_CHUNK,
                     ncand * 8, workspace ? workspace_bytes : 0L);
-    float* cand_val = (float*)workspace;
-    int* cand_idx = (int*)(cand_val + ncand);
-    hipLaunchKernelGGL(decode_chunk_kernel, dim3(nchunks), dim3(TOPK_THREADS), 0, st, cls_last, (int)n, K, cand_val, cand_idx);
-    p.cls = cand_val;
-    if (ncand <= TOPK_THREADS * 4)
-      hipLaunchKernelGGL(decode_topk_kernel<4>, dim3(1), dim3(TOPK_THREADS), 0, st, p, (int)ncand, (const int*)cand_idx);
-    else
-      hipLaunchKernelGGL(decode_topk_kernel<TOPK_MAXV>, dim3(1), dim3(TOPK_THREADS), 0, st, p, (int)ncand, (const int*)cand_idx);
   }
+  decode_launch(p, n, nchunks, ncand, workspace, st);
   FAR3D_CHECK_LAUNCH("far3d_decode_topk");
   return FAR3D_OK;
 }
@@ -652,14 +681,11 @@ extern "C" int far3d_decode_topk_mem(const float* cls_last, const float* box_las
   return FAR3D_OK;
 }
 
-// far3d_decode_topk_mem for B scene streams: one launch of the STREAMS instantiations (grid (2, B)) where the one-stream entry takes its
-// fused launch; otherwise that entry per stream, each with its own slice of the workspace.  Every size rule of the one-stream entry is
-// checked here first, so that a bad argument launches nothing for any stream.
-extern "C" int far3d_decode_topk_mem_streams(const float* cls_last, const float* box_last, int B, int A, int num_classes, int code_size,
-                                             int K, const float* post_center_range, float* boxes, float* scores, int64_t* labels,
-                                             unsigned char* keep, void* workspace, long workspace_bytes, const float* mem_scores,
-                                             int mem_n, int mem_K, int64_t* mem_idx_out, const long* batch_strides, void* stream) {
-  const char* who = "far3d_decode_topk_mem_streams";
+// Every argument rule of the streams entries (`who` names the entry in the messages); nchunks / ncand: the chunked decode's, 0 below it.
+static int decode_streams_check(const char* who, const float* cls_last, const float* box_last, int B, int A, int num_classes, int code_size,
+                                int K, const float* post_center_range, float* boxes, float* scores, int64_t* labels, unsigned char* keep,
+                                void* workspace, long workspace_bytes, const float* mem_scores, int mem_n, int mem_K, int64_t* mem_idx_out,
+                                const long* batch_strides, int& nchunks, long& ncand) {
   FAR3D_CHECK_ARG(cls_last, "%s: cls_last is a null pointer", who);
   FAR3D_CHECK_ARG(box_last, "%s: box_last is a null pointer", who);
   FAR3D_CHECK_ARG(post_center_range, "%s: post_center_range is a null pointer", who);
@@ -676,8 +702,8 @@ extern "C" int far3d_decode_topk_mem_streams(const float* cls_last, const float*
   const long n = (long)A * num_classes;
   FAR3D_CHECK_ARG(A > 0 && num_classes > 0 && code_size >= 8 && K > 0 && K <= TOPK_MAXK && n < (1L << 30) && K <= n,
                   "%s: bad sizes A=%d num_classes=%d code_size=%d K=%d (K <= %d)", who, A, num_classes, code_size, K, TOPK_MAXK);
+  nchunks = 0; ncand = 0;
   if (n > DECODE_CHUNK) {
-    int nchunks; long ncand;
     if (const int rc = decode_chunks(who, n, K, nchunks, ncand)) return rc;
     FAR3D_CHECK_ARG(workspace && workspace_bytes >= ncand * 8 && ((uintptr_t)workspace % 8) == 0 && workspace_bytes % 8 == 0,
                     "%s: A*num_classes=%ld > %d needs a workspace of B x workspace_bytes, workspace_bytes >= FAR3D_DECODE_WS_BYTES = %ld per "
@@ -689,6 +715,22 @@ extern "C" int far3d_decode_topk_mem_streams(const float* cls_last, const float*
   for (int i = 0; i < 8; ++i)
     FAR3D_CHECK_ARG(B == 1 || batch_strides[i] >= extent[i], "%s: batch_strides[%d] (%s) = %ld elements is below one stream's %ld", who, i,
                     names[i], batch_strides[i], extent[i]);
+  return FAR3D_OK;
+}
+
+// far3d_decode_topk_mem for B scene streams: one launch of the STREAMS instantiations (grid (2, B)) where the one-stream entry takes its
+// fused launch; otherwise that entry per stream, each with its own slice of the workspace.  Every size rule of the one-stream entry is
+// checked here first, so that a bad argument launches nothing for any stream.
+extern "C" int far3d_decode_topk_mem_streams(const float* cls_last, const float* box_last, int B, int A, int num_classes, int code_size,
+                                             int K, const float* post_center_range, float* boxes, float* scores, int64_t* labels,
+                                             unsigned char* keep, void* workspace, long workspace_bytes, const float* mem_scores,
+                                             int mem_n, int mem_K, int64_t* mem_idx_out, const long* batch_strides, void* stream) {
+  const char* who = "far3d_decode_topk_mem_streams";
+  int nchunks; long ncand;
+  if (const int rc = decode_streams_check(who, cls_last, box_last, B, A, num_classes, code_size, K, post_center_range, boxes, scores, labels, keep,
+                                          workspace, workspace_bytes, mem_scores, mem_n, mem_K, mem_idx_out, batch_strides, nchunks, ncand))
+    return rc;
+  const long n = (long)A * num_classes;
   const bool fused = n <= DECODE_CHUNK && mem_n <= TOPK_THREADS * 4;
   const long* bs = batch_strides;
   if (!fused) {
@@ -707,6 +749,45 @@ extern "C" int far3d_decode_topk_mem_streams(const float* cls_last, const float*
   const dim3 grid(2, B);
   topk_for_maxv(n, [&](auto mv) { hipLaunchKernelGGL((decode_topk_mem_kernel<decltype(mv)::value, DecodeStreams>), grid, dim3(TOPK_THREADS), 0, st, p, (int)n, mem_scores, mem_n, mem_K, (long*)mem_idx_out, ds); });
   FAR3D_CHECK_LAUNCH(who);
+  return FAR3D_OK;
+}
+
+// far3d_decode_topk_mem_streams + the query row of every decoded box (query_out (K) int32 per stream, query_stride elements apart), for
+// B >= 1 streams: the same launches with the tracked instantiations, so every other output has the bits of the untracked entry.  Fused:
+// one launch of 2 * B workgroups; otherwise per stream far3d_topk and the one- or two-launch decode (decode_launch), as
+// far3d_decode_topk_mem issues them.
+extern "C" int far3d_decode_topk_tracked(const float* cls_last, const float* box_last, int B, int A, int num_classes, int code_size,
+                                         int K, const float* post_center_range, float* boxes, float* scores, int64_t* labels,
+                                         unsigned char* keep, void* workspace, long workspace_bytes, const float* mem_scores,
+                                         int mem_n, int mem_K, int64_t* mem_idx_out, const long* batch_strides, int32_t* query_out,
+                                         long query_stride, void* stream) {
+  const char* who = "far3d_decode_topk_tracked";
+  FAR3D_CHECK_ARG(query_out, "%s: query_out is a null pointer", who);
+  int nchunks; long ncand;
+  if (const int rc = decode_streams_check(who, cls_last, box_last, B, A, num_classes, code_size, K, post_center_range, boxes, scores, labels, keep,
+                                          workspace, workspace_bytes, mem_scores, mem_n, mem_K, mem_idx_out, batch_strides, nchunks, ncand))
+    return rc;
+  FAR3D_CHECK_ARG(B == 1 || query_stride >= K, "%s: query_stride = %ld elements is below one stream's %d", who, query_stride, K);
+  const long n = (long)A * num_classes;
+  const long* bs = batch_strides;
+  hipStream_t st = (hipStream_t)stream;
+  if (n <= DECODE_CHUNK && mem_n <= TOPK_THREADS * 4) {
+    const DecodeParams p = decode_fill_params(cls_last, box_last, A, num_classes, code_size, K, post_center_range, boxes, scores, labels, keep);
+    DecodeStreamsQuery ds;
+    static_cast<DecodeStreams&>(ds) = DecodeStreams{bs[0], bs[1], bs[2], bs[3], bs[4], bs[5], bs[6], bs[7]};
+    ds.query = query_out; ds.query_stride = query_stride;
+    const dim3 grid(2, B);
+    topk_for_maxv(n, [&](auto mv) { hipLaunchKernelGGL((decode_topk_mem_kernel<decltype(mv)::value, DecodeStreamsQuery>), grid, dim3(TOPK_THREADS), 0, st, p, (int)n, mem_scores, mem_n, mem_K, (long*)mem_idx_out, ds); });
+    FAR3D_CHECK_LAUNCH(who);
+    return FAR3D_OK;
+  }
+  for (long b = 0; b < B; ++b) {
+    if (const int rc = far3d_topk(mem_scores + b * bs[6], mem_n, mem_K, mem_idx_out + b * bs[7], nullptr, stream)) return rc;
+    const DecodeParams p = decode_fill_params(cls_last + b * bs[0], box_last + b * bs[1], A, num_classes, code_size, K, post_center_range,
+                                              boxes + b * bs[2], scores + b * bs[3], labels + b * bs[4], keep + b * bs[5]);
+    decode_launch(p, n, nchunks, ncand, workspace ? (char*)workspace + b * workspace_bytes : nullptr, st, (int*)(query_out + b * query_stride));
+    FAR3D_CHECK_LAUNCH(who);
+  }
   return FAR3D_OK;
 }
 

@@ -44,14 +44,17 @@ def box_to_av2(boxes_3d):
     return torch.cat([centre, t[:, [3, 4, 5]], yaw_to_quat(t[:, 6])], dim=1)
 
 
-def format_results(outputs, data_infos, classes=AV2_CLASSES, feather_path=None):
+def format_results(outputs, data_infos, classes=AV2_CLASSES, feather_path=None, track_ids=None):
     """ref argoverse2_dataset.py:267-331.  outputs: one dict per sample with boxes_3d / scores_3d / labels_3d (optionally under
     'pts_bbox'); data_infos: per sample `scene_id` and `lidar_timestamp_ns`.  Returns the detections frame indexed by
-    (log_id, timestamp_ns), sorted like the reference; feather_path additionally writes the score-sorted submission file."""
+    (log_id, timestamp_ns), sorted like the reference; feather_path additionally writes the score-sorted submission file.
+    track_ids: optional, one sequence of ints per sample (a sample's `track_ids_3d`, aligned with its boxes): the frame gets a
+    `track_id` column.  Not given: no such column."""
     import pandas as pd
     assert len(data_infos) == len(outputs)
+    assert track_ids is None or len(track_ids) == len(outputs)
     frames = []
-    for out_i, info in zip(outputs, data_infos):
+    for i, (out_i, info) in enumerate(zip(outputs, data_infos)):
         if "pts_bbox" in out_i:
             out_i = out_i["pts_bbox"]
         labels = torch.as_tensor(out_i["labels_3d"]).cpu().numpy().tolist()
@@ -59,7 +62,11 @@ def format_results(outputs, data_infos, classes=AV2_CLASSES, feather_path=None):
         df["score"] = torch.as_tensor(out_i["scores_3d"]).cpu().numpy()
         df["log_id"] = info["scene_id"]
         df["timestamp_ns"] = int(info["lidar_timestamp_ns"])
-        df["category"] = [classes[i].upper() for i in labels]
+        df["category"] = [classes[c].upper() for c in labels]
+        if track_ids is not None:
+            ids = torch.as_tensor(track_ids[i]).cpu().numpy().astype("int64")
+            assert len(ids) == len(df), "track_ids[%d] holds %d ids for %d boxes" % (i, len(ids), len(df))
+            df["track_id"] = ids
         frames.append(df)
     dts = pd.concat(frames).set_index(["log_id", "timestamp_ns"]).sort_index()
     dts = dts.sort_values("score", ascending=False).reset_index()

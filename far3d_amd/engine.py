@@ -78,6 +78,10 @@ def default_cfg(**over):
         # depthwise 3x3 + BN + Swish, pointwise 1x1 + BN + Swish per layer).  depth_level: the FPN level the depth branch reads
         # (reg_depth_level p3 / p4 / p5 = 0 / 1 / 2); the proposals take the depth map's stride from strides[depth_level]
         roi_depthwise=False, depth_level=0,
+        # track ids (INTEGRATION.md "Track ids"): None = off; dict(birth_thr=p) adds `query_idx` / `track_ids` to the result -- the identity
+        # of a detection across the frames of its scene, carried through the streaming memory (far3d_track_update).  birth_thr: the
+        # max-class probability from which a ranked query without an identity is given a new one (0.0: every ranked query)
+        track=None,
     )
     cfg.update(over)
     return cfg
@@ -91,6 +95,29 @@ def multi_depth_topk(cfg):
     if not 1 <= k <= 8:
         raise ValueError("multi_depth topk=%s: supported values are 1 ... 8 (or -1, the same as 1)" % md.get("topk"))
     return k
+
+
+def track_options(cfg):
+    """cfg['track'] checked: None (tracking off) or dict(birth_thr=<probability>).  Tracking needs num_propagated <= topk_proposals: a memory
+    slot beyond the frame's top-k is one that was carried over, and propagating it again would put its id on two queries.  A pure
+    function of cfg: no device, no library."""
+    tr = cfg.get("track")
+    if tr is None or tr is False:
+        return None
+    tr = {} if tr is True else dict(tr)
+    unknown = sorted(set(tr) - {"birth_thr"})
+    if unknown:
+        raise ValueError("track: unknown option(s) %s (known: birth_thr)" % ", ".join(unknown))
+    thr = float(tr.get("birth_thr", 0.0))
+    if not 0.0 <= thr <= 1.0:
+        raise ValueError("track birth_thr=%r: a probability in [0, 1]" % (tr.get("birth_thr"),))
+    if cfg["num_propagated"] > cfg["topk_proposals"]:
+        raise ValueError("track: num_propagated=%d > topk_proposals=%d: a memory slot that was carried over would be propagated a second time "
+                         "with the same id; tracking needs num_propagated <= topk_proposals" % (cfg["num_propagated"], cfg["topk_proposals"]))
+    if cfg["topk_proposals"] > ops.TRACK_MAX_K or cfg["memory_len"] > ops.TRACK_MAX_L or cfg["max_num"] > ops.TRACK_MAX_DEC:
+        raise ValueError("track: topk_proposals=%d / memory_len=%d / max_num=%d beyond far3d_track_update's %d / %d / %d" %
+                         (cfg["topk_proposals"], cfg["memory_len"], cfg["max_num"], ops.TRACK_MAX_K, ops.TRACK_MAX_L, ops.TRACK_MAX_DEC))
+    return dict(birth_thr=thr)
 
 
 def dwsep_layers(cfg, precision):
@@ -243,6 +270,7 @@ class Far3DEngine:
         self.mem = None
         self.prev_scene = None
         self.md_k = multi_depth_topk(self.cfg)
+        self.track = track_options(self.cfg)      # None, or dict(birth_thr): mem["track"] / _track_next exist, the result carries track ids
         self.roi_dw = bool(self.cfg.get("roi_depthwise", False))
         self.depth_level = int(self.cfg.get("depth_level", 0) or 0)
         if not 0 <= self.depth_level < len(self.cfg["strides"]):
@@ -808,12 +836,25 @@ class Far3DEngine:
         self.mem = dict(emb=torch.zeros(1, Lm, E, device=dev), ref=torch.zeros(1, Lm, 3, device=dev),
                         ts=torch.zeros(1, Lm, 1, device=dev, dtype=torch.float64), pose=torch.zeros(1, Lm, 4, 4, device=dev),
                         velo=torch.zeros(1, Lm, 2, device=dev))
+        if self.track is not None:
+            # one id per memory slot (0: none), zeroed with the memory; the counter of the next id lives beside it: a scene change
+            # does not reset it, so an id is never used twice (reset_tracks)
+            self.mem["track"] = torch.zeros(1, Lm, dtype=torch.int64, device=dev)
+            self._track_next = torch.ones(1, 1, dtype=torch.int64, device=dev)
         self._mem_valid = False
 
     def reset_memory(self):
         """Forget the streaming memory (detectors/far3d.py:252-257): the next frame is treated as the first of a scene."""
         self._mem_valid = False
         self.prev_scene = None
+
+    def reset_tracks(self):
+        """Start the track ids at 1 again and forget the streaming memory (ids of the old numbering must not survive in it).  A scene
+        change alone never resets the counter."""
+        if self.track is None:
+            raise ValueError("reset_tracks: tracking is off (cfg track=None)")
+        self._track_next.fill_(1)
+        self.reset_memory()
 
     # ------------------------------------------------------------------------------------------ a7/a8: decoder
     def _row_chains(self, packed):
@@ -1306,10 +1347,14 @@ class Far3DEngine:
         return cls, linear(linear(rr, self.reg_b[1].pc, act="relu", out_dtype=at), self.reg_b[2].pc)
 
     @staticmethod
-    def _head_result(hs, all_cls, all_box, outs_dec, idx, result):
-        """One stream's `outs` of the head (hs: its _head_prepare result)."""
-        return dict(all_cls_scores=all_cls, all_bbox_preds=all_box, outs_dec=outs_dec, num_adaptive=hs.M, num_adaptive_dev=hs.m_dev,
+    def _head_result(hs, all_cls, all_box, outs_dec, idx, result, scores=None):
+        """One stream's `outs` of the head (hs: its _head_prepare result).  scores (tracking on): the score plane memory_topk ranked and
+        the births were judged on, as `memory_scores`."""
+        outs = dict(all_cls_scores=all_cls, all_bbox_preds=all_box, outs_dec=outs_dec, num_adaptive=hs.M, num_adaptive_dev=hs.m_dev,
                     feat_flatten=hs.tokens, reference_points=hs.ref, memory_topk=idx, result=result)
+        if scores is not None:
+            outs["memory_scores"] = scores
+        return outs
 
     def _head_finish(self, hs, outs_dec):
         """The part of head_stage behind the decoder: the shared cls / reg heads over all layers (_head_branches, or the row chain),
@@ -1327,18 +1372,31 @@ class Far3DEngine:
         all_box = box_flat.view(nl, 1, A, cfg["code_size"])
         # ---- a11: memory post-update (farhead.py:479-508): top-k by max-class score, push, truncate, ego warp -- in place
         # (the top-k rides in the decode's launch as a second workgroup: far3d_decode_topk_mem -- both rank the last layer's outputs)
-        result, idx = self.decode(all_cls, all_box, mem_scores=sc, mem_K=cfg["topk_proposals"])
+        if self.track is None:
+            result, idx = self.decode(all_cls, all_box, mem_scores=sc, mem_K=cfg["topk_proposals"])
+        else:           # the same decode + the boxes' query rows, then the ids: the one-stream case of the streams path
+            results, idx = self.decode_streams(all_cls[-1], all_box[-1], sc[None], cfg["topk_proposals"], tracked=True)
+            self._track_update(results, idx, sc[None], hs, self.mem["track"], self._track_next)
+            result, idx = {k: v[0] for k, v in results.items()}, idx[0]
         ops.memory_post_update(hs.m, idx, outs_dec[-1], all_box[-1][0], hs.dd["ego_pose"], hs.dd["timestamp"], self.mem)
-        return self._head_result(hs, all_cls, all_box, outs_dec, idx, result)
+        return self._head_result(hs, all_cls, all_box, outs_dec, idx, result, sc if self.track is not None else None)
 
-    def _head_finish_streams(self, hss, outs_dec, enter):
+    def _track_update(self, results, idx, scores, hs, mem_track, next_id):
+        """One far3d_track_update launch for the B streams of results / idx / scores (leading B): the streams' mem_track (B, L) and
+        next_id (B, 1) are updated in place, results gains track_ids (B, Kdec).  The propagated rows are the last num_propagated of the A."""
+        P = self.cfg["num_propagated"]
+        results["track_ids"] = ops.track_update(idx, scores, mem_track, next_id, hs.A - P, P, self.track["birth_thr"],
+                                                query_idx=results["query_idx"])
+
+    def _head_finish_streams(self, hss, outs_dec, enter, track=None):
         """_head_finish for B scene streams (streams.StreamBatch): hss the B _head_prepare results, outs_dec decoder_streams' result
         (B, layers, A, E), enter(b) a context manager that makes the engine stream b (its buffer set and streaming memory).  Returns the
         B result dicts of _head_finish, bit for bit.  The row-local work runs once over all streams' rows on (B, layers * A, .)
         buffers: ONE gathering copy of the decoder's (layers, B, A, E) rows into stream-major order, nan_to_num, _head_finish's own
         unfused cls / reg branches (_head_branches; StreamBatch refuses fused_rows) through ops.linear_streams (the tile of ONE stream's
         layers * A rows); the decode and the memory update's top-k of all streams are ONE far3d_decode_topk_mem_streams launch.  Per
-        stream stay head_finalize and memory_post_update."""
+        stream stay head_finalize and memory_post_update.  track (tracking on): the streams' (mem_track (B, L), next_id (B, 1)), updated by
+        ONE far3d_track_update launch."""
         cfg = self.cfg
         E, nl, ncls, code = cfg["embed_dims"], cfg["num_layers"], cfg["num_classes"], cfg["code_size"]
         B, A = len(hss), hss[0].A
@@ -1348,21 +1406,27 @@ class Far3DEngine:
         BOX, SC = buf("box", (B, nl * A, code), torch.float32), buf("score", (B, A), torch.float32)
         for b, hs in enumerate(hss):
             ops.head_finalize(rr[b], hs.ref, CLS[b], cfg["pc_range"], nl, ncls, hole=hs.hole, out=(BOX[b], SC[b]))
-        results, idx = self.decode_streams(CLS.view(B, nl, A, ncls)[:, -1], BOX.view(B, nl, A, code)[:, -1], SC, cfg["topk_proposals"])
+        results, idx = self.decode_streams(CLS.view(B, nl, A, ncls)[:, -1], BOX.view(B, nl, A, code)[:, -1], SC, cfg["topk_proposals"],
+                                           tracked=self.track is not None)
+        if self.track is not None:
+            self._track_update(results, idx, SC, hss[0], *track)
         res = []
         for b, hs in enumerate(hss):
             all_cls, all_box = CLS[b].view(nl, 1, A, ncls), BOX[b].view(nl, 1, A, code)
             with enter(b):
                 ops.memory_post_update(hs.m, idx[b], OD[b, -1], all_box[-1][0], hs.dd["ego_pose"], hs.dd["timestamp"], self.mem)
-            res.append(self._head_result(hs, all_cls, all_box, OD[b], idx[b], {k: v[b] for k, v in results.items()}))
+            res.append(self._head_result(hs, all_cls, all_box, OD[b], idx[b], {k: v[b] for k, v in results.items()},
+                                         SC[b] if self.track is not None else None))
         return res
 
-    def decode_streams(self, cls_last, box_last, mem_scores, mem_K):
+    def decode_streams(self, cls_last, box_last, mem_scores, mem_K, tracked=False):
         """`decode` of B scene streams in one launch: cls_last (B, A, num_classes) / box_last (B, A, code_size) the last layer's logits
-        and boxes, mem_scores (B, A) -- views with contiguous streams.  -> (dict of (B, .) results, idx (B, mem_K))."""
+        and boxes, mem_scores (B, A) -- views with contiguous streams.  -> (dict of (B, .) results, idx (B, mem_K)).  tracked: the
+        dict also holds query_idx (B, K), the query row of every box (ops.decode_topk_tracked)."""
         B, A, ncls = cls_last.shape
         K, ws, rng = self._decode_args(A * ncls, B)
-        return ops.decode_topk_mem_streams(cls_last, box_last, K, rng, mem_scores, mem_K, workspace=ws)
+        fn = ops.decode_topk_tracked if tracked else ops.decode_topk_mem_streams
+        return fn(cls_last, box_last, K, rng, mem_scores, mem_K, workspace=ws)
 
     def _stage_inputs(self, data):
         """Copy the frame's inputs into static device buffers (so that a captured graph can be replayed on them)."""

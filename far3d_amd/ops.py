@@ -2034,7 +2034,7 @@ def memory_prepare(state, ego_pose_inv, timestamp, pseudo_ref, dim_t256, prev_ex
         if pseudo_ref.shape[0] < P or pseudo_ref.shape[1] != 3:
             raise ValueError("memory_prepare: pseudo_ref must be (>= %d, 3) (got %s)" % (P, tuple(pseudo_ref.shape)))
     dev = state["emb"].device
-    m = {k: torch.empty_like(v) for k, v in state.items()}
+    m = {k: torch.empty_like(state[k]) for k, _, _ in _MEM_KEYS}      # the kernel's five planes (an engine's memory may carry more keys)
     temp_ref = temp_ref_out if temp_ref_out is not None else torch.empty((L, 3), dtype=torch.float32, device=dev)
     if tuple(temp_ref.shape) != (L, 3) or not temp_ref.is_contiguous():
         raise ValueError("memory_prepare: temp_ref_out must be a contiguous (L,3) tensor")
@@ -2223,6 +2223,35 @@ def decode_topk(cls_last, box_last, K, post_center_range, workspace=None, mem_sc
     return res
 
 
+def _decode_streams(who, cls_last, box_last, K, post_center_range, mem_scores, mem_K, workspace, tracked):
+    """The checks, outputs and call of decode_topk_mem_streams (tracked False) and decode_topk_tracked (True: + query_idx)."""
+    lib = _lib.require_device()
+    for t, name in ((cls_last, "cls_last"), (box_last, "box_last")):
+        if t.dim() != 3 or t.dtype != torch.float32 or not t.is_cuda or not t[0].is_contiguous():
+            raise ValueError("%s: %s must be a (B, A, C) float32 device tensor with contiguous streams" % (who, name))
+    if mem_scores.dim() != 2 or mem_scores.dtype != torch.float32 or not mem_scores.is_cuda or mem_scores.stride(1) != 1:
+        raise ValueError("%s: mem_scores must be a (B, n) float32 device tensor with unit inner stride" % who)
+    B, A, ncls = cls_last.shape
+    code = box_last.shape[2]
+    if box_last.shape[:2] != (B, A) or mem_scores.shape[0] != B:
+        raise ValueError("%s: cls_last %s, box_last %s and mem_scores %s disagree on (B, A)" %
+                         (who, tuple(cls_last.shape), tuple(box_last.shape), tuple(mem_scores.shape)))
+    K, mem_K, dev = int(K), int(mem_K), cls_last.device
+    res, workspace, need = _decode_outputs(dev, A * ncls, code, K, workspace, B)
+    outs = [res[k] for k in ("boxes_3d", "scores_3d", "labels_3d", "keep")]
+    idx = torch.empty((B, mem_K), dtype=torch.int64, device=dev)
+    rk, rp = _host_f32(list(post_center_range))
+    strides = (ctypes.c_long * 8)(cls_last.stride(0), box_last.stride(0), *[t.stride(0) for t in outs], mem_scores.stride(0), idx.stride(0))
+    args = (_ptr(cls_last), _ptr(box_last), B, A, ncls, code, K, rp, *[_ptr(t) for t in outs], _opt_ptr(workspace), need, _ptr(mem_scores),
+            mem_scores.shape[1], mem_K, _ptr(idx), ctypes.cast(strides, ctypes.c_void_p))
+    if tracked:
+        q = res["query_idx"] = torch.empty((B, K), dtype=torch.int32, device=dev)
+        _lib.check(lib.far3d_decode_topk_tracked(*args, _ptr(q), q.stride(0), _stream(cls_last)), "far3d_decode_topk_tracked")
+    else:
+        _lib.check(lib.far3d_decode_topk_mem_streams(*args, _stream(cls_last)), "far3d_decode_topk_mem_streams")
+    return res, idx
+
+
 def decode_topk_mem_streams(cls_last, box_last, K, post_center_range, mem_scores, mem_K, workspace=None):
     """decode_topk(..., mem_scores, mem_K) for B scene streams in ONE launch of 2 * B workgroups (far3d_decode_topk_mem_streams):
     cls_last (B, A, ncls), box_last (B, A, code), mem_scores (B, n) f32, each stream's block contiguous, any stride between the blocks (so
@@ -2230,28 +2259,50 @@ def decode_topk_mem_streams(cls_last, box_last, K, post_center_range, mem_scores
     bool), idx (B, mem_K) i64); [b] of each has the bits of the one-stream call on stream b's operands, whatever B is.  Shapes outside
     the fused launch (A * ncls > 40960 or n > 4096) run the one-stream entry per stream; workspace: optional uint8 device buffer of
     B * decode_ws_bytes(A * ncls, K) bytes for that case (allocated here when needed and not given)."""
+    return _decode_streams("decode_topk_mem_streams", cls_last, box_last, K, post_center_range, mem_scores, mem_K, workspace, False)
+
+
+def decode_topk_tracked(cls_last, box_last, K, post_center_range, mem_scores, mem_K, workspace=None):
+    """decode_topk_mem_streams whose dict also holds query_idx (B, K) int32: the query row every decoded box came from (its flat index
+    in cls_last // ncls; far3d_decode_topk_tracked).  Same arguments; every other output has the bits of decode_topk_mem_streams."""
+    return _decode_streams("decode_topk_tracked", cls_last, box_last, K, post_center_range, mem_scores, mem_K, workspace, True)
+
+
+TRACK_MAX_K, TRACK_MAX_L, TRACK_MAX_DEC = 1024, 4096, 1024     # csrc/track.hip
+
+
+def track_update(topk_idx, score, mem_track, next_id, row_start, num_propagated, birth_thr=0.0, query_idx=None):
+    """Track ids of one frame for B scene streams in ONE launch (far3d_track_update; the contract is in include/far3d_hip.h and,
+    executable, in tests/track_refs.py).  topk_idx (B, K) int64 the memory update's ranked rows, score (B, A) f32 head_finalize's score
+    plane (probabilities; -inf in a hole), mem_track (B, L) int64 and next_id (B, 1) int64 the streams' state, UPDATED IN PLACE;
+    row_start: the first propagated query row (num_query + adaptive rows); birth_thr: a probability.  Each stream's block contiguous,
+    any stride between the blocks.  query_idx (B, Kdec) int32 (decode_topk_tracked) -> returns track_ids (B, Kdec) int64; None -> None."""
     lib = _lib.require_device()
-    for t, name in ((cls_last, "cls_last"), (box_last, "box_last")):
-        if t.dim() != 3 or t.dtype != torch.float32 or not t.is_cuda or not t[0].is_contiguous():
-            raise ValueError("decode_topk_mem_streams: %s must be a (B, A, C) float32 device tensor with contiguous streams" % name)
-    if mem_scores.dim() != 2 or mem_scores.dtype != torch.float32 or not mem_scores.is_cuda or mem_scores.stride(1) != 1:
-        raise ValueError("decode_topk_mem_streams: mem_scores must be a (B, n) float32 device tensor with unit inner stride")
-    B, A, ncls = cls_last.shape
-    code = box_last.shape[2]
-    if box_last.shape[:2] != (B, A) or mem_scores.shape[0] != B:
-        raise ValueError("decode_topk_mem_streams: cls_last %s, box_last %s and mem_scores %s disagree on (B, A)" %
-                         (tuple(cls_last.shape), tuple(box_last.shape), tuple(mem_scores.shape)))
-    K, mem_K, dev = int(K), int(mem_K), cls_last.device
-    res, workspace, need = _decode_outputs(dev, A * ncls, code, K, workspace, B)
-    outs = [res[k] for k in ("boxes_3d", "scores_3d", "labels_3d", "keep")]
-    idx = torch.empty((B, mem_K), dtype=torch.int64, device=dev)
-    rk, rp = _host_f32(list(post_center_range))
-    strides = (ctypes.c_long * 8)(cls_last.stride(0), box_last.stride(0), *[t.stride(0) for t in outs], mem_scores.stride(0), idx.stride(0))
-    _lib.check(lib.far3d_decode_topk_mem_streams(_ptr(cls_last), _ptr(box_last), B, A, ncls, code, K, rp, *[_ptr(t) for t in outs],
-                                                 _opt_ptr(workspace), need, _ptr(mem_scores), mem_scores.shape[1], mem_K, _ptr(idx),
-                                                 ctypes.cast(strides, ctypes.c_void_p), _stream(cls_last)),
-               "far3d_decode_topk_mem_streams")
-    return res, idx
+    for t, name, dt in ((topk_idx, "topk_idx", torch.int64), (score, "score", torch.float32), (mem_track, "mem_track", torch.int64),
+                        (next_id, "next_id", torch.int64)) + (((query_idx, "query_idx", torch.int32),) if query_idx is not None else ()):
+        if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.dtype != dt or not t.is_cuda or t.stride(1) != 1:
+            raise ValueError("track_update: %s must be a (B, n) %s device tensor with unit inner stride" % (name, dt))
+    B, K = topk_idx.shape
+    A, L = score.shape[1], mem_track.shape[1]
+    if score.shape[0] != B or mem_track.shape[0] != B or tuple(next_id.shape) != (B, 1) or (query_idx is not None and query_idx.shape[0] != B):
+        raise ValueError("track_update: topk_idx %s, score %s, mem_track %s, next_id %s%s disagree on B (next_id is (B, 1))" %
+                         (tuple(topk_idx.shape), tuple(score.shape), tuple(mem_track.shape), tuple(next_id.shape),
+                          ", query_idx %s" % (tuple(query_idx.shape),) if query_idx is not None else ""))
+    P = int(num_propagated)
+    if P > K:
+        raise ValueError("track_update: num_propagated=%d > the %d ranked rows (topk_proposals): a memory slot that was carried over would "
+                         "be propagated a second time with the same id" % (P, K))
+    thr = float(birth_thr)
+    if not 0.0 <= thr <= 1.0:
+        raise ValueError("track_update: birth_thr=%r is a probability in [0, 1]" % (birth_thr,))
+    Kdec = 0 if query_idx is None else query_idx.shape[1]
+    ids = torch.empty((B, Kdec), dtype=torch.int64, device=score.device) if query_idx is not None else None
+    strides = (ctypes.c_long * 6)(topk_idx.stride(0), score.stride(0), query_idx.stride(0) if Kdec else 0, mem_track.stride(0),
+                                  next_id.stride(0), ids.stride(0) if Kdec else 0)
+    _lib.check(lib.far3d_track_update(_ptr(topk_idx), _ptr(score), _ptr(query_idx) if Kdec else None, _ptr(mem_track), _ptr(next_id),
+                                      _ptr(ids) if Kdec else None, B, A, K, L, Kdec, int(row_start), P, thr,
+                                      ctypes.cast(strides, ctypes.c_void_p), _stream(score)), "far3d_track_update")
+    return ids
 
 
 def camera_prep(lidar2img, intrinsics=None, extrinsics=None):

@@ -842,7 +842,8 @@ class FarHead(_SchemaModule):
 
     @torch.no_grad()
     def get_bboxes(self, preds_dicts, img_metas, rescale=False):
-        """ref farhead.py:1224-1245 -> [[boxes, scores, labels]] (boxes wrapped in img_metas[0]['box_type_3d'] when given)."""
+        """ref farhead.py:1224-1245 -> [[boxes, scores, labels]] (boxes wrapped in img_metas[0]['box_type_3d'] when given).  With
+        tracking on (the engine's cfg track) the list has a fourth entry, the kept boxes' track ids (int64; 0 = none)."""
         r = preds_dicts.get("_far3d_result")
         if r is None:
             r = self._eng.decode(preds_dicts["all_cls_scores"], preds_dicts["all_bbox_preds"])
@@ -851,7 +852,7 @@ class FarHead(_SchemaModule):
         box_type = img_metas[0].get("box_type_3d")
         if box_type is not None:
             boxes = box_type(boxes, boxes.size(-1))
-        return [[boxes, scores, labels]]
+        return [[boxes, scores, labels] + ([r["track_ids"][keep]] if "track_ids" in r else [])]
 
 
 # ------------------------------------------------------------------------------------------------ detector
@@ -861,7 +862,7 @@ class Far3D(nn.Module):
 
     def __init__(self, use_grid_mask=False, img_backbone=None, img_neck=None, pts_bbox_head=None, img_roi_head=None,
                  train_cfg=None, test_cfg=None, stride=(16,), position_level=(0,), aux_2d_only=True, single_test=False,
-                 pretrained=None, proposal_topk=None, proposal_capacity=None, **kwargs):
+                 pretrained=None, proposal_topk=None, proposal_capacity=None, track=None, **kwargs):
         super().__init__()
         self.img_backbone = BACKBONES.build(img_backbone)
         self.img_neck = NECKS.build(img_neck)
@@ -873,6 +874,7 @@ class Far3D(nn.Module):
         # build-side extension: the reference's threshold rule with static shapes -- rows reserved for the adaptive queries, count on
         # the device (None = the legacy form with a host sync on M); see INTEGRATION.md "Proposal modes"
         self.proposal_capacity = proposal_capacity
+        self.track = track                     # build-side extension: track ids (None = off; True or dict(birth_thr=p)); prepare(track=) too
         self.engine = None
         self.eval()
 
@@ -903,12 +905,17 @@ class Far3D(nn.Module):
             depthnet=dict(num_depth_bins=r.depthnet_config.get("num_depth_bins", 50), depth_min=r.depthnet_config.get("depth_min", 0.1),
                           depth_max=r.depthnet_config.get("depth_max", 110.0), stride=r.depthnet_config.get("stride", 8)),
             score_thr=r.threshold_score, proposal_topk=self.proposal_topk, proposal_capacity=self.proposal_capacity,
-            multi_depth=dict(h.multi_depth_config), roi_depthwise=r.use_depthwise, depth_level=r.depth_level)
+            multi_depth=dict(h.multi_depth_config), roi_depthwise=r.use_depthwise, depth_level=r.depth_level,
+            track=dict(birth_thr=0.0) if self.track is True else (self.track or None))
 
-    def prepare(self, device="cuda:0", precision="bf16", fused_dwsep=False):
+    def prepare(self, device="cuda:0", precision="bf16", fused_dwsep=False, track=None):
         """Fold BN, pack weights for the kernels, upload.  Must be called again after loading new weights.
         fused_dwsep: the engine's opt-in of the same name -- the depthwise-separable layers of a light model (depthwise backbone specs,
-        use_depthwise towers) as one launch each where the fused kernel takes them (engine.dwsep_layers)."""
+        use_depthwise towers) as one launch each where the fused kernel takes them (engine.dwsep_layers).
+        track: True or dict(birth_thr=p) switches the track ids on (None keeps the constructor's `track`): simple_test then adds
+        `track_ids_3d` to pts_bbox, FarHead.get_bboxes a fourth list entry (INTEGRATION.md "Track ids")."""
+        if track is not None:
+            self.track = track
         self.engine = _engine.Far3DEngine(self.state_dict(), self.engine_cfg(), device=device, precision=precision)
         self.engine.fused_dwsep = bool(fused_dwsep)
         return self
@@ -939,6 +946,8 @@ class Far3D(nn.Module):
         r = outs["result"]
         keep = r["keep"]
         res = dict(boxes_3d=r["boxes_3d"][keep], scores_3d=r["scores_3d"][keep], labels_3d=r["labels_3d"][keep])
+        if "track_ids" in r:
+            res["track_ids_3d"] = r["track_ids"][keep]      # kept rows only, like the boxes (0 = no identity)
         box_type = img_metas[0].get("box_type_3d")
         if box_type is not None:
             res["boxes_3d"] = box_type(res["boxes_3d"], res["boxes_3d"].size(-1))

@@ -19,6 +19,8 @@ proposal_capacity=R: the reference's shipped proposal rule at a static row count
 There every stream carries its own count of rows that hold a query, on the device: `proposals` runs per stream behind the joint
 backbone / FPN / 2D-head pass, the decoder pass hands the B counts to far3d_attention_streams and far3d_aggregate_batched_holes, and
 head_finalize masks each stream's hole.  No host sync in any mode; check_proposal_overflow() is the one that reads the flags.
+Track ids (engine cfg track): the streams' id queues and counters are rows of one tensor each, so head_batch updates all of them in ONE
+far3d_track_update launch; every stream's ids are those of a plain engine fed its frames.
 Everything else is refused with a ValueError that names the option."""
 import contextlib
 import functools
@@ -103,6 +105,14 @@ class StreamBatch:
         # per stream: the streaming memory (allocated once, zeroed in place on that stream's scene change) and the scene it is in
         self._state = [dict(mem={k: torch.zeros_like(v) for k, v in engine.mem.items()}, prev_scene=None, mem_valid=False)
                        for _ in range(self.streams)]
+        # track ids (engine cfg track): the streams' id queues are the rows of ONE (B, L) tensor and their counters of ONE (B, 1), so that
+        # a single far3d_track_update launch reaches all of them; stream b's mem["track"] is its row, zeroed with the rest of its memory
+        self._track = None
+        if engine.track is not None:
+            self._track = (torch.zeros((self.streams, engine.cfg["memory_len"]), dtype=torch.int64, device=engine.dev),
+                           torch.ones((self.streams, 1), dtype=torch.int64, device=engine.dev))
+            for b, st in enumerate(self._state):
+                st["mem"]["track"] = self._track[0][b:b + 1]
         self._tokens = None         # (B, N, S, 256): stream b's camera stage writes slice b, the decoder pass reads all of it
         self._images = None         # (B * N, 3, H, W): stream b stages its images in rows [b * N, (b + 1) * N) (camera_batch)
         for b in range(self.streams):
@@ -140,17 +150,29 @@ class StreamBatch:
         e, s = self.engine, self._state[b]
         keep = (e.mem, e.prev_scene, e._mem_valid)
         e.mem, e.prev_scene, e._mem_valid = s["mem"], s["prev_scene"], s["mem_valid"]
+        if self._track is not None:
+            keep_next, e._track_next = e._track_next, self._track[1][b:b + 1]
         try:
             with e.buffers(self._key(b)):
                 yield
         finally:
             s["prev_scene"], s["mem_valid"] = e.prev_scene, e._mem_valid
             e.mem, e.prev_scene, e._mem_valid = keep
+            if self._track is not None:
+                e._track_next = keep_next
 
     def reset_memory(self, b=None):
         """Forget the streaming memory of stream b (None: of every stream): its next frame is the first of a scene."""
         for i in (range(self.streams) if b is None else [int(b)]):
             self._state[i]["prev_scene"], self._state[i]["mem_valid"] = None, False
+
+    def reset_tracks(self, b=None):
+        """Far3DEngine.reset_tracks for stream b (None: every stream): its ids start at 1 again and its memory is forgotten."""
+        if self._track is None:
+            raise ValueError("reset_tracks: tracking is off (engine cfg track=None)")
+        for i in (range(self.streams) if b is None else [int(b)]):
+            self._track[1][i].fill_(1)
+        self.reset_memory(b)
 
     def memory(self, b):
         """Stream b's streaming memory (the dict of Far3DEngine.mem)."""
@@ -225,7 +247,7 @@ class StreamBatch:
             outs_dec = e.decoder_streams(pick("X2"), pick("x0"), pick("qpos"), pick("tokens"), pick("ref"), sts[0]["hw"], sts[0]["starts"],
                                          pick("lidar2img"), pad_hw, hss[0].A, holes=pick("hole"))
             if self.head_batch:
-                res = e._head_finish_streams(hss, outs_dec, self._stream)
+                res = e._head_finish_streams(hss, outs_dec, self._stream, track=self._track)
             else:
                 res = []
                 for b, hs in enumerate(hss):

@@ -766,6 +766,37 @@ int far3d_decode_topk_mem_streams(const float* cls_last, const float* box_last, 
                                   const float* post_center_range, float* boxes, float* scores, int64_t* labels, unsigned char* keep,
                                   void* workspace, long workspace_bytes, const float* mem_scores, int mem_n, int mem_K,
                                   int64_t* mem_idx_out, const long* batch_strides, void* stream);
+/* far3d_decode_topk_mem_streams that also says which query every decoded box came from: query_out (K) int32 per stream, stream b's
+ * query_stride elements behind stream 0's (>= K for B > 1) -- query_out[i] = (flat index of output i in cls_last) / num_classes, the
+ * row whose logit labels[i] ranked, with the decode's tie rule (the ranking is the same).  Both decode paths write it: the fused
+ * launch, and for A*num_classes > 40960 (or mem_n > 4096) per stream far3d_topk plus the one- or two-launch decode.  All other
+ * arguments, rules and outputs are those of far3d_decode_topk_mem_streams, bit for bit (the same kernels, instantiated with the
+ * extra store). */
+int far3d_decode_topk_tracked(const float* cls_last, const float* box_last, int B, int A, int num_classes, int code_size, int K,
+                              const float* post_center_range, float* boxes, float* scores, int64_t* labels, unsigned char* keep,
+                              void* workspace, long workspace_bytes, const float* mem_scores, int mem_n, int mem_K,
+                              int64_t* mem_idx_out, const long* batch_strides, int32_t* query_out, long query_stride, void* stream);
+
+/* Track ids: the identity of a detection across the frames of a scene stream, carried through the streaming memory.  One launch for
+ * B >= 1 streams (one workgroup each), no host read.  State per stream, updated IN PLACE: mem_track (L) int64, one id per memory slot
+ * (0 = no identity; the caller zeroes it wherever it zeroes the memory), and next_id (1) int64, the next id to hand out (starts at 1;
+ * never reset by a scene change, so an id is unique in its stream).  Per frame, from topk_idx (K) int64 -- the memory update's ranked
+ * query rows, far3d_decode_topk_mem's mem_idx_out -- and score (A) f32, far3d_head_finalize's score plane, which holds PROBABILITIES
+ * (max-class sigmoid; -inf in the rows of a hole):
+ *  1. id of query row r: mem_track[r - row_start] as it stood before this call if row_start <= r < row_start + P (a propagated query:
+ *     row_start = num_query + adaptive rows, the static split the engine uses in the hole modes too), else 0;
+ *  2. birth, in rank order: a ranked row with id 0 whose score is finite and >= birth_thr (a probability; compared as doubles) gets
+ *     next_id + (births before it in this frame); next_id advances by the number of births.  A row at -inf is never born;
+ *  3. queue: mem_track = cat(ids of topk_idx[0 .. K), old mem_track)[:L] -- far3d_memory_post_update's shift.  Every old slot is read
+ *     before any is written;
+ *  4. detections (Kdec > 0): track_ids[i] (Kdec) int64 = the id after step 2 of query row query_idx[i] (int32, far3d_decode_topk_tracked's
+ *     query_out), 0 for a row outside the top-k.  Two boxes of one query (two classes) share their id.
+ * K <= 1024, K <= L <= 4096, Kdec <= 1024, P <= K (a slot carried over in the queue must not be propagated again: its id would be
+ * live twice).  batch_strides: 6 longs on the HOST, elements between stream b and b + 1 of topk_idx, score, query_idx, mem_track,
+ * next_id, track_ids (for B > 1 none below one stream's extent). */
+int far3d_track_update(const int64_t* topk_idx, const float* score, const int32_t* query_idx, int64_t* mem_track, int64_t* next_id,
+                       int64_t* track_ids, int B, int A, int K, int L, int Kdec, int row_start, int P, double birth_thr,
+                       const long* batch_strides, void* stream);
 
 /* Per-frame camera calibration in one launch: img2lidar (N,4,4) = inverse(lidar2img) (ref models/dense_heads/farhead.py:798;
  * Gauss-Jordan with partial pivoting in f64) and c14 (N,14) = [fx/1e3, fy/1e3, extrinsics[:3,:4]] (ref farhead.py:553-556).
