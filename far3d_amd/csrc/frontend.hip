@@ -8,8 +8,6 @@
 //   far3d_proposal_gather  2D box decode (:491-501), depth-bin lookup + LID un-binning, un-projection to normalised 3D
 //                          reference points and the 257-wide context vector (ref models/dense_heads/farhead.py:571-610,
 //                          710-827, 521-531).
-//   far3d_row_affine_ln    out = gamma[row] * LN_noaffine(x[row]) + beta[row] (+ add[row]): the MLN(180) modulation of
-//                          queries / memory (ref models/utils/misc.py:153-190; farhead.py:292-303).
 #include "common.hpp"
 #include "prop_core.hpp"
 
@@ -587,47 +585,5 @@ extern "C" int far3d_compact_rows(const float* src, const int32_t* counts, int n
   hipLaunchKernelGGL(compact_rows_kernel, dim3(dst_rows), dim3(64), 0, (hipStream_t)stream, src, (const int*)counts, nblocks, rows_per_block,
                      D, dst, dst_rows, (int*)m_out, (int*)overflow_out);
   FAR3D_CHECK_LAUNCH("far3d_compact_rows");
-  return FAR3D_OK;
-}
-
-// ------------------------------------------------------------------------------------------ row-affine LayerNorm (MLN apply)
-__global__ __launch_bounds__(256) void row_affine_ln_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
-                                                            const float* __restrict__ beta, const float* __restrict__ add,
-                                                            float* __restrict__ y, int rows, int C, int ldx, int ldg, int lda,
-                                                            int ldy, float eps, int do_ln) {
-  const int lane = threadIdx.x & 63;
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= rows) return;
-  const int c = lane * 4;   // C == 256
-  float4 v = *reinterpret_cast<const float4*>(x + (long)row * ldx + c);
-  if (do_ln) {
-    float s = (v.x + v.y) + (v.z + v.w);
-    for (int o = 32; o >= 1; o >>= 1) s += __shfl_xor(s, o);
-    const float mean = s / C;
-    const float a = v.x - mean, b = v.y - mean, d = v.z - mean, e = v.w - mean;
-    float q = (a * a + b * b) + (d * d + e * e);
-    for (int o = 32; o >= 1; o >>= 1) q += __shfl_xor(q, o);
-    const float rstd = 1.f / sqrtf(q / C + eps);
-    v = make_float4(a * rstd, b * rstd, d * rstd, e * rstd);
-  }
-  const float4 g = *reinterpret_cast<const float4*>(gamma + (long)row * ldg + c);
-  const float4 b = *reinterpret_cast<const float4*>(beta + (long)row * ldg + c);
-  float4 o = make_float4(g.x * v.x + b.x, g.y * v.y + b.y, g.z * v.z + b.z, g.w * v.w + b.w);
-  if (add) {
-    const float4 a = *reinterpret_cast<const float4*>(add + (long)row * lda + c);
-    o.x += a.x; o.y += a.y; o.z += a.z; o.w += a.w;
-  }
-  *reinterpret_cast<float4*>(y + (long)row * ldy + c) = o;
-}
-
-// gamma/beta rows use stride ldg (0 = one shared row for all rows); add rows stride lda (0 = shared row).
-extern "C" int far3d_row_affine_ln(const float* x, const float* gamma, const float* beta, const float* add, float* y,
-                                   int rows, int C, int ldx, int ldg, int lda, int ldy, float eps, int do_ln, void* stream) {
-  FAR3D_CHECK_ARG(x && gamma && beta && y, "far3d_row_affine_ln: null argument");
-  FAR3D_CHECK_ARG(C == 256 && ldx % 4 == 0 && ldg % 4 == 0 && lda % 4 == 0 && ldy % 4 == 0, "far3d_row_affine_ln: C must be 256, strides multiples of 4");
-  if (rows <= 0) return FAR3D_OK;
-  hipLaunchKernelGGL(row_affine_ln_kernel, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, x, gamma, beta, add, y, rows,
-                     C, ldx, ldg, lda, ldy, eps, do_ln);
-  FAR3D_CHECK_LAUNCH("far3d_row_affine_ln");
   return FAR3D_OK;
 }

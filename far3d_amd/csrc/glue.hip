@@ -2,6 +2,7 @@
 // Each replaces a chain of 10-40 tiny tensor ops of the reference (every one of which costs a launch + a kernel
 // boundary on the GPU); arithmetic follows the reference expression by expression.
 #include "common.hpp"
+#include "row_core.hpp"
 
 #define TWO_PI_F 6.283185307179586f
 #define TWO_PI_D 6.283185307179586
@@ -267,12 +268,6 @@ extern "C" int far3d_add_cast(const float* a, const float* b, void* out_sum, int
   return FAR3D_OK;
 }
 
-__device__ __forceinline__ float glue_wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
 // ---------------------------------------------------------------- camera embedding -> camera part of the attention logits
 // For every decoder layer l and camera n (models/utils/detr3d_transformer.py:497-505, 531-538):
 //   e  = LayerNorm(ReLU(W2 ReLU(W0 lidar2img[n][:3,:].flatten() + b0) + b2))       cam_embed = Linear-ReLU-Linear-ReLU-LN
@@ -302,12 +297,12 @@ __global__ __launch_bounds__(256) void cam_embed_chain_kernel(const float* __res
   for (int k = 0; k < Hd; ++k) a += w2[k * 256] * h0[k];
   a = fmaxf(a, 0.f);
   // LayerNorm over the 256 channels (two-pass: mean, then centred variance)
-  float s = glue_wave_sum(a);
+  float s = wave_sum(a);
   if ((t & 63) == 0) red[t >> 6] = s;
   __syncthreads();
   const float mean = (red[0] + red[1] + red[2] + red[3]) * (1.f / 256.f);
   const float d = a - mean;
-  s = glue_wave_sum(d * d);
+  s = wave_sum(d * d);
   if ((t & 63) == 0) red[4 + (t >> 6)] = s;
   __syncthreads();
   const float var = (red[4] + red[5] + red[6] + red[7]) * (1.f / 256.f);

@@ -3,20 +3,43 @@
 //                             hand the next GEMM "query + query_pos" without another pass).  Decoder norms
 //                             (ref models/utils/detr3d_transformer.py:304-307,398-400), cls branch LN
 //                             (ref models/dense_heads/farhead.py:230-239), cam_embed LN (:506-512), time_embedding LN.
+//   far3d_row_affine_ln    -- out = gamma[row] * LN_noaffine(x[row]) + beta[row] (+ add[row]): the MLN(180) modulation of
+//                             queries / memory (ref models/utils/misc.py:153-190; farhead.py:292-303).
 //   far3d_groupnorm_nhwc   -- GroupNorm(32, C) + ReLU on NHWC maps (ref models/depth_predictor/depth_predictor.py:43-45).
 //   far3d_ese_nhwc         -- VoVNet eSE: x * hsigmoid(fc(avgpool(x))) (+ identity) (ref models/backbones/vovnet.py:173-185,232-236).
 //   far3d_maxpool3x3s2_nhwc-- MaxPool2d(3, 2, ceil_mode=True) (ref models/backbones/vovnet.py:249-250).
 #include "common.hpp"
 #include "dw_core.hpp"
+#include "row_core.hpp"
+#include <algorithm>
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-  return v;
+// ---- host side: what the entries of this file share.  An entry calls the rules in its own order with its own name: the order decides
+// which message a call with two faults gets.
+namespace {
+// storage code -> f(T()); F32 = false for the kernels that exist for the two bf16 storages only
+template <bool F32 = true, typename F> inline void norm_for_storage(int dt, F f) {
+  if constexpr (F32)
+    if (dt == FAR3D_DT_F32) return f(float());
+  if (dt == FAR3D_DT_BF16_PAIR) f(pair_t()); else f(bf16_t());
 }
+inline bool pair_channels_ok(int dt, int C) { return dt != FAR3D_DT_BF16_PAIR || C % 32 == 0; }      // C against pair storage
+inline int storage_scale(int dt) { return dt == FAR3D_DT_BF16_PAIR ? 2 : 1; }                        // stored elements per logical channel
+inline int norm_check_storage(const char* who, int dt, bool channels_ok = true) {
+  FAR3D_CHECK_ARG((dt == FAR3D_DT_F32 || dt == FAR3D_DT_BF16 || dt == FAR3D_DT_BF16_PAIR) && channels_ok, "%s: unsupported dtype", who);
+  return FAR3D_OK;
+}
+inline bool multiples_of(long m, std::initializer_list<long> v) { return std::all_of(v.begin(), v.end(), [m](long s) { return s % m == 0; }); }
+inline bool aligned16(std::initializer_list<const void*> v) {      // NULL passes
+  return std::all_of(v.begin(), v.end(), [](const void* p) { return (uintptr_t)p % 16 == 0; });
+}
+// MaxPool2d(3, 2, ceil_mode=True): ceil((n - 3) / 2) + 1 outputs, the last window starting inside the input
+inline int pooled_size(int n) { const int e = (n - 3 + 1) / 2 + 1; return (e - 1) * 2 >= n ? e - 1 : e; }
+// grid of the element-wise kernels: one 4-channel piece per thread, a grid-stride loop past 8192 workgroups
+inline dim3 elementwise_grid(long total4) { return dim3((unsigned)std::min(8192L, (total4 + 255) / 256)); }
+}  // namespace
 
 // ---------------------------------------------------------------- LayerNorm
-template <int MAXV>  // float4 per lane; C <= 256 * MAXV
+template <int MAXV>  // float4 per lane; C <= 256 * MAXV.  The row's arithmetic: row_core.hpp
 __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
                                                         const float* __restrict__ beta, float* __restrict__ y, int rows,
                                                         int C, int ldx, int ldy, float eps, int act,
@@ -34,19 +57,14 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
   for (int i = 0; i < MAXV; ++i) {
     const int c = (lane + 64 * i) * 4;
     v[i] = c < C ? *reinterpret_cast<const float4*>(xr + c) : make_float4(0, 0, 0, 0);
-    s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
+    s += ln_lane_sum(v[i]);
   }
-  const float mean = wave_sum(s) / C;
+  const float mean = ln_mean(s, C);
   float q = 0.f;
 #pragma unroll
-  for (int i = 0; i < MAXV; ++i) {
-    const int c = (lane + 64 * i) * 4;
-    if (c < C) {
-      const float a = v[i].x - mean, b = v[i].y - mean, d = v[i].z - mean, e = v[i].w - mean;
-      q += (a * a + b * b) + (d * d + e * e);
-    }
-  }
-  const float rstd = 1.f / sqrtf(wave_sum(q) / C + eps);
+  for (int i = 0; i < MAXV; ++i)
+    if ((lane + 64 * i) * 4 < C) q += ln_lane_squares(v[i], mean);
+  const float rstd = ln_rstd(q, C, eps);
 #pragma unroll
   for (int i = 0; i < MAXV; ++i) {
     const int c = (lane + 64 * i) * 4;
@@ -54,11 +72,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
       float4 g = make_float4(1, 1, 1, 1), b = make_float4(0, 0, 0, 0);
       if (gamma) g = *reinterpret_cast<const float4*>(gamma + c);
       if (beta) b = *reinterpret_cast<const float4*>(beta + c);
-      float4 o;
-      o.x = (v[i].x - mean) * rstd * g.x + b.x;
-      o.y = (v[i].y - mean) * rstd * g.y + b.y;
-      o.z = (v[i].z - mean) * rstd * g.z + b.z;
-      o.w = (v[i].w - mean) * rstd * g.w + b.w;
+      float4 o = ln_apply(v[i], mean, rstd, g, b);
       if (act == 1) { o.x = fmaxf(o.x, 0.f); o.y = fmaxf(o.y, 0.f); o.z = fmaxf(o.z, 0.f); o.w = fmaxf(o.w, 0.f); }
       *reinterpret_cast<float4*>(y + (long)row * ldy + c) = o;
       if (yb) {
@@ -104,6 +118,43 @@ extern "C" int far3d_layernorm_rows(const float* x, const float* gamma, const fl
                                     int y2_dt, void* yb, int ldyb, int yb_dt, const int32_t* out_rows, void* stream) {
   FAR3D_CHECK_ARG(out_rows && (y2 || yb), "far3d_layernorm_rows: needs out_rows and at least one of y2 / yb");
   return layernorm_launch(x, gamma, beta, y, rows, C, ldx, ldy, eps, act, add, lda, y2, ldy2, y2_dt, yb, ldyb, yb_dt, out_rows, stream);
+}
+
+// ---------------------------------------------------------------- row-affine LayerNorm (MLN apply)
+__global__ __launch_bounds__(256) void row_affine_ln_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
+                                                            const float* __restrict__ beta, const float* __restrict__ add,
+                                                            float* __restrict__ y, int rows, int C, int ldx, int ldg, int lda,
+                                                            int ldy, float eps, int do_ln) {
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const int c = lane * 4;   // C == 256
+  float4 v = *reinterpret_cast<const float4*>(x + (long)row * ldx + c);
+  if (do_ln) {
+    const float mean = ln_mean(ln_lane_sum(v), C);
+    const float rstd = ln_rstd(ln_lane_squares(v, mean), C, eps);
+    v = make_float4((v.x - mean) * rstd, (v.y - mean) * rstd, (v.z - mean) * rstd, (v.w - mean) * rstd);
+  }
+  const float4 g = *reinterpret_cast<const float4*>(gamma + (long)row * ldg + c);
+  const float4 b = *reinterpret_cast<const float4*>(beta + (long)row * ldg + c);
+  float4 o = make_float4(g.x * v.x + b.x, g.y * v.y + b.y, g.z * v.z + b.z, g.w * v.w + b.w);
+  if (add) {
+    const float4 a = *reinterpret_cast<const float4*>(add + (long)row * lda + c);
+    o.x += a.x; o.y += a.y; o.z += a.z; o.w += a.w;
+  }
+  *reinterpret_cast<float4*>(y + (long)row * ldy + c) = o;
+}
+
+// gamma/beta rows use stride ldg (0 = one shared row for all rows); add rows stride lda (0 = shared row).
+extern "C" int far3d_row_affine_ln(const float* x, const float* gamma, const float* beta, const float* add, float* y,
+                                   int rows, int C, int ldx, int ldg, int lda, int ldy, float eps, int do_ln, void* stream) {
+  FAR3D_CHECK_ARG(x && gamma && beta && y, "far3d_row_affine_ln: null argument");
+  FAR3D_CHECK_ARG(C == 256 && ldx % 4 == 0 && ldg % 4 == 0 && lda % 4 == 0 && ldy % 4 == 0, "far3d_row_affine_ln: C must be 256, strides multiples of 4");
+  if (rows <= 0) return FAR3D_OK;
+  hipLaunchKernelGGL(row_affine_ln_kernel, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, x, gamma, beta, add, y, rows,
+                     C, ldx, ldg, lda, ldy, eps, do_ln);
+  FAR3D_CHECK_LAUNCH("far3d_row_affine_ln");
+  return FAR3D_OK;
 }
 
 // ---------------------------------------------------------------- per-(image, channel) sums over H*W
@@ -160,30 +211,23 @@ __global__ __launch_bounds__(256) void chan_sums_kernel(const T* __restrict__ x,
   }
 }
 
-// number of partial-sum workgroups per image: >= 64 Ki elements per workgroup, at most FAR3D_SUMS_MAX_PARTS
-static int chan_sums_parts(int HW, int C) {
-  long n = ((long)HW * C) >> 16;
-  if (n < 1) n = 1;
-  if (n > FAR3D_SUMS_MAX_PARTS) n = FAR3D_SUMS_MAX_PARTS;
-  const int rstep = 256 / (C / 4);
-  int rows_per_block = (int)((HW + n - 1) / n);
-  rows_per_block = ((rows_per_block + 8 * rstep - 1) / (8 * rstep)) * (8 * rstep);
-  return (HW + rows_per_block - 1) / rows_per_block;
+// Partial-sum workgroups per image (>= 64 Ki elements per workgroup, at most FAR3D_SUMS_MAX_PARTS) and the rows each of them takes:
+// a multiple of the 8 * rstep rows of one unrolled pass.  nparts = ceil(HW / rows_per_block), so no workgroup is empty.
+struct ChanSumsPlan { int nparts, rows_per_block; };
+static ChanSumsPlan chan_sums_plan(int HW, int C) {
+  const long n = std::min<long>(FAR3D_SUMS_MAX_PARTS, std::max<long>(1, ((long)HW * C) >> 16));
+  const int pass = 8 * (256 / (C / 4));
+  const int rows_per_block = (int)(((HW + n - 1) / n + pass - 1) / pass) * pass;
+  return {(HW + rows_per_block - 1) / rows_per_block, rows_per_block};
 }
 
 static int launch_chan_sums(const void* x, int dt, float* part, int N, int HW, int C, int ldx, long img_stride, hipStream_t st) {
-  const int nblk = chan_sums_parts(HW, C);
-  const int rstep = 256 / (C / 4);
-  int rows_per_block = (HW + nblk - 1) / nblk;
-  rows_per_block = ((rows_per_block + 8 * rstep - 1) / (8 * rstep)) * (8 * rstep);
-  dim3 grid(nblk, N), block(256);
-  if (dt == FAR3D_DT_F32)
-    hipLaunchKernelGGL(chan_sums_kernel<float>, grid, block, 0, st, (const float*)x, part, HW, C, ldx, img_stride, rows_per_block);
-  else if (dt == FAR3D_DT_BF16_PAIR)
-    hipLaunchKernelGGL(chan_sums_kernel<pair_t>, grid, block, 0, st, (const pair_t*)x, part, HW, C, ldx, img_stride, rows_per_block);
-  else
-    hipLaunchKernelGGL(chan_sums_kernel<bf16_t>, grid, block, 0, st, (const bf16_t*)x, part, HW, C, ldx, img_stride, rows_per_block);
-  return nblk;
+  const ChanSumsPlan p = chan_sums_plan(HW, C);
+  norm_for_storage(dt, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(chan_sums_kernel<T>, dim3(p.nparts, N), dim3(256), 0, st, (const T*)x, part, HW, C, ldx, img_stride, p.rows_per_block);
+  });
+  return p.nparts;
 }
 
 // ---------------------------------------------------------------- eSE
@@ -324,30 +368,25 @@ __global__ __launch_bounds__(256) void ese_apply_kernel(const T* __restrict__ x,
 extern "C" int far3d_ese_nhwc(const void* x, int dt, const float* fcw, const float* fcb, const void* identity, void* y,
                               float* scratch, int N, int HW, int C, int ldx, long x_img_stride, int ldi,
                               long i_img_stride, int ldy, long y_img_stride, long long* chan_sums, void* stream) {
-  FAR3D_CHECK_ARG(x && fcw && fcb && y && scratch, "far3d_ese_nhwc: null pointer argument");
-  FAR3D_CHECK_ARG(!chan_sums || dt != FAR3D_DT_F32, "far3d_ese_nhwc: fixed-point channel sums describe a bf16 / pair map");
-  FAR3D_CHECK_ARG(N > 0 && HW > 0 && C > 0 && C % 4 == 0 && C <= 1024 && ldx % 4 == 0 && ldy % 4 == 0 && (!identity || ldi % 4 == 0),
-                  "far3d_ese_nhwc: bad sizes (C=%d must be a multiple of 4, <= 1024)", C);
-  FAR3D_CHECK_ARG(dt == FAR3D_DT_F32 || dt == FAR3D_DT_BF16 || dt == FAR3D_DT_BF16_PAIR, "far3d_ese_nhwc: unsupported dtype");
-  FAR3D_CHECK_ARG(dt != FAR3D_DT_BF16_PAIR || C % 32 == 0, "far3d_ese_nhwc: pair storage needs C %% 32 == 0");
+  const char* who = "far3d_ese_nhwc";
+  FAR3D_CHECK_ARG(x && fcw && fcb && y && scratch, "%s: null pointer argument", who);
+  FAR3D_CHECK_ARG(!chan_sums || dt != FAR3D_DT_F32, "%s: fixed-point channel sums describe a bf16 / pair map", who);
+  FAR3D_CHECK_ARG(N > 0 && HW > 0 && C > 0 && C <= 1024 && multiples_of(4, {C, ldx, ldy, identity ? ldi : 0}),
+                  "%s: bad sizes (C=%d must be a multiple of 4, <= 1024)", who, C);
+  if (const int rc = norm_check_storage(who, dt)) return rc;
+  FAR3D_CHECK_ARG(pair_channels_ok(dt, C), "%s: pair storage needs C %% 32 == 0", who);
   hipStream_t st = (hipStream_t)stream;
   float* sums = scratch;
   float* gate = scratch + (long)N * FAR3D_SUMS_MAX_PARTS * C * 2;
   const int nparts = chan_sums ? 0 : launch_chan_sums(x, dt, sums, N, HW, C, ldx, x_img_stride, st);
   hipLaunchKernelGGL(ese_gate_kernel, dim3((C + 15) / 16, N), dim3(256), 0, st, sums, fcw, fcb, gate, C, 1.f / HW, nparts, (const long long*)chan_sums);
   const long total4 = (long)N * HW * (C / 4);
-  long blocks = (total4 + 255) / 256;
-  if (blocks > 8192) blocks = 8192;
-  if (dt == FAR3D_DT_F32)
-    hipLaunchKernelGGL(ese_apply_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, st, (const float*)x, gate,
-                       (const float*)identity, (float*)y, total4, C, HW, ldx, x_img_stride, ldi, i_img_stride, ldy, y_img_stride, chan_sums, N * C);
-  else if (dt == FAR3D_DT_BF16_PAIR)
-    hipLaunchKernelGGL(ese_apply_kernel<pair_t>, dim3((unsigned)blocks), dim3(256), 0, st, (const pair_t*)x, gate,
-                       (const pair_t*)identity, (pair_t*)y, total4, C, HW, ldx, x_img_stride, ldi, i_img_stride, ldy, y_img_stride, chan_sums, N * C);
-  else
-    hipLaunchKernelGGL(ese_apply_kernel<bf16_t>, dim3((unsigned)blocks), dim3(256), 0, st, (const bf16_t*)x, gate,
-                       (const bf16_t*)identity, (bf16_t*)y, total4, C, HW, ldx, x_img_stride, ldi, i_img_stride, ldy, y_img_stride, chan_sums, N * C);
-  FAR3D_CHECK_LAUNCH("far3d_ese_nhwc");
+  norm_for_storage(dt, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(ese_apply_kernel<T>, elementwise_grid(total4), dim3(256), 0, st, (const T*)x, gate, (const T*)identity, (T*)y, total4, C,
+                       HW, ldx, x_img_stride, ldi, i_img_stride, ldy, y_img_stride, chan_sums, N * C);
+  });
+  FAR3D_CHECK_LAUNCH(who);
   return FAR3D_OK;
 }
 
@@ -457,18 +496,17 @@ extern "C" int far3d_ese_fused_nhwc(const void* x, int dt, const float* fcw, con
                                     float* gate, int N, int H, int W, int C, int ldx, long x_img_stride, int ldi,
                                     long i_img_stride, int ldy, long y_img_stride, int Hp, int Wp, int ldp, long p_img_stride,
                                     long long* chan_sums, void* stream) {
-  FAR3D_CHECK_ARG(x && fcw && fcb && gate && chan_sums && (y || pooled), "far3d_ese_fused_nhwc: null pointer argument (y or pooled must be given)");
-  FAR3D_CHECK_ARG(dt == FAR3D_DT_BF16 || dt == FAR3D_DT_BF16_PAIR, "far3d_ese_fused_nhwc: bf16 or pair-stored maps (the fixed-point channel sums describe those)");
-  FAR3D_CHECK_ARG(N > 0 && H > 0 && W > 0 && C > 0 && C <= 1024 && C % (dt == FAR3D_DT_BF16_PAIR ? 32 : 8) == 0, "far3d_ese_fused_nhwc: bad sizes (C=%d)", C);
-  auto al = [](const void* p) { return ((uintptr_t)p % 16) == 0; };
-  FAR3D_CHECK_ARG(al(x) && ldx % 8 == 0 && x_img_stride % 8 == 0 && (!identity || (al(identity) && ldi % 8 == 0 && i_img_stride % 8 == 0)) &&
-                  (!y || (al(y) && ldy % 8 == 0 && y_img_stride % 8 == 0)) && (!pooled || (al(pooled) && ldp % 8 == 0 && p_img_stride % 8 == 0)) && al(gate),
-                  "far3d_ese_fused_nhwc: pointers and strides must be multiples of 16 bytes");
-  if (pooled) {      // ceil_mode output size: ceil((H-3)/2)+1, last window must start inside the input
-    int eh = (H - 3 + 1) / 2 + 1; if ((eh - 1) * 2 >= H) --eh;
-    int ew = (W - 3 + 1) / 2 + 1; if ((ew - 1) * 2 >= W) --ew;
-    FAR3D_CHECK_ARG(Hp == eh && Wp == ew, "far3d_ese_fused_nhwc: pooled size %dx%d != ceil-mode size %dx%d", Hp, Wp, eh, ew);
-  }
+  const char* who = "far3d_ese_fused_nhwc";
+  FAR3D_CHECK_ARG(x && fcw && fcb && gate && chan_sums && (y || pooled), "%s: null pointer argument (y or pooled must be given)", who);
+  FAR3D_CHECK_ARG(dt == FAR3D_DT_BF16 || dt == FAR3D_DT_BF16_PAIR, "%s: bf16 or pair-stored maps (the fixed-point channel sums describe those)", who);
+  FAR3D_CHECK_ARG(N > 0 && H > 0 && W > 0 && C > 0 && C <= 1024 && C % 8 == 0 && pair_channels_ok(dt, C), "%s: bad sizes (C=%d)", who, C);
+  FAR3D_CHECK_ARG(aligned16({x, identity, y, pooled, gate}) &&
+                  multiples_of(8, {ldx, x_img_stride, identity ? ldi : 0, identity ? i_img_stride : 0, y ? ldy : 0, y ? y_img_stride : 0,
+                                   pooled ? ldp : 0, pooled ? p_img_stride : 0}),
+                  "%s: pointers and strides must be multiples of 16 bytes", who);
+  if (pooled)
+    FAR3D_CHECK_ARG(Hp == pooled_size(H) && Wp == pooled_size(W), "%s: pooled size %dx%d != ceil-mode size %dx%d", who, Hp, Wp, pooled_size(H),
+                    pooled_size(W));
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(ese_gate_kernel, dim3((C + 15) / 16, N), dim3(256), 0, st, (const float*)nullptr, fcw, fcb, gate, C, 1.f / ((float)H * W), 0,
                      (const long long*)chan_sums);
@@ -482,19 +520,16 @@ extern "C" int far3d_ese_fused_nhwc(const void* x, int dt, const float* fcw, con
   int unit = 1;
   while ((256 * unit) % cq) ++unit;
   const long items = (long)(y ? H * W : Hp * Wp) * cq;
-  long db = (items + 4 * 256 - 1) / (4 * 256);
-  if (db > 1200) db = 1200;
+  long db = std::min(1200L, (items + 4 * 256 - 1) / (4 * 256));
   db = (db + unit - 1) / unit * unit;
   P.DB = (int)db;
-  dim3 grid((unsigned)P.DB, (unsigned)N);
-  if (dt == FAR3D_DT_BF16_PAIR) {
-    if (pooled) hipLaunchKernelGGL((ese_fused_kernel<pair_t, true>), grid, dim3(256), 0, st, P);
-    else hipLaunchKernelGGL((ese_fused_kernel<pair_t, false>), grid, dim3(256), 0, st, P);
-  } else {
-    if (pooled) hipLaunchKernelGGL((ese_fused_kernel<bf16_t, true>), grid, dim3(256), 0, st, P);
-    else hipLaunchKernelGGL((ese_fused_kernel<bf16_t, false>), grid, dim3(256), 0, st, P);
-  }
-  FAR3D_CHECK_LAUNCH("far3d_ese_fused_nhwc");
+  norm_for_storage<false>(dt, [&](auto t) {
+    auto launch = [&](auto pool) {
+      hipLaunchKernelGGL((ese_fused_kernel<decltype(t), decltype(pool)::value>), dim3((unsigned)P.DB, (unsigned)N), dim3(256), 0, st, P);
+    };
+    if (pooled) launch(std::true_type{}); else launch(std::false_type{});
+  });
+  FAR3D_CHECK_LAUNCH(who);
   return FAR3D_OK;
 }
 
@@ -547,30 +582,23 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const T* __restrict__ x, 
 
 extern "C" int far3d_groupnorm_nhwc(const void* x, int dt, const float* gamma, const float* beta, void* y, float* scratch,
                                     int N, int HW, int C, int groups, float eps, int relu, void* stream) {
-  FAR3D_CHECK_ARG(x && gamma && beta && y && scratch, "far3d_groupnorm_nhwc: null pointer argument");
-  FAR3D_CHECK_ARG(N > 0 && HW > 0 && C % 4 == 0 && C <= 1024 && groups > 0 && C % groups == 0, "far3d_groupnorm_nhwc: bad sizes C=%d groups=%d", C, groups);
-  FAR3D_CHECK_ARG(dt == FAR3D_DT_F32 || dt == FAR3D_DT_BF16 || (dt == FAR3D_DT_BF16_PAIR && C % 32 == 0), "far3d_groupnorm_nhwc: unsupported dtype");
-  const int cs = dt == FAR3D_DT_BF16_PAIR ? 2 : 1;      // stored elements per logical channel
+  const char* who = "far3d_groupnorm_nhwc";
+  FAR3D_CHECK_ARG(x && gamma && beta && y && scratch, "%s: null pointer argument", who);
+  FAR3D_CHECK_ARG(N > 0 && HW > 0 && C % 4 == 0 && C <= 1024 && groups > 0 && C % groups == 0, "%s: bad sizes C=%d groups=%d", who, C, groups);
+  if (const int rc = norm_check_storage(who, dt, pair_channels_ok(dt, C))) return rc;
+  FAR3D_CHECK_ARG(groups * 2 <= C, "%s: groups*2 must be <= C", who);      // gn_stats_kernel's rule; in front of the first launch
+  const int cs = storage_scale(dt);
   hipStream_t st = (hipStream_t)stream;
   float* sums = scratch;                                              // [N][nparts][C][2]
   float* stat = scratch + (long)N * FAR3D_SUMS_MAX_PARTS * C * 2;     // [N][groups][2]
   const int nparts = launch_chan_sums(x, dt, sums, N, HW, C, C * cs, (long)HW * C * cs, st);
-  FAR3D_CHECK_ARG(groups * 2 <= C, "far3d_groupnorm_nhwc: groups*2 must be <= C");
-  hipLaunchKernelGGL(gn_stats_kernel, dim3(N), dim3(256), 0, st, sums, stat, C, groups,
-                     1.f / ((float)HW * (C / groups)), eps, nparts);
+  hipLaunchKernelGGL(gn_stats_kernel, dim3(N), dim3(256), 0, st, sums, stat, C, groups, 1.f / ((float)HW * (C / groups)), eps, nparts);
   const long total4 = (long)N * HW * (C / 4);
-  long blocks = (total4 + 255) / 256;
-  if (blocks > 8192) blocks = 8192;
-  if (dt == FAR3D_DT_F32)
-    hipLaunchKernelGGL(gn_apply_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, st, (const float*)x, stat, gamma, beta,
-                       (float*)y, total4, C, groups, HW, relu);
-  else if (dt == FAR3D_DT_BF16_PAIR)
-    hipLaunchKernelGGL(gn_apply_kernel<pair_t>, dim3((unsigned)blocks), dim3(256), 0, st, (const pair_t*)x, stat, gamma, beta,
-                       (pair_t*)y, total4, C, groups, HW, relu);
-  else
-    hipLaunchKernelGGL(gn_apply_kernel<bf16_t>, dim3((unsigned)blocks), dim3(256), 0, st, (const bf16_t*)x, stat, gamma, beta,
-                       (bf16_t*)y, total4, C, groups, HW, relu);
-  FAR3D_CHECK_LAUNCH("far3d_groupnorm_nhwc");
+  norm_for_storage(dt, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(gn_apply_kernel<T>, elementwise_grid(total4), dim3(256), 0, st, (const T*)x, stat, gamma, beta, (T*)y, total4, C, groups, HW, relu);
+  });
+  FAR3D_CHECK_LAUNCH(who);
   return FAR3D_OK;
 }
 
@@ -604,23 +632,18 @@ __global__ __launch_bounds__(256) void maxpool_kernel(const T* __restrict__ x, T
 
 extern "C" int far3d_maxpool3x3s2_nhwc(const void* x, int dt, void* y, int N, int H, int W, int C, int Ho, int Wo, int ldy,
                                        long y_img_stride, void* stream) {
-  FAR3D_CHECK_ARG(x && y, "far3d_maxpool3x3s2_nhwc: null pointer argument");
-  FAR3D_CHECK_ARG(dt == FAR3D_DT_F32 || dt == FAR3D_DT_BF16 || (dt == FAR3D_DT_BF16_PAIR && C % 32 == 0), "far3d_maxpool3x3s2_nhwc: unsupported dtype");
-  FAR3D_CHECK_ARG(N > 0 && H > 0 && W > 0 && C % 4 == 0 && ldy >= C * (dt == FAR3D_DT_BF16_PAIR ? 2 : 1) && ldy % 4 == 0, "far3d_maxpool3x3s2_nhwc: bad sizes");
-  // ceil_mode output size: ceil((H-3)/2)+1, last window must start inside the input
-  int eh = (H - 3 + 1) / 2 + 1; if ((eh - 1) * 2 >= H) --eh;
-  int ew = (W - 3 + 1) / 2 + 1; if ((ew - 1) * 2 >= W) --ew;
-  FAR3D_CHECK_ARG(Ho == eh && Wo == ew, "far3d_maxpool3x3s2_nhwc: output %dx%d != ceil-mode size %dx%d", Ho, Wo, eh, ew);
+  const char* who = "far3d_maxpool3x3s2_nhwc";
+  FAR3D_CHECK_ARG(x && y, "%s: null pointer argument", who);
+  if (const int rc = norm_check_storage(who, dt, pair_channels_ok(dt, C))) return rc;
+  FAR3D_CHECK_ARG(N > 0 && H > 0 && W > 0 && C % 4 == 0 && ldy >= C * storage_scale(dt) && ldy % 4 == 0, "%s: bad sizes", who);
+  FAR3D_CHECK_ARG(Ho == pooled_size(H) && Wo == pooled_size(W), "%s: output %dx%d != ceil-mode size %dx%d", who, Ho, Wo, pooled_size(H),
+                  pooled_size(W));
   const long total4 = (long)N * Ho * Wo * (C / 4);
-  long blocks = (total4 + 255) / 256;
-  if (blocks > 8192) blocks = 8192;
-  hipStream_t st = (hipStream_t)stream;
-  if (dt == FAR3D_DT_F32)
-    hipLaunchKernelGGL(maxpool_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, st, (const float*)x, (float*)y, total4, C, H, W, Ho, Wo, ldy, y_img_stride);
-  else if (dt == FAR3D_DT_BF16_PAIR)
-    hipLaunchKernelGGL(maxpool_kernel<pair_t>, dim3((unsigned)blocks), dim3(256), 0, st, (const pair_t*)x, (pair_t*)y, total4, C, H, W, Ho, Wo, ldy, y_img_stride);
-  else
-    hipLaunchKernelGGL(maxpool_kernel<bf16_t>, dim3((unsigned)blocks), dim3(256), 0, st, (const bf16_t*)x, (bf16_t*)y, total4, C, H, W, Ho, Wo, ldy, y_img_stride);
-  FAR3D_CHECK_LAUNCH("far3d_maxpool3x3s2_nhwc");
+  norm_for_storage(dt, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(maxpool_kernel<T>, elementwise_grid(total4), dim3(256), 0, (hipStream_t)stream, (const T*)x, (T*)y, total4, C, H, W, Ho, Wo,
+                       ldy, y_img_stride);
+  });
+  FAR3D_CHECK_LAUNCH(who);
   return FAR3D_OK;
 }

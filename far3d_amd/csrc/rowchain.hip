@@ -20,11 +20,11 @@
 // contiguous KiB = 8 full lines and IS the B operand of a v_mfma_f32_16x16x32_bf16) -- no LDS staging, no barrier inside a
 // GEMM; a wave owns the column tiles t = wave + 8 i and keeps the next tile's 8 fragments in flight under the current
 // tile's 8 MFMAs.  fp32 accumulators; epilogues follow the unfused kernels' order (bias -> activation -> residual); the
-// LayerNorm is far3d_layernorm's arithmetic instruction for instruction (one wave per row, float4 per lane, the same
-// shuffle tree), so given the same GEMM result the normalised rows are bit-identical.  Rows never interact: a row's
-// output does not depend on which block or launch carries it (the query-sharded decoder relies on that).
+// LayerNorm is far3d_layernorm's own row (row_core.hpp), so given the same GEMM result the normalised rows are bit-identical.
+// Rows never interact: a row's output does not depend on which block or launch carries it (the query-sharded decoder relies on that).
 // bf16 operands only (the exact-fp32 / split-bf16 decoders keep the unfused path).
 #include "common.hpp"
+#include "row_core.hpp"
 
 typedef __attribute__((__vector_size__(8 * sizeof(__bf16)))) __bf16 bf16x8_t;
 typedef __attribute__((__vector_size__(4 * sizeof(float)))) float f32x4_t;
@@ -43,12 +43,6 @@ typedef __attribute__((__vector_size__(4 * sizeof(float)))) float f32x4_t;
 #define RC_LDS (RC_F_BYTES + RC_A0_BYTES + RC_A1_BYTES)
 #define RC_WL_TILES 29                 // column tiles of the merged aggregation linear: 449..464 outputs (benchmark: 416 + 39)
 #define RC_WL_SLD 468                  // floats per staged row of its output
-
-__device__ __forceinline__ float rc_wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
 
 // D[16 x 16*NTILES] = A[16 x K] W^T for this wave's column tiles t = wave + 8 i (i < TW); tiles past NTILES repeat the last
 // valid one (their accumulators are never stored) so that the whole step is one basic block.  An "iteration" is one column
@@ -125,20 +119,12 @@ __device__ __forceinline__ void rc_bias(const float* __restrict__ bias, float (&
   }
 }
 
-// one wave, one row: far3d_layernorm's arithmetic (norm.hip layernorm_kernel<1>, C = 256)
+// one wave, one row of the fp32 row buffer: the LayerNorm row of row_core.hpp with one piece per lane, C = RC_E
 __device__ __forceinline__ float4 rc_layernorm_row(const float* Frow, const float4& g, const float4& bt, float eps, int lane) {
   const float4 v = *reinterpret_cast<const float4*>(Frow + lane * 4);
-  const float s = (v.x + v.y) + (v.z + v.w);
-  const float mean = rc_wave_sum(s) / RC_E;
-  const float a = v.x - mean, b = v.y - mean, d = v.z - mean, e = v.w - mean;
-  const float q = (a * a + b * b) + (d * d + e * e);
-  const float rstd = 1.f / sqrtf(rc_wave_sum(q) / RC_E + eps);
-  float4 o;
-  o.x = (v.x - mean) * rstd * g.x + bt.x;
-  o.y = (v.y - mean) * rstd * g.y + bt.y;
-  o.z = (v.z - mean) * rstd * g.z + bt.z;
-  o.w = (v.w - mean) * rstd * g.w + bt.w;
-  return o;
+  const float mean = ln_mean(ln_lane_sum(v), RC_E);
+  const float rstd = ln_rstd(ln_lane_squares(v, mean), RC_E, eps);
+  return ln_apply(v, mean, rstd, g, bt);
 }
 
 __device__ __forceinline__ uint2 rc_pack4(const float4& v) { return make_uint2(pack_bf16x2(v.x, v.y), pack_bf16x2(v.z, v.w)); }

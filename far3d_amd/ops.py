@@ -1250,30 +1250,39 @@ def layernorm(x, gamma, beta, eps=1e-5, act=None, add=None, out=None, add_dtype=
     return res if len(res) > 1 else y
 
 
+def _norm_operands(who, x, pair, *views):
+    """What the NHWC normalisation wrappers do alike.  x: (N,H,W,C) (pair: a pair-stored bf16 map of 2C stored channels, checked under the
+    wrapper's name `who`).  views: (tensor | None, name) pairs.  Returns N, H, W, the logical C, the storage code and, per view, what
+    the library takes: (pointer, pixel stride, image stride), (None, 0, 0) for an absent one."""
+    N, H, W, C = x.shape
+    if pair:
+        if x.dtype != torch.bfloat16 or C % 64:
+            raise ValueError("%s: pair storage is bf16 with a multiple of 64 stored channels" % who)
+        C //= 2
+    args = tuple((None, 0, 0) if t is None else (_ptr(t),) + _nhwc_view(t, name) for t, name in views)
+    return (N, H, W, C, DT_BF16_PAIR if pair else _dt(x)) + args
+
+
+def _norm_scratch(who, scratch, N, C, device):
+    """The ese_scratch_floats(N, C) f32 workspace of ese_nhwc / groupnorm_nhwc: allocated when None, refused when too small."""
+    if scratch is None:
+        scratch = torch.empty(ese_scratch_floats(N, C), dtype=torch.float32, device=device)
+    if scratch.numel() < ese_scratch_floats(N, C):
+        raise ValueError("%s: scratch needs %d floats" % (who, ese_scratch_floats(N, C)))
+    return scratch
+
+
 def ese_nhwc(x, fcw, fcb, identity=None, out=None, scratch=None, pair=False, sums=None):
     """x * hsigmoid(fc(mean_hw x)) (+ identity) on NHWC views (any channel slice / pixel stride).  scratch: optional
     ese_scratch_floats(N, C) f32 workspace (never needs zeroing; the pooling is deterministic).  pair: x / identity / out are
     pair-stored bf16 maps (2C stored channels).  sums: the int64 channel sums conv2d_nhwc(..., sums=) accumulated while it produced
     x -- the pooling pass is skipped and the sums come back zeroed."""
     lib = _lib.require_device()
-    N, H, W, C = x.shape
-    if pair:
-        if x.dtype != torch.bfloat16 or C % 64:
-            raise ValueError("ese_nhwc: pair storage is bf16 with a multiple of 64 stored channels")
-        C //= 2
-    ldx, xs = _nhwc_view(x, "x")
     if out is None:
         out = torch.empty(tuple(x.shape), dtype=x.dtype, device=x.device)
-    ldy, ys = _nhwc_view(out, "out")
-    ldi, isd, ip = 0, 0, None
-    if identity is not None:
-        ldi, isd = _nhwc_view(identity, "identity")
-        ip = _ptr(identity)
-    if scratch is None:
-        scratch = torch.empty(ese_scratch_floats(N, C), dtype=torch.float32, device=x.device)
-    if scratch.numel() < ese_scratch_floats(N, C):
-        raise ValueError("ese_nhwc: scratch needs %d floats" % ese_scratch_floats(N, C))
-    _lib.check(lib.far3d_ese_nhwc(_ptr(x), DT_BF16_PAIR if pair else _dt(x), _ptr(fcw), _ptr(fcb), ip, _ptr(out), _ptr(scratch), N, H * W, C,
+    N, H, W, C, dt, (xp, ldx, xs), (yp, ldy, ys), (ip, ldi, isd) = _norm_operands("ese_nhwc", x, pair, (x, "x"), (out, "out"), (identity, "identity"))
+    scratch = _norm_scratch("ese_nhwc", scratch, N, C, x.device)
+    _lib.check(lib.far3d_ese_nhwc(xp, dt, _ptr(fcw), _ptr(fcb), ip, yp, _ptr(scratch), N, H * W, C,
                                   ldx, xs, ldi, isd, ldy, ys, _sums_ptr(sums, N, C), _stream(x)), "far3d_ese_nhwc")
     return out
 
@@ -1299,29 +1308,14 @@ def ese_fused_nhwc(x, fcw, fcb, sums, gate, identity=None, out=None, pooled=None
     the concat convolution, y = x * gate (+ identity) into `out` (None: not written) and, optionally, MaxPool2d(3, 2, ceil_mode=True)(y) into
     `pooled` (an NHWC view, e.g. the input slice of the next stage's concat buffer).  gate: >= N*C floats of workspace."""
     lib = _lib.require_device()
-    N, H, W, C = x.shape
-    if pair:
-        C //= 2
     if out is None and pooled is None:
         raise ValueError("ese_fused_nhwc: nothing to write (out and pooled are both None)")
-    ldx, xs = _nhwc_view(x, "x")
-    ldy, ys, yp = 0, 0, None
-    if out is not None:
-        ldy, ys = _nhwc_view(out, "out")
-        yp = _ptr(out)
-    ldi, isd, ip = 0, 0, None
-    if identity is not None:
-        ldi, isd = _nhwc_view(identity, "identity")
-        ip = _ptr(identity)
-    Hp = Wp = ldp = ps = 0
-    pp = None
-    if pooled is not None:
-        Hp, Wp = pooled.shape[1], pooled.shape[2]
-        ldp, ps = _nhwc_view(pooled, "pooled")
-        pp = _ptr(pooled)
+    N, H, W, C, dt, (xp, ldx, xs), (yp, ldy, ys), (ip, ldi, isd), (pp, ldp, ps) = _norm_operands(
+        "ese_fused_nhwc", x, pair, (x, "x"), (out, "out"), (identity, "identity"), (pooled, "pooled"))
+    Hp, Wp = (pooled.shape[1], pooled.shape[2]) if pooled is not None else (0, 0)
     if gate.numel() < N * C or gate.dtype != torch.float32:
         raise ValueError("ese_fused_nhwc: gate needs N*C floats")
-    _lib.check(lib.far3d_ese_fused_nhwc(_ptr(x), DT_BF16_PAIR if pair else _dt(x), _ptr(fcw), _ptr(fcb), ip, yp, pp, _ptr(gate), N, H, W, C,
+    _lib.check(lib.far3d_ese_fused_nhwc(xp, dt, _ptr(fcw), _ptr(fcb), ip, yp, pp, _ptr(gate), N, H, W, C,
                                         ldx, xs, ldi, isd, ldy, ys, Hp, Wp, ldp, ps, _sums_ptr(sums, N, C), _stream(x)), "far3d_ese_fused_nhwc")
     return out if out is not None else pooled
 
@@ -1329,16 +1323,11 @@ def ese_fused_nhwc(x, fcw, fcb, sums, gate, identity=None, out=None, pooled=None
 def groupnorm_nhwc(x, gamma, beta, groups=32, eps=1e-5, relu=True, out=None, scratch=None, pair=False):
     lib = _lib.require_device()
     _chk(x, "x", ndim=4)
-    N, H, W, C = x.shape
-    if pair:
-        if x.dtype != torch.bfloat16 or C % 64:
-            raise ValueError("groupnorm_nhwc: pair storage is bf16 with a multiple of 64 stored channels")
-        C //= 2
+    N, H, W, C, dt = _norm_operands("groupnorm_nhwc", x, pair)
     if out is None:
         out = torch.empty_like(x)
-    if scratch is None:
-        scratch = torch.empty(ese_scratch_floats(N, C), dtype=torch.float32, device=x.device)
-    _lib.check(lib.far3d_groupnorm_nhwc(_ptr(x), DT_BF16_PAIR if pair else _dt(x), _ptr(gamma), _ptr(beta), _ptr(out), _ptr(scratch), N, H * W, C,
+    scratch = _norm_scratch("groupnorm_nhwc", scratch, N, C, x.device)
+    _lib.check(lib.far3d_groupnorm_nhwc(_ptr(x), dt, _ptr(gamma), _ptr(beta), _ptr(out), _ptr(scratch), N, H * W, C,
                                         groups, float(eps), 1 if relu else 0, _stream(x)), "far3d_groupnorm_nhwc")
     return out
 
@@ -1346,22 +1335,11 @@ def groupnorm_nhwc(x, gamma, beta, groups=32, eps=1e-5, relu=True, out=None, scr
 def maxpool3x3s2_nhwc(x, out=None, pair=False):
     lib = _lib.require_device()
     _chk(x, "x", ndim=4)
-    N, H, W, C = x.shape
-    Cs = C
-    if pair:
-        if x.dtype != torch.bfloat16 or C % 64:
-            raise ValueError("maxpool3x3s2_nhwc: pair storage is bf16 with a multiple of 64 stored channels")
-        C //= 2
-    Ho, Wo = -(-(H - 3) // 2) + 1, -(-(W - 3) // 2) + 1
-    if (Ho - 1) * 2 >= H:
-        Ho -= 1
-    if (Wo - 1) * 2 >= W:
-        Wo -= 1
+    Ho, Wo = maxpool_out_hw(x.shape[1], x.shape[2])
     if out is None:
-        out = torch.empty((N, Ho, Wo, Cs), dtype=x.dtype, device=x.device)
-    ldy, ys = _nhwc_view(out, "out")
-    _lib.check(lib.far3d_maxpool3x3s2_nhwc(_ptr(x), DT_BF16_PAIR if pair else _dt(x), _ptr(out), N, H, W, C, Ho, Wo, ldy, ys, _stream(x)),
-               "far3d_maxpool3x3s2_nhwc")
+        out = torch.empty((x.shape[0], Ho, Wo, x.shape[3]), dtype=x.dtype, device=x.device)
+    N, H, W, C, dt, (yp, ldy, ys) = _norm_operands("maxpool3x3s2_nhwc", x, pair, (out, "out"))
+    _lib.check(lib.far3d_maxpool3x3s2_nhwc(_ptr(x), dt, yp, N, H, W, C, Ho, Wo, ldy, ys, _stream(x)), "far3d_maxpool3x3s2_nhwc")
     return out
 
 
