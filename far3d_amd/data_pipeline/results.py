@@ -44,15 +44,22 @@ def box_to_av2(boxes_3d):
     return torch.cat([centre, t[:, [3, 4, 5]], yaw_to_quat(t[:, 6])], dim=1)
 
 
-def format_results(outputs, data_infos, classes=AV2_CLASSES, feather_path=None, track_ids=None):
+def format_results(outputs, data_infos, classes=AV2_CLASSES, feather_path=None, track_ids=None, track_records=None,
+                   primary_only=False):
     """ref argoverse2_dataset.py:267-331.  outputs: one dict per sample with boxes_3d / scores_3d / labels_3d (optionally under
     'pts_bbox'); data_infos: per sample `scene_id` and `lidar_timestamp_ns`.  Returns the detections frame indexed by
     (log_id, timestamp_ns), sorted like the reference; feather_path additionally writes the score-sorted submission file.
     track_ids: optional, one sequence of ints per sample (a sample's `track_ids_3d`, aligned with its boxes): the frame gets a
-    `track_id` column.  Not given: no such column."""
+    `track_id` column.  Not given: no such column.
+    track_records: optional, one dict(age=, primary=, velocity=) per sample (its `track_age_3d`, `track_primary_3d`, `track_velocity_3d`
+    (n, 3), aligned with its boxes): the frame gets `track_age`, `track_primary`, `vx_m`, `vy_m`, `vz_m` columns.  primary_only (needs
+    track_records) keeps the primary rows only: at most one row per (log_id, timestamp_ns, track_id), none without an identity."""
     import pandas as pd
     assert len(data_infos) == len(outputs)
     assert track_ids is None or len(track_ids) == len(outputs)
+    assert track_records is None or len(track_records) == len(outputs)
+    if primary_only and track_records is None:
+        raise ValueError("format_results: primary_only needs track_records (the primary flags)")
     frames = []
     for i, (out_i, info) in enumerate(zip(outputs, data_infos)):
         if "pts_bbox" in out_i:
@@ -67,6 +74,17 @@ def format_results(outputs, data_infos, classes=AV2_CLASSES, feather_path=None, 
             ids = torch.as_tensor(track_ids[i]).cpu().numpy().astype("int64")
             assert len(ids) == len(df), "track_ids[%d] holds %d ids for %d boxes" % (i, len(ids), len(df))
             df["track_id"] = ids
+        if track_records is not None:
+            rec = track_records[i]
+            age = torch.as_tensor(rec["age"]).cpu().numpy().astype("int32")
+            prim = torch.as_tensor(rec["primary"]).cpu().numpy().astype(bool)
+            vel = torch.as_tensor(rec["velocity"]).cpu().numpy().astype("float32").reshape(-1, 3)
+            for name, v in (("age", age), ("primary", prim), ("velocity", vel)):
+                assert len(v) == len(df), "track_records[%d]['%s'] holds %d entries for %d boxes" % (i, name, len(v), len(df))
+            df["track_age"], df["track_primary"] = age, prim
+            df["vx_m"], df["vy_m"], df["vz_m"] = vel[:, 0], vel[:, 1], vel[:, 2]
+            if primary_only:
+                df = df[df["track_primary"]]
         frames.append(df)
     dts = pd.concat(frames).set_index(["log_id", "timestamp_ns"]).sort_index()
     dts = dts.sort_values("score", ascending=False).reset_index()

@@ -80,7 +80,8 @@ def default_cfg(**over):
         roi_depthwise=False, depth_level=0,
         # track ids (INTEGRATION.md "Track ids"): None = off; dict(birth_thr=p) adds `query_idx` / `track_ids` to the result -- the identity
         # of a detection across the frames of its scene, carried through the streaming memory (far3d_track_update).  birth_thr: the
-        # max-class probability from which a ranked query without an identity is given a new one (0.0: every ranked query)
+        # max-class probability from which a ranked query without an identity is given a new one (0.0: every ranked query).
+        # records=True (INTEGRATION.md "Track records") adds `track_age` / `track_primary` / `track_velocity` (far3d_track_records)
         track=None,
     )
     cfg.update(over)
@@ -98,16 +99,19 @@ def multi_depth_topk(cfg):
 
 
 def track_options(cfg):
-    """cfg['track'] checked: None (tracking off) or dict(birth_thr=<probability>).  Tracking needs num_propagated <= topk_proposals: a memory
+    """cfg['track'] checked: None (tracking off) or dict(birth_thr=<probability>[, records=<bool>]: `records` is in the result only where
+    the caller gave it).  Tracking needs num_propagated <= topk_proposals: a memory
     slot beyond the frame's top-k is one that was carried over, and propagating it again would put its id on two queries.  A pure
     function of cfg: no device, no library."""
     tr = cfg.get("track")
     if tr is None or tr is False:
         return None
     tr = {} if tr is True else dict(tr)
-    unknown = sorted(set(tr) - {"birth_thr"})
+    unknown = sorted(set(tr) - {"birth_thr", "records"})
     if unknown:
-        raise ValueError("track: unknown option(s) %s (known: birth_thr)" % ", ".join(unknown))
+        raise ValueError("track: unknown option(s) %s (known: birth_thr, records)" % ", ".join(unknown))
+    if "records" in tr and not isinstance(tr["records"], bool):
+        raise ValueError("track records=%r: a bool" % (tr["records"],))
     thr = float(tr.get("birth_thr", 0.0))
     if not 0.0 <= thr <= 1.0:
         raise ValueError("track birth_thr=%r: a probability in [0, 1]" % (tr.get("birth_thr"),))
@@ -117,7 +121,7 @@ def track_options(cfg):
     if cfg["topk_proposals"] > ops.TRACK_MAX_K or cfg["memory_len"] > ops.TRACK_MAX_L or cfg["max_num"] > ops.TRACK_MAX_DEC:
         raise ValueError("track: topk_proposals=%d / memory_len=%d / max_num=%d beyond far3d_track_update's %d / %d / %d" %
                          (cfg["topk_proposals"], cfg["memory_len"], cfg["max_num"], ops.TRACK_MAX_K, ops.TRACK_MAX_L, ops.TRACK_MAX_DEC))
-    return dict(birth_thr=thr)
+    return dict(birth_thr=thr, **({"records": tr["records"]} if "records" in tr else {}))
 
 
 def dwsep_layers(cfg, precision):
@@ -841,6 +845,9 @@ class Far3DEngine:
             # does not reset it, so an id is never used twice (reset_tracks)
             self.mem["track"] = torch.zeros(1, Lm, dtype=torch.int64, device=dev)
             self._track_next = torch.ones(1, 1, dtype=torch.int64, device=dev)
+            if self.track.get("records"):
+                # frames the id of each slot has been ranked (> 0 exactly where track != 0): shifted and zeroed with the ids
+                self.mem["track_hits"] = torch.zeros(1, Lm, dtype=torch.int32, device=dev)
         self._mem_valid = False
 
     def reset_memory(self):
@@ -1376,17 +1383,30 @@ class Far3DEngine:
             result, idx = self.decode(all_cls, all_box, mem_scores=sc, mem_K=cfg["topk_proposals"])
         else:           # the same decode + the boxes' query rows, then the ids: the one-stream case of the streams path
             results, idx = self.decode_streams(all_cls[-1], all_box[-1], sc[None], cfg["topk_proposals"], tracked=True)
-            self._track_update(results, idx, sc[None], hs, self.mem["track"], self._track_next)
+            self._track_update(results, idx, sc[None], [hs], self.mem["track"], self._track_next, self.mem.get("track_hits"))
             result, idx = {k: v[0] for k, v in results.items()}, idx[0]
         ops.memory_post_update(hs.m, idx, outs_dec[-1], all_box[-1][0], hs.dd["ego_pose"], hs.dd["timestamp"], self.mem)
         return self._head_result(hs, all_cls, all_box, outs_dec, idx, result, sc if self.track is not None else None)
 
-    def _track_update(self, results, idx, scores, hs, mem_track, next_id):
-        """One far3d_track_update launch for the B streams of results / idx / scores (leading B): the streams' mem_track (B, L) and
-        next_id (B, 1) are updated in place, results gains track_ids (B, Kdec).  The propagated rows are the last num_propagated of the A."""
-        P = self.cfg["num_propagated"]
-        results["track_ids"] = ops.track_update(idx, scores, mem_track, next_id, hs.A - P, P, self.track["birth_thr"],
+    def _track_update(self, results, idx, scores, hss, mem_track, next_id, mem_hits=None):
+        """One far3d_track_update launch for the B streams of results / idx / scores (leading B; hss: their _head_prepare results): the
+        streams' mem_track (B, L) and next_id (B, 1) are updated in place, results gains track_ids (B, Kdec).  The propagated rows are
+        the last num_propagated of the A.  mem_hits (track records=True): the streams' (B, L) counter plane, updated in place by ONE
+        far3d_track_records launch behind the ids; results gains track_age, track_primary (B, Kdec) and track_velocity (B, Kdec, 3).
+        It reads the pre-updated memory hs.m, so it runs before memory_post_update -- which writes the state, never hs.m."""
+        P, A = self.cfg["num_propagated"], hss[0].A
+        results["track_ids"] = ops.track_update(idx, scores, mem_track, next_id, A - P, P, self.track["birth_thr"],
                                                 query_idx=results["query_idx"])
+        if mem_hits is not None:
+            B, L = mem_hits.shape
+            if B == 1:
+                m_ref, m_ts = hss[0].m["ref"], hss[0].m["ts"].view(1, L)
+            else:       # every stream's memory_prepare wrote buffers of its own: one gathering copy each
+                m_ref = torch.cat([hs.m["ref"] for hs in hss], out=self._buf(("trk_ref", B), (B, L, 3), torch.float32))
+                m_ts = torch.cat([hs.m["ts"] for hs in hss], out=self._buf(("trk_ts", B), (B, L, 1), torch.float64)).view(B, L)
+            results["track_age"], results["track_primary"], results["track_velocity"] = ops.track_records(
+                idx, mem_track, mem_hits, results["query_idx"], results["track_ids"], results["keep"], results["boxes_3d"], m_ref, m_ts,
+                A, A - P, P)
 
     def _head_finish_streams(self, hss, outs_dec, enter, track=None):
         """_head_finish for B scene streams (streams.StreamBatch): hss the B _head_prepare results, outs_dec decoder_streams' result
@@ -1395,8 +1415,8 @@ class Far3DEngine:
         buffers: ONE gathering copy of the decoder's (layers, B, A, E) rows into stream-major order, nan_to_num, _head_finish's own
         unfused cls / reg branches (_head_branches; StreamBatch refuses fused_rows) through ops.linear_streams (the tile of ONE stream's
         layers * A rows); the decode and the memory update's top-k of all streams are ONE far3d_decode_topk_mem_streams launch.  Per
-        stream stay head_finalize and memory_post_update.  track (tracking on): the streams' (mem_track (B, L), next_id (B, 1)), updated by
-        ONE far3d_track_update launch."""
+        stream stay head_finalize and memory_post_update.  track (tracking on): the streams' (mem_track (B, L), next_id (B, 1)[,
+        mem_hits (B, L)]), updated by ONE far3d_track_update launch [and ONE far3d_track_records launch]."""
         cfg = self.cfg
         E, nl, ncls, code = cfg["embed_dims"], cfg["num_layers"], cfg["num_classes"], cfg["code_size"]
         B, A = len(hss), hss[0].A
@@ -1409,7 +1429,7 @@ class Far3DEngine:
         results, idx = self.decode_streams(CLS.view(B, nl, A, ncls)[:, -1], BOX.view(B, nl, A, code)[:, -1], SC, cfg["topk_proposals"],
                                            tracked=self.track is not None)
         if self.track is not None:
-            self._track_update(results, idx, SC, hss[0], *track)
+            self._track_update(results, idx, SC, hss, *track)
         res = []
         for b, hs in enumerate(hss):
             all_cls, all_box = CLS[b].view(nl, 1, A, ncls), BOX[b].view(nl, 1, A, code)

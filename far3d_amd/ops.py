@@ -2283,6 +2283,52 @@ def track_update(topk_idx, score, mem_track, next_id, row_start, num_propagated,
     return ids
 
 
+def track_records(topk_idx, mem_track, mem_hits, query_idx, track_ids, keep, boxes, m_ref, m_ts, num_rows, row_start, num_propagated):
+    """Track records of one frame for B scene streams in ONE launch behind track_update (far3d_track_records; the contract is in
+    include/far3d_hip.h and, executable, in tests/track_record_refs.py).  topk_idx (B, K) int64 and mem_track (B, L) int64 as
+    track_update took / left them, mem_hits (B, L) int32 the streams' counter plane, UPDATED IN PLACE; query_idx (B, Kdec) int32,
+    track_ids (B, Kdec) int64, keep (B, Kdec) bool or uint8 and boxes (B, Kdec, >= 3) f32 of the decode; m_ref (B, L, 3) f32 and
+    m_ts (B, L) f64 of this frame's memory_prepare; num_rows: the A query rows, row_start: the first propagated one.  Each stream's
+    block contiguous, any stride between the blocks.  Returns (track_age (B, Kdec) int32, track_primary (B, Kdec) bool,
+    track_velocity (B, Kdec, 3) f32)."""
+    lib = _lib.require_device()
+    for t, name, dts in ((topk_idx, "topk_idx", (torch.int64,)), (mem_track, "mem_track", (torch.int64,)), (mem_hits, "mem_hits", (torch.int32,)),
+                         (query_idx, "query_idx", (torch.int32,)), (track_ids, "track_ids", (torch.int64,)),
+                         (keep, "keep", (torch.bool, torch.uint8)), (m_ts, "m_ts", (torch.float64,))):
+        if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.dtype not in dts or not t.is_cuda or (t.shape[1] > 1 and t.stride(1) != 1):
+            raise ValueError("track_records: %s must be a (B, n) %s device tensor with unit inner stride" % (name, " or ".join(map(str, dts))))
+    for t, name in ((boxes, "boxes"), (m_ref, "m_ref")):
+        if not isinstance(t, torch.Tensor) or t.dim() != 3 or t.dtype != torch.float32 or not t.is_cuda or (t.numel() > 0 and t.stride(2) != 1):
+            raise ValueError("track_records: %s must be a (B, n, c) torch.float32 device tensor with unit inner stride" % name)
+    B, K = topk_idx.shape
+    L, Kdec = mem_track.shape[1], query_idx.shape[1]
+    if any(t.shape[0] != B for t in (mem_track, mem_hits, query_idx, track_ids, keep, boxes, m_ref, m_ts)):
+        raise ValueError("track_records: the operands disagree on B=%d (the leading dimension of topk_idx)" % B)
+    if tuple(mem_hits.shape) != (B, L) or tuple(m_ts.shape) != (B, L) or tuple(m_ref.shape) != (B, L, 3) or m_ref.stride(1) != 3:
+        raise ValueError("track_records: mem_hits %s and m_ts %s must be (B, L=%d) like mem_track, m_ref %s (B, L, 3) with contiguous streams" %
+                         (tuple(mem_hits.shape), tuple(m_ts.shape), L, tuple(m_ref.shape)))
+    if tuple(track_ids.shape) != (B, Kdec) or tuple(keep.shape) != (B, Kdec) or boxes.shape[1] != Kdec or boxes.shape[2] < 3:
+        raise ValueError("track_records: track_ids %s and keep %s must be (B, Kdec=%d) like query_idx, boxes %s (B, Kdec, >= 3)" %
+                         (tuple(track_ids.shape), tuple(keep.shape), Kdec, tuple(boxes.shape)))
+    P = int(num_propagated)
+    if P > K:
+        raise ValueError("track_records: num_propagated=%d > the %d ranked rows (topk_proposals): a memory slot that was carried over would "
+                         "be propagated a second time with the same id" % (P, K))
+    dev = mem_hits.device
+    age = torch.empty((B, Kdec), dtype=torch.int32, device=dev)
+    primary = torch.empty((B, Kdec), dtype=torch.bool, device=dev)
+    velocity = torch.empty((B, Kdec, 3), dtype=torch.float32, device=dev)
+    ptr = lambda t: _ptr(t) if Kdec else None
+    strides = (ctypes.c_long * 12)(topk_idx.stride(0), mem_track.stride(0), query_idx.stride(0), track_ids.stride(0), keep.stride(0),
+                                   boxes.stride(0), m_ref.stride(0), m_ts.stride(0), mem_hits.stride(0), age.stride(0), primary.stride(0),
+                                   velocity.stride(0))
+    _lib.check(lib.far3d_track_records(_ptr(topk_idx), _ptr(mem_track), ptr(query_idx), ptr(track_ids), ptr(keep), ptr(boxes), _ptr(m_ref),
+                                       _ptr(m_ts), _ptr(mem_hits), ptr(age), ptr(primary), ptr(velocity), B, int(num_rows), K, L, Kdec,
+                                       int(row_start), P, boxes.stride(1) if Kdec else boxes.shape[2], ctypes.cast(strides, ctypes.c_void_p), _stream(mem_hits)),
+               "far3d_track_records")
+    return age, primary, velocity
+
+
 def camera_prep(lidar2img, intrinsics=None, extrinsics=None):
     """lidar2img / intrinsics / extrinsics (N,4,4) f32 -> (img2lidar (N,4,4) = inverse(lidar2img), c14 (N,14) | None)."""
     lib = _lib.require_device()

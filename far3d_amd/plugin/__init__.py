@@ -843,7 +843,8 @@ class FarHead(_SchemaModule):
     @torch.no_grad()
     def get_bboxes(self, preds_dicts, img_metas, rescale=False):
         """ref farhead.py:1224-1245 -> [[boxes, scores, labels]] (boxes wrapped in img_metas[0]['box_type_3d'] when given).  With
-        tracking on (the engine's cfg track) the list has a fourth entry, the kept boxes' track ids (int64; 0 = none)."""
+        tracking on (the engine's cfg track) the list has a fourth entry, the kept boxes' track ids (int64; 0 = none); with track
+        records=True three more behind it: their ages (int32), primary flags (bool) and velocities ((n, 3) f32)."""
         r = preds_dicts.get("_far3d_result")
         if r is None:
             r = self._eng.decode(preds_dicts["all_cls_scores"], preds_dicts["all_bbox_preds"])
@@ -852,7 +853,10 @@ class FarHead(_SchemaModule):
         box_type = img_metas[0].get("box_type_3d")
         if box_type is not None:
             boxes = box_type(boxes, boxes.size(-1))
-        return [[boxes, scores, labels] + ([r["track_ids"][keep]] if "track_ids" in r else [])]
+        return [[boxes, scores, labels] + [r[k][keep] for k in ("track_ids",) + _TRACK_RECORDS if k in r]]
+
+
+_TRACK_RECORDS = ("track_age", "track_primary", "track_velocity")      # the result keys of track records=True, in output order
 
 
 # ------------------------------------------------------------------------------------------------ detector
@@ -874,7 +878,7 @@ class Far3D(nn.Module):
         # build-side extension: the reference's threshold rule with static shapes -- rows reserved for the adaptive queries, count on
         # the device (None = the legacy form with a host sync on M); see INTEGRATION.md "Proposal modes"
         self.proposal_capacity = proposal_capacity
-        self.track = track                     # build-side extension: track ids (None = off; True or dict(birth_thr=p)); prepare(track=) too
+        self.track = track                     # build-side extension: track ids (None = off; True or dict(birth_thr=p, records=bool)); prepare(track=) too
         self.engine = None
         self.eval()
 
@@ -913,7 +917,8 @@ class Far3D(nn.Module):
         fused_dwsep: the engine's opt-in of the same name -- the depthwise-separable layers of a light model (depthwise backbone specs,
         use_depthwise towers) as one launch each where the fused kernel takes them (engine.dwsep_layers).
         track: True or dict(birth_thr=p) switches the track ids on (None keeps the constructor's `track`): simple_test then adds
-        `track_ids_3d` to pts_bbox, FarHead.get_bboxes a fourth list entry (INTEGRATION.md "Track ids")."""
+        `track_ids_3d` to pts_bbox, FarHead.get_bboxes a fourth list entry (INTEGRATION.md "Track ids").  dict(records=True) also adds
+        `track_age_3d`, `track_primary_3d`, `track_velocity_3d` and three more list entries (INTEGRATION.md "Track records")."""
         if track is not None:
             self.track = track
         self.engine = _engine.Far3DEngine(self.state_dict(), self.engine_cfg(), device=device, precision=precision)
@@ -948,6 +953,9 @@ class Far3D(nn.Module):
         res = dict(boxes_3d=r["boxes_3d"][keep], scores_3d=r["scores_3d"][keep], labels_3d=r["labels_3d"][keep])
         if "track_ids" in r:
             res["track_ids_3d"] = r["track_ids"][keep]      # kept rows only, like the boxes (0 = no identity)
+        for k in _TRACK_RECORDS:
+            if k in r:
+                res[k + "_3d"] = r[k][keep]
         box_type = img_metas[0].get("box_type_3d")
         if box_type is not None:
             res["boxes_3d"] = box_type(res["boxes_3d"], res["boxes_3d"].size(-1))

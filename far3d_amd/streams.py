@@ -20,7 +20,8 @@ There every stream carries its own count of rows that hold a query, on the devic
 backbone / FPN / 2D-head pass, the decoder pass hands the B counts to far3d_attention_streams and far3d_aggregate_batched_holes, and
 head_finalize masks each stream's hole.  No host sync in any mode; check_proposal_overflow() is the one that reads the flags.
 Track ids (engine cfg track): the streams' id queues and counters are rows of one tensor each, so head_batch updates all of them in ONE
-far3d_track_update launch; every stream's ids are those of a plain engine fed its frames.
+far3d_track_update launch; every stream's ids are those of a plain engine fed its frames.  Track records (track records=True): the
+streams' hit counters are the rows of a third tensor, updated by ONE far3d_track_records launch behind the ids.
 Everything else is refused with a ValueError that names the option."""
 import contextlib
 import functools
@@ -111,8 +112,12 @@ class StreamBatch:
         if engine.track is not None:
             self._track = (torch.zeros((self.streams, engine.cfg["memory_len"]), dtype=torch.int64, device=engine.dev),
                            torch.ones((self.streams, 1), dtype=torch.int64, device=engine.dev))
+            if "track_hits" in engine.mem:      # track records: one more plane beside the ids, a row per stream
+                self._track += (torch.zeros((self.streams, engine.cfg["memory_len"]), dtype=torch.int32, device=engine.dev),)
             for b, st in enumerate(self._state):
                 st["mem"]["track"] = self._track[0][b:b + 1]
+                if len(self._track) > 2:
+                    st["mem"]["track_hits"] = self._track[2][b:b + 1]
         self._tokens = None         # (B, N, S, 256): stream b's camera stage writes slice b, the decoder pass reads all of it
         self._images = None         # (B * N, 3, H, W): stream b stages its images in rows [b * N, (b + 1) * N) (camera_batch)
         for b in range(self.streams):

@@ -798,6 +798,32 @@ int far3d_track_update(const int64_t* topk_idx, const float* score, const int32_
                        int64_t* track_ids, int B, int A, int K, int L, int Kdec, int row_start, int P, double birth_thr,
                        const long* batch_strides, void* stream);
 
+/* Track records: what a tracker output needs beside the ids -- an age per id, ONE primary box per id and frame, a velocity -- from
+ * state the streaming memory already carries plus one counter plane.  Launched behind far3d_track_update on the same stream, one
+ * launch for B >= 1 streams (one workgroup each), no host read.  State per stream, updated IN PLACE: mem_hits (L) int32, the number
+ * of frames the id in that slot of mem_track has been ranked (> 0 exactly where mem_track != 0; zeroed wherever mem_track is).
+ * Inputs per stream: topk_idx (K) int64 and mem_track (L) int64 AS far3d_track_update LEFT IT (its first K entries are the ranked
+ * rows' ids); query_idx (Kdec) int32, track_ids (Kdec) int64, keep (Kdec) bytes and boxes (Kdec rows of box_stride >= 3 floats, the
+ * centre in metres first) of the decode; m_ref (L,3) f32 and m_ts (L) f64 of this frame's far3d_memory_prepare: a slot's previous
+ * centre warped into the current lidar frame, and the seconds since it was written.  With rank t < K, row r = topk_idx[t]:
+ *  1. rank t inherited its id iff row_start <= r < row_start + P and mem_hits[r - row_start] > 0 before this call;
+ *  2. hits of rank t: the old mem_hits[r - row_start] + 1 if inherited, else 1 if mem_track[t] != 0 (a birth), else 0;
+ *     mem_hits = cat(hits of ranks [0, K), old mem_hits)[:L], every old slot read before any is written;
+ *  3. track_age[j] (Kdec) int32 = hits of the rank whose row is query_idx[j], minus 1 (0: born this frame); -1 where track_ids[j]
+ *     is 0 or no rank has that row (rows outside [0, A) match none, as in far3d_track_update step 4);
+ *  4. track_primary[j] (Kdec) bytes = 1 iff track_ids[j] != 0, keep[j] != 0 and no j' < j has the same id with keep set: in the
+ *     decode's descending score order the best kept box of its id, so a frame never has two primaries of one id;
+ *  5. track_velocity[j] (Kdec,3) f32 = (boxes[j][0:3] - m_ref[s]) / (float)m_ts[s] for a box whose rank inherited its id, with
+ *     s = query_idx[j] - row_start and m_ts[s] finite and > 0: fp32, one subtraction and one division per component; metres per
+ *     second in the current lidar frame, ego motion removed.  Every other box gets +0.0.
+ * Sizes as far3d_track_update: K <= 1024, K <= L <= 4096, Kdec <= 1024, P <= K <= A.  batch_strides: 12 longs on the HOST,
+ * elements between stream b and b + 1 of topk_idx, mem_track, query_idx, track_ids, keep, boxes, m_ref, m_ts, mem_hits, track_age,
+ * track_primary, track_velocity (for B > 1 none below one stream's extent). */
+int far3d_track_records(const int64_t* topk_idx, const int64_t* mem_track, const int32_t* query_idx, const int64_t* track_ids,
+                        const unsigned char* keep, const float* boxes, const float* m_ref, const double* m_ts, int32_t* mem_hits,
+                        int32_t* track_age, unsigned char* track_primary, float* track_velocity, int B, int A, int K, int L, int Kdec,
+                        int row_start, int P, int box_stride, const long* batch_strides, void* stream);
+
 /* Per-frame camera calibration in one launch: img2lidar (N,4,4) = inverse(lidar2img) (ref models/dense_heads/farhead.py:798;
  * Gauss-Jordan with partial pivoting in f64) and c14 (N,14) = [fx/1e3, fy/1e3, extrinsics[:3,:4]] (ref farhead.py:553-556).
  * Either output may be NULL. */
