@@ -83,6 +83,10 @@ def default_cfg(**over):
         # max-class probability from which a ranked query without an identity is given a new one (0.0: every ranked query).
         # records=True (INTEGRATION.md "Track records") adds `track_age` / `track_primary` / `track_velocity` (far3d_track_records)
         track=None,
+        # duplicate suppression (INTEGRATION.md "Duplicate suppression"): None = off; dict(mode="iou_bev" | "centre", thr, class_aware,
+        # score_thr) adds `dup_keep` / `dup_of` to the result -- a greedy pass over the decoded boxes' rotated BEV footprints
+        # (far3d_box_dedup); with track records=True `track_primary` is then the first SURVIVING box of its id
+        dedup=None,
     )
     cfg.update(over)
     return cfg
@@ -122,6 +126,40 @@ def track_options(cfg):
         raise ValueError("track: topk_proposals=%d / memory_len=%d / max_num=%d beyond far3d_track_update's %d / %d / %d" %
                          (cfg["topk_proposals"], cfg["memory_len"], cfg["max_num"], ops.TRACK_MAX_K, ops.TRACK_MAX_L, ops.TRACK_MAX_DEC))
     return dict(birth_thr=thr, **({"records": tr["records"]} if "records" in tr else {}))
+
+
+DEDUP_DEFAULTS = dict(mode="iou_bev", thr=0.5, class_aware=True, score_thr=0.0)
+
+
+def dedup_options(cfg):
+    """cfg['dedup'] checked: None (duplicate suppression off) or the dict(mode, thr, class_aware, score_thr) of ops.box_dedup with the
+    defaults filled in (True: all defaults).  mode 'iou_bev': thr an IoU in [0, 1); mode 'centre': thr a distance in metres, finite and
+    > 0.  A pure function of cfg: no device, no library."""
+    dd = cfg.get("dedup")
+    if dd is None or dd is False:
+        return None
+    dd = {} if dd is True else dict(dd)
+    unknown = sorted(set(dd) - set(DEDUP_DEFAULTS))
+    if unknown:
+        raise ValueError("dedup: unknown option(s) %s (known: %s)" % (", ".join(unknown), ", ".join(DEDUP_DEFAULTS)))
+    dd = dict(DEDUP_DEFAULTS, **dd)
+    if dd["mode"] not in ops.DEDUP_MODES:
+        raise ValueError("dedup mode=%r: one of %s" % (dd["mode"], ", ".join(ops.DEDUP_MODES)))
+    for k in ("thr", "score_thr"):
+        if isinstance(dd[k], bool) or not isinstance(dd[k], (int, float)):
+            raise ValueError("dedup %s=%r: a number" % (k, dd[k]))
+        dd[k] = float(dd[k])
+    if dd["mode"] == "iou_bev" and not 0.0 <= dd["thr"] < 1.0:
+        raise ValueError("dedup thr=%r: an IoU in [0, 1) (mode iou_bev)" % (dd["thr"],))
+    if dd["mode"] == "centre" and not 0.0 < dd["thr"] < float("inf"):
+        raise ValueError("dedup thr=%r: a finite distance > 0 in metres (mode centre)" % (dd["thr"],))
+    if not isinstance(dd["class_aware"], bool):
+        raise ValueError("dedup class_aware=%r: a bool" % (dd["class_aware"],))
+    if not 0.0 <= dd["score_thr"] <= 1.0:
+        raise ValueError("dedup score_thr=%r: a probability in [0, 1]" % (dd["score_thr"],))
+    if cfg["max_num"] > ops.DEDUP_MAX_DEC:
+        raise ValueError("dedup: max_num=%d decoded boxes beyond far3d_box_dedup's %d" % (cfg["max_num"], ops.DEDUP_MAX_DEC))
+    return dd
 
 
 def dwsep_layers(cfg, precision):
@@ -275,6 +313,7 @@ class Far3DEngine:
         self.prev_scene = None
         self.md_k = multi_depth_topk(self.cfg)
         self.track = track_options(self.cfg)      # None, or dict(birth_thr): mem["track"] / _track_next exist, the result carries track ids
+        self.dedup = dedup_options(self.cfg)      # None, or ops.box_dedup's options: the result carries dup_keep / dup_of
         self.roi_dw = bool(self.cfg.get("roi_depthwise", False))
         self.depth_level = int(self.cfg.get("depth_level", 0) or 0)
         if not 0 <= self.depth_level < len(self.cfg["strides"]):
@@ -1381,12 +1420,23 @@ class Far3DEngine:
         # (the top-k rides in the decode's launch as a second workgroup: far3d_decode_topk_mem -- both rank the last layer's outputs)
         if self.track is None:
             result, idx = self.decode(all_cls, all_box, mem_scores=sc, mem_K=cfg["topk_proposals"])
+            if self.dedup is not None:
+                result = dict(result)
+                self._box_dedup(result, lambda v: v[None], lambda v: v[0])
         else:           # the same decode + the boxes' query rows, then the ids: the one-stream case of the streams path
             results, idx = self.decode_streams(all_cls[-1], all_box[-1], sc[None], cfg["topk_proposals"], tracked=True)
+            self._box_dedup(results)
             self._track_update(results, idx, sc[None], [hs], self.mem["track"], self._track_next, self.mem.get("track_hits"))
             result, idx = {k: v[0] for k, v in results.items()}, idx[0]
         ops.memory_post_update(hs.m, idx, outs_dec[-1], all_box[-1][0], hs.dd["ego_pose"], hs.dd["timestamp"], self.mem)
         return self._head_result(hs, all_cls, all_box, outs_dec, idx, result, sc if self.track is not None else None)
+
+    def _box_dedup(self, results, to_streams=lambda v: v, from_streams=lambda v: v):
+        """Duplicate suppression on (cfg dedup): ONE far3d_box_dedup launch behind the decode for the B streams of results (leading B
+        after to_streams); results gains dup_keep and dup_of.  It reads the decode's outputs and writes none of them.  Off: nothing."""
+        if self.dedup is not None:
+            dk, of = ops.box_dedup(*(to_streams(results[k]) for k in ("boxes_3d", "scores_3d", "labels_3d", "keep")), **self.dedup)
+            results["dup_keep"], results["dup_of"] = from_streams(dk), from_streams(of)
 
     def _track_update(self, results, idx, scores, hss, mem_track, next_id, mem_hits=None):
         """One far3d_track_update launch for the B streams of results / idx / scores (leading B; hss: their _head_prepare results): the
@@ -1405,8 +1455,8 @@ class Far3DEngine:
                 m_ref = torch.cat([hs.m["ref"] for hs in hss], out=self._buf(("trk_ref", B), (B, L, 3), torch.float32))
                 m_ts = torch.cat([hs.m["ts"] for hs in hss], out=self._buf(("trk_ts", B), (B, L, 1), torch.float64)).view(B, L)
             results["track_age"], results["track_primary"], results["track_velocity"] = ops.track_records(
-                idx, mem_track, mem_hits, results["query_idx"], results["track_ids"], results["keep"], results["boxes_3d"], m_ref, m_ts,
-                A, A - P, P)
+                idx, mem_track, mem_hits, results["query_idx"], results["track_ids"], results.get("dup_keep", results["keep"]),
+                results["boxes_3d"], m_ref, m_ts, A, A - P, P)      # dedup on: the primary is the first SURVIVING box of its id
 
     def _head_finish_streams(self, hss, outs_dec, enter, track=None):
         """_head_finish for B scene streams (streams.StreamBatch): hss the B _head_prepare results, outs_dec decoder_streams' result
@@ -1428,6 +1478,7 @@ class Far3DEngine:
             ops.head_finalize(rr[b], hs.ref, CLS[b], cfg["pc_range"], nl, ncls, hole=hs.hole, out=(BOX[b], SC[b]))
         results, idx = self.decode_streams(CLS.view(B, nl, A, ncls)[:, -1], BOX.view(B, nl, A, code)[:, -1], SC, cfg["topk_proposals"],
                                            tracked=self.track is not None)
+        self._box_dedup(results)
         if self.track is not None:
             self._track_update(results, idx, SC, hss, *track)
         res = []

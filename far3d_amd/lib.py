@@ -102,6 +102,7 @@ SIGNATURES = {
                                           _p, _p, _p, c_long, _p]),
     "far3d_track_update": (c_int, [_p] * 6 + [c_int] * 7 + [ctypes.c_double, _p, _p]),
     "far3d_track_records": (c_int, [_p] * 12 + [c_int] * 8 + [_p, _p]),
+    "far3d_box_dedup": (c_int, [_p] * 7 + [c_int] * 5 + [ctypes.c_double, ctypes.c_double, _p, _p]),
     "far3d_camera_prep": (c_int, [_p, _p, _p, _p, _p, c_int, _p]),
     "far3d_nan_to_num": (c_int, [_p, _p, c_long, _p]),
     "far3d_image_resample_h": (c_int, [_p, c_long, c_int, c_int, _p, _p, _p, c_int, c_int, c_int, c_int, c_int, _p]),

@@ -2329,6 +2329,52 @@ def track_records(topk_idx, mem_track, mem_hits, query_idx, track_ids, keep, box
     return age, primary, velocity
 
 
+DEDUP_MAX_DEC = 1024                          # csrc/dedup.hip
+DEDUP_MODES = ("iou_bev", "centre")           # far3d_box_dedup's mode 0 / 1
+
+
+def box_dedup(boxes, scores, labels, keep, mode="iou_bev", thr=0.5, class_aware=True, score_thr=0.0, return_overlaps=False):
+    """Duplicate suppression of the decoded boxes of B scene streams in ONE launch (far3d_box_dedup; the contract is in
+    include/far3d_hip.h and, executable, in tests/dedup_refs.py).  boxes (B, Kdec, >= 7) f32, scores (B, Kdec) f32, labels (B, Kdec)
+    int64, keep (B, Kdec) bool or uint8: the decode's outputs in its order; none is written.  Each stream's block contiguous, any
+    stride between the blocks.  mode 'iou_bev' (thr an IoU in [0, 1)) or 'centre' (thr a distance in metres > 0).  Returns (dup_keep
+    (B, Kdec) bool, dup_of (B, Kdec) int32[, overlaps (B, Kdec, Kdec) f32 with return_overlaps: the kernel's own overlap of every
+    judged pair, for inspection])."""
+    lib = _lib.require_device()
+    for t, name, dts in ((scores, "scores", (torch.float32,)), (labels, "labels", (torch.int64,)), (keep, "keep", (torch.bool, torch.uint8))):
+        if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.dtype not in dts or not t.is_cuda or (t.shape[1] > 1 and t.stride(1) != 1):
+            raise ValueError("box_dedup: %s must be a (B, Kdec) %s device tensor with unit inner stride" % (name, " or ".join(map(str, dts))))
+    if (not isinstance(boxes, torch.Tensor) or boxes.dim() != 3 or boxes.dtype != torch.float32 or not boxes.is_cuda or boxes.shape[2] < 7
+            or (boxes.numel() > 0 and boxes.stride(2) != 1)):
+        raise ValueError("box_dedup: boxes must be a (B, Kdec, >= 7) torch.float32 device tensor with unit inner stride")
+    B, Kdec = scores.shape
+    if B < 1 or any(tuple(t.shape[:2]) != (B, Kdec) for t in (boxes, labels, keep)):
+        raise ValueError("box_dedup: boxes %s, labels %s and keep %s must be (B=%d, Kdec=%d) like scores" %
+                         (tuple(boxes.shape), tuple(labels.shape), tuple(keep.shape), B, Kdec))
+    if Kdec > DEDUP_MAX_DEC:
+        raise ValueError("box_dedup: Kdec=%d boxes beyond far3d_box_dedup's %d" % (Kdec, DEDUP_MAX_DEC))
+    if mode not in DEDUP_MODES:
+        raise ValueError("box_dedup: mode=%r is none of %s" % (mode, ", ".join(DEDUP_MODES)))
+    thr, score_thr = float(thr), float(score_thr)
+    if mode == "iou_bev" and not 0.0 <= thr < 1.0:
+        raise ValueError("box_dedup: thr=%r is an IoU in [0, 1) (mode iou_bev)" % (thr,))
+    if mode == "centre" and not 0.0 < thr < float("inf"):
+        raise ValueError("box_dedup: thr=%r is a finite distance > 0 in metres (mode centre)" % (thr,))
+    if not 0.0 <= score_thr <= 1.0:
+        raise ValueError("box_dedup: score_thr=%r is a probability in [0, 1]" % (score_thr,))
+    dev = scores.device
+    dup_keep = torch.empty((B, Kdec), dtype=torch.bool, device=dev)
+    dup_of = torch.empty((B, Kdec), dtype=torch.int32, device=dev)
+    over = torch.empty((B, Kdec, Kdec), dtype=torch.float32, device=dev) if return_overlaps else None
+    ptr = lambda t: _ptr(t) if Kdec and t is not None else None
+    strides = (ctypes.c_long * 7)(boxes.stride(0), scores.stride(0), labels.stride(0), keep.stride(0), dup_keep.stride(0), dup_of.stride(0),
+                                  over.stride(0) if over is not None else 0)
+    _lib.check(lib.far3d_box_dedup(ptr(boxes), ptr(scores), ptr(labels), ptr(keep), ptr(dup_keep), ptr(dup_of), ptr(over), B, Kdec,
+                                   boxes.stride(1) if Kdec else boxes.shape[2], DEDUP_MODES.index(mode), 1 if class_aware else 0, thr,
+                                   score_thr, ctypes.cast(strides, ctypes.c_void_p), _stream(scores)), "far3d_box_dedup")
+    return (dup_keep, dup_of, over) if return_overlaps else (dup_keep, dup_of)
+
+
 def camera_prep(lidar2img, intrinsics=None, extrinsics=None):
     """lidar2img / intrinsics / extrinsics (N,4,4) f32 -> (img2lidar (N,4,4) = inverse(lidar2img), c14 (N,14) | None)."""
     lib = _lib.require_device()

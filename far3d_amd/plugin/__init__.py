@@ -844,11 +844,12 @@ class FarHead(_SchemaModule):
     def get_bboxes(self, preds_dicts, img_metas, rescale=False):
         """ref farhead.py:1224-1245 -> [[boxes, scores, labels]] (boxes wrapped in img_metas[0]['box_type_3d'] when given).  With
         tracking on (the engine's cfg track) the list has a fourth entry, the kept boxes' track ids (int64; 0 = none); with track
-        records=True three more behind it: their ages (int32), primary flags (bool) and velocities ((n, 3) f32)."""
+        records=True three more behind it: their ages (int32), primary flags (bool) and velocities ((n, 3) f32).  With duplicate
+        suppression on (cfg dedup) the rows are those of `dup_keep` instead of `keep`."""
         r = preds_dicts.get("_far3d_result")
         if r is None:
             r = self._eng.decode(preds_dicts["all_cls_scores"], preds_dicts["all_bbox_preds"])
-        keep = r["keep"]
+        keep = r.get("dup_keep", r["keep"])      # duplicate suppression on: the survivors, a subset of keep
         boxes, scores, labels = r["boxes_3d"][keep], r["scores_3d"][keep], r["labels_3d"][keep]
         box_type = img_metas[0].get("box_type_3d")
         if box_type is not None:
@@ -866,7 +867,7 @@ class Far3D(nn.Module):
 
     def __init__(self, use_grid_mask=False, img_backbone=None, img_neck=None, pts_bbox_head=None, img_roi_head=None,
                  train_cfg=None, test_cfg=None, stride=(16,), position_level=(0,), aux_2d_only=True, single_test=False,
-                 pretrained=None, proposal_topk=None, proposal_capacity=None, track=None, **kwargs):
+                 pretrained=None, proposal_topk=None, proposal_capacity=None, track=None, dedup=None, **kwargs):
         super().__init__()
         self.img_backbone = BACKBONES.build(img_backbone)
         self.img_neck = NECKS.build(img_neck)
@@ -879,6 +880,7 @@ class Far3D(nn.Module):
         # the device (None = the legacy form with a host sync on M); see INTEGRATION.md "Proposal modes"
         self.proposal_capacity = proposal_capacity
         self.track = track                     # build-side extension: track ids (None = off; True or dict(birth_thr=p, records=bool)); prepare(track=) too
+        self.dedup = dedup                     # build-side extension: duplicate suppression (None = off; True or engine.dedup_options' dict); prepare(dedup=) too
         self.engine = None
         self.eval()
 
@@ -910,17 +912,21 @@ class Far3D(nn.Module):
                           depth_max=r.depthnet_config.get("depth_max", 110.0), stride=r.depthnet_config.get("stride", 8)),
             score_thr=r.threshold_score, proposal_topk=self.proposal_topk, proposal_capacity=self.proposal_capacity,
             multi_depth=dict(h.multi_depth_config), roi_depthwise=r.use_depthwise, depth_level=r.depth_level,
-            track=dict(birth_thr=0.0) if self.track is True else (self.track or None))
+            track=dict(birth_thr=0.0) if self.track is True else (self.track or None), dedup=None if self.dedup is None or self.dedup is False else self.dedup)
 
-    def prepare(self, device="cuda:0", precision="bf16", fused_dwsep=False, track=None):
+    def prepare(self, device="cuda:0", precision="bf16", fused_dwsep=False, track=None, dedup=None):
         """Fold BN, pack weights for the kernels, upload.  Must be called again after loading new weights.
         fused_dwsep: the engine's opt-in of the same name -- the depthwise-separable layers of a light model (depthwise backbone specs,
         use_depthwise towers) as one launch each where the fused kernel takes them (engine.dwsep_layers).
         track: True or dict(birth_thr=p) switches the track ids on (None keeps the constructor's `track`): simple_test then adds
         `track_ids_3d` to pts_bbox, FarHead.get_bboxes a fourth list entry (INTEGRATION.md "Track ids").  dict(records=True) also adds
-        `track_age_3d`, `track_primary_3d`, `track_velocity_3d` and three more list entries (INTEGRATION.md "Track records")."""
+        `track_age_3d`, `track_primary_3d`, `track_velocity_3d` and three more list entries (INTEGRATION.md "Track records").
+        dedup: True or dict(mode=, thr=, class_aware=, score_thr=) switches the duplicate suppression on (None keeps the constructor's
+        `dedup`): simple_test and FarHead.get_bboxes then return the rows of `dup_keep` (INTEGRATION.md "Duplicate suppression")."""
         if track is not None:
             self.track = track
+        if dedup is not None:
+            self.dedup = dedup
         self.engine = _engine.Far3DEngine(self.state_dict(), self.engine_cfg(), device=device, precision=precision)
         self.engine.fused_dwsep = bool(fused_dwsep)
         return self
@@ -949,7 +955,7 @@ class Far3D(nn.Module):
         if self.proposal_capacity is not None:
             self.engine.check_proposal_overflow()      # a frame that did not fit the reserved rows is an error, never a silent truncation
         r = outs["result"]
-        keep = r["keep"]
+        keep = r.get("dup_keep", r["keep"])      # duplicate suppression on: the survivors, a subset of keep
         res = dict(boxes_3d=r["boxes_3d"][keep], scores_3d=r["scores_3d"][keep], labels_3d=r["labels_3d"][keep])
         if "track_ids" in r:
             res["track_ids_3d"] = r["track_ids"][keep]      # kept rows only, like the boxes (0 = no identity)

@@ -22,6 +22,7 @@ head_finalize masks each stream's hole.  No host sync in any mode; check_proposa
 Track ids (engine cfg track): the streams' id queues and counters are rows of one tensor each, so head_batch updates all of them in ONE
 far3d_track_update launch; every stream's ids are those of a plain engine fed its frames.  Track records (track records=True): the
 streams' hit counters are the rows of a third tensor, updated by ONE far3d_track_records launch behind the ids.
+Duplicate suppression (engine cfg dedup): head_batch makes ONE far3d_box_dedup launch behind the joint decode, a workgroup per stream.
 Everything else is refused with a ValueError that names the option."""
 import contextlib
 import functools

@@ -824,6 +824,30 @@ int far3d_track_records(const int64_t* topk_idx, const int64_t* mem_track, const
                         int32_t* track_age, unsigned char* track_primary, float* track_velocity, int B, int A, int K, int L, int Kdec,
                         int row_start, int P, int box_stride, const long* batch_strides, void* stream);
 
+/* Duplicate suppression of the decoded boxes by their rotated bird's-eye-view footprints (far3d_amd/csrc/dedup.hip; executable in
+ * tests/dedup_refs.py).  One launch for B >= 1 streams (one workgroup each), no host read, no atomics.  Inputs per stream, in the
+ * decode's order (descending score): boxes (Kdec rows of box_stride >= 7 floats: x, y, z, d3, d4, h, yaw, ...), scores (Kdec) f32,
+ * labels (Kdec) int64, keep (Kdec) bytes.  None is written.
+ *  - a box is a CANDIDATE iff keep != 0, its score is finite and (double)score >= score_thr;
+ *  - its footprint is the rectangle centred at (x, y) that extends d3 along (cos yaw, sin yaw) and d4 along (-sin yaw, cos yaw);
+ *  - a candidate with a non-finite x, y, d3, d4 or yaw, or with d3 <= 0 or d4 <= 0, is UNJUDGEABLE: it neither suppresses nor is
+ *    suppressed;
+ *  - a JUDGED pair is (j, i), j < i, both judgeable candidates, with equal labels if class_aware != 0.  Its overlap o: mode 0
+ *    (iou_bev) the IoU of the two footprints, a hit iff o > thr; mode 1 (centre) the squared distance of the centres in m^2, a hit
+ *    iff o < thr * thr;
+ *  - greedy in index order: box i is suppressed iff a j < i with dup_keep[j] = 1 hits it (a suppressed box suppresses nobody).
+ * Outputs: dup_keep (Kdec) bytes, 1 exactly for candidates that are not suppressed; dup_of (Kdec) int32, the smallest surviving j
+ * that hit i, -1 for every box that is not suppressed.  overlap_out: NULL, or (Kdec, Kdec) f32 whose entry [i][j] is the fp32 o of
+ * the judged pair (j, i) -- 0 where mode 0 rejects the pair by the distance of the centres against the sum of the circumradii --
+ * and 0 everywhere else.  The arithmetic is fp32 in the suppressor's frame; the contract is the exact value on the fp32 inputs, so a
+ * pair whose o lies within rounding of thr may fall on either side.  Kdec <= 1024 (0: nothing is written); thr in [0, 1) for mode 0,
+ * finite and > 0 for mode 1; score_thr in [0, 1].  batch_strides: 7 longs on the HOST, elements between stream b and b + 1 of boxes,
+ * scores, labels, keep, dup_keep, dup_of, overlap_out (for B > 1 none below one stream's extent; the last is not read with
+ * overlap_out NULL). */
+int far3d_box_dedup(const float* boxes, const float* scores, const int64_t* labels, const unsigned char* keep,
+                    unsigned char* dup_keep, int32_t* dup_of, float* overlap_out, int B, int Kdec, int box_stride, int mode,
+                    int class_aware, double thr, double score_thr, const long* batch_strides, void* stream);
+
 /* Per-frame camera calibration in one launch: img2lidar (N,4,4) = inverse(lidar2img) (ref models/dense_heads/farhead.py:798;
  * Gauss-Jordan with partial pivoting in f64) and c14 (N,14) = [fx/1e3, fy/1e3, extrinsics[:3,:4]] (ref farhead.py:553-556).
  * Either output may be NULL. */
